@@ -2,14 +2,22 @@
 """bench.py -- the SCDA hot path on MI355X: VGG16 Faster-R-CNN + 4-cluster SCDA training iteration
 (forward + backward + gradient all-reduce + Adam, all four optimiser phases), synthetic 512x1024 input, batch 1/GPU.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N > 1: either started by itself -- it then launches N ranks, one per GPU -- or under
    `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`)
 
 One "step" = one iteration = 1 source + 1 target 512x1024 image per GPU; images/s = 2 * N * steps / time (as in the
 reference, the source image goes forward AND backward, the target image forward only -- it has no loss; `config.iters_per_s`
-is the iteration rate for comparisons with iteration-based numbers).
-Prints ONE JSON line (rank 0).  Extra objects:
+is the iteration rate for comparisons with iteration-based numbers).  `ms_per_step` = wall time of the K timed steps / K.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and prints the headline figure, nothing else.
+--dump-outputs DIR  after the timed steps, rank 0 writes what the last timed step computed as DIR/<name>.npy: every entry of the
+                    dict ScdaTrainer.step returns (float32 scalars) and a fixed, seeded sample of each net's parameters after
+                    that step's optimiser updates (param_sample_<net>.npy, float32, at most 2^20 values per net).  The inputs
+                    and initial weights are seeded, so two builds run with the same arguments can be compared file by file.
+--full              also everything beside the headline figure (the extra objects below: event-pair timing of the dominant
+                    kernel and of the trainer's segments inside the timed region, extra profiled iterations after it, host CPU
+                    time, the CPU baseline).
+Extra objects (--full only):
   roofline      dominant kernel (fp32-MFMA implicit-GEMM conv forward with direct-to-LDS staging, 3x3 stride 1, 128- or 256-row tiles): algorithmic FLOPs of its
                 launches inside the timed region / their summed duration (HIP events recorded on the launch stream by the
                 library's profiler), against the 157.3 TFLOP/s fp32-MFMA peak
@@ -17,7 +25,8 @@ Prints ONE JSON line (rank 0).  Extra objects:
                 work per iteration, SURVEY.md 8d / BASELINE.md 2) x iterations/s
   cpu_baseline  the CPU oracle of the same iteration (oracle/torch_ref.py, a faithful PyTorch-CPU restatement of the
                 reference's train() body, pinned against the reference) timed on this box's host cores: rank 0, N=1 only;
-                1 warm-up + 3 timed iterations
+                1 warm-up + 3 timed iterations; --no-cpu-baseline leaves it out
+  segments, host  device time between the trainer's phase marks, CPU time of the enqueueing thread / process per step
 Before timing, the detector is pre-conditioned: warm-up iterations continue (up to 40) until the RPN yields the
 full post-NMS quota on both images, so that NMS / RoI sampling see realistic proposal sets; the counts are in the JSON.
 """
@@ -146,6 +155,32 @@ def synth_batch(rank, H=H, W=W):
     return src, tgt, gts, torch.tensor([[H, W, 1.0]])
 
 
+DUMP_SAMPLE = 1 << 20          # parameter values per net in --dump-outputs (4 nets x 4 MB)
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(d, out, tr):
+    """--dump-outputs: what the last timed step computed, as <d>/<name>.npy -- the step's returned dict (one float32 scalar per
+    entry) and, per net, the parameters after the step's optimiser update (all of them when there are at most DUMP_SAMPLE, else the
+    values at the distinct ones of DUMP_SAMPLE indices drawn from a seeded generator, ascending, over the net's parameters in
+    named_parameters() order)"""
+    os.makedirs(d, exist_ok=True)
+    arrays = {}
+    for k, v in out.items():
+        t = torch.as_tensor(v).detach().cpu()
+        arrays[k] = t.numpy().astype(np.float64 if t.dtype == torch.float64 else np.float32)
+    for name, m in (("det", tr.model), ("dec", tr.dec), ("dis", tr.dis), ("dis_patch", tr.dis_patch)):
+        flat = torch.cat([p.detach().reshape(-1) for _, p in m.named_parameters()])
+        if flat.numel() > DUMP_SAMPLE:
+            idx = np.unique(np.random.RandomState(7).randint(0, flat.numel(), DUMP_SAMPLE))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        arrays["param_sample_" + name] = flat.float().cpu().numpy()
+    total = sum(x.nbytes for x in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, total
+    for k, x in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), x)
+
+
 def pmc_traffic(kernel, prefix=""):
     """-> (bytes per launch, source file, launches averaged, algorithmic bytes per launch of the SAME launches or None, traffic / 8-L2 floor or None)"""
     t = _pmc_traffic(kernel, prefix)
@@ -250,11 +285,17 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)    # ~4 s of device work: long enough for an outside observer (the driver's gpu_busy sampler) to see the GPU
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--config", choices=["vgg16", "resnet50", "maskrcnn"], default="vgg16",
                     help="vgg16 = BASELINE.json configs[1] (the metric's configuration, default); resnet50 = configs[3]'s detector "
                          "(ResNet-50 C4 + SCDA at 800x1344, performance-only: the reference has no runnable model for it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (losses, a seeded sample of the updated parameters) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also roofline / segment / host figures and the CPU baseline (the plain run measures the headline figure only)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     rank = int(os.environ.get("RANK", 0))
     world = int(os.environ.get("WORLD_SIZE", 1))
@@ -326,10 +367,10 @@ def main():
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
-    # event pairs around the dominant kernel only: they are queue markers.  VGG (the judged configuration): 24 launches per
+    # --full: event pairs around the dominant kernel only: they are queue markers.  VGG (the judged configuration): 24 launches per
     # iteration, timed INSIDE the timed region.  ResNet: its dominant class is 86 launches per iteration, so it is timed in a
     # separate pass after the timed region (3 more iterations) and the throughput number stays unperturbed.
-    in_region = a.config == "vgg16"
+    in_region = a.config == "vgg16" and a.full
     dom_list = list(dominant) if isinstance(dominant, tuple) else [dominant]
     # An event pair is two queue markers, and a launch behind a marker starts ~6 us after the kernel in front of it has ended where
     # an unmarked one follows back to back: with the pairs around all 39 Winograd launches of EVERY timed iteration the iteration is
@@ -367,17 +408,19 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if a.dump_outputs and rank == 0:      # before --full's extra iterations move the parameters on
+        dump_outputs(a.dump_outputs, out, tr)
     in_region_timed = in_region
     mask_rois = getattr(tr.model, "last_mask_rois", None) if a.config == "maskrcnn" else None
     if mask_rois is not None:
         f_iter += RC.mask_branch_tflop(mask_rois)
-    if not in_region:
+    if a.full and not in_region:
         native.prof_enable(dom_list)
         for _ in range(3):
             tr.step(src, gts, info, tgt, **step_kw)
         torch.cuda.synchronize()
     native.prof_enable(False)
-    prof = native.prof_collect()
+    prof = native.prof_collect() if a.full else {}
     template = None
     if os.environ.get("SCDA_BENCH_NO_TEMPLATE_PASS"):     # profile collection: keep the trace to the warm-up + timed iterations
         in_region = False
@@ -496,18 +539,22 @@ def main():
                        "images_per_step": "1 source (forward + backward) + 1 target (forward only: it carries no loss), per GPU",
                        "proposals_post_nms": {"source": tr.last_num_proposals[0], "target": tr.last_num_proposals[1], "quota": quota},
                        "preconditioning_iterations": a.warmup + precond},
-            "roofline": roof,
-            # where the iteration's time is (verdict r05 item 2): device time by segment, and what the host spent
-            "segments": segments,
-            "host_ms_per_step": round(cpu_main / a.steps * 1e3, 3),
-            "host": {"main_thread_cpu_ms_per_step": round(cpu_main / a.steps * 1e3, 3),
-                     "process_cpu_ms_per_step": round(cpu_proc / a.steps * 1e3, 3),
-                     "note": "CPU time over the timed region / steps; the main thread enqueues the whole iteration and spins while it waits "
-                             "for a device result (RPN outputs, keep lists), so main-thread time ~ wall time unless blocking waits are on",
-                     "cpu_quota": _hostenv.cpu_quota(), "cpu_count": os.cpu_count()},
         }
-        if world == 1 and not a.no_cpu_baseline:
-            res["cpu_baseline"] = cpu_baseline() if a.config == "vgg16" else cpu_baseline_resnet(a.config == "maskrcnn")
+        if a.full:
+            res.update({
+                "roofline": roof,
+                # where the iteration's time is (verdict r05 item 2): device time by segment, and what the host spent
+                "segments": segments,
+                "host_ms_per_step": round(cpu_main / a.steps * 1e3, 3),
+                "host": {"main_thread_cpu_ms_per_step": round(cpu_main / a.steps * 1e3, 3),
+                         "process_cpu_ms_per_step": round(cpu_proc / a.steps * 1e3, 3),
+                         "note": "CPU time over the timed region / steps; the main thread enqueues the whole iteration and spins while it "
+                                 "waits for a device result (RPN outputs, keep lists), so main-thread time ~ wall time unless blocking "
+                                 "waits are on",
+                         "cpu_quota": _hostenv.cpu_quota(), "cpu_count": os.cpu_count()},
+            })
+            if world == 1 and not a.no_cpu_baseline:
+                res["cpu_baseline"] = cpu_baseline() if a.config == "vgg16" else cpu_baseline_resnet(a.config == "maskrcnn")
         print(json.dumps(res), flush=True)
     if world > 1:
         dist.barrier()

@@ -45,7 +45,7 @@ bash scripts/collect_profiles.sh $TAG > $OUT/collect.log 2>&1
 export SCDA_BENCH_NO_TEMPLATE_PASS=1
 python scripts/kernel_categories.py $OUT/kernel_stats.md 13 > $OUT/kernel_categories.md
 ( cd /tmp; export TMPDIR=/tmp
-  rocprofv3 --kernel-trace --output-format csv -d $OUT/kt_csv -o kt -- python $R/bench.py --steps 6 --warmup 3 --no-cpu-baseline > $OUT/kt_csv.log 2>&1 )
+  rocprofv3 --kernel-trace --output-format csv -d $OUT/kt_csv -o kt -- python $R/bench.py --full --steps 6 --warmup 3 --no-cpu-baseline > $OUT/kt_csv.log 2>&1 )
 python scripts/exposed_time.py "$OUT/kt_csv/*kernel_trace.csv" 6 > $OUT/exposed_time.md
 rm -rf $OUT/kt_csv
 python scripts/shape_budget.py > $OUT/shape_budget.txt 2> $OUT/shape_budget.err
@@ -53,22 +53,22 @@ python scripts/bench_conv_layers.py > $OUT/conv_layers.txt 2> $OUT/conv_layers.e
 python scripts/device_phase_times.py > $OUT/device_phase_times.txt 2>/dev/null
 python scripts/time_s2_dgrad.py > $OUT/s2_conv_layers.txt 2>/dev/null
 ( python scripts/host_cpu_use.py spin; python scripts/host_cpu_use.py block ) > $OUT/host_cpu.txt 2>/dev/null
-python bench.py --config resnet50 --steps 10 --warmup 4 --no-cpu-baseline > $OUT/resnet50_bench.json 2>/dev/null
-python bench.py --config maskrcnn --steps 10 --warmup 4 --no-cpu-baseline > $OUT/maskrcnn_bench.json 2>/dev/null
+python bench.py --full --config resnet50 --steps 10 --warmup 4 --no-cpu-baseline > $OUT/resnet50_bench.json 2>/dev/null
+python bench.py --full --config maskrcnn --steps 10 --warmup 4 --no-cpu-baseline > $OUT/maskrcnn_bench.json 2>/dev/null
 mkdir -p $OUT/maskrcnn
 bash scripts/kt.sh $TAG/maskrcnn "--config maskrcnn" > $OUT/maskrcnn/kernel_categories.md 2>/dev/null
 mkdir -p $OUT/resnet50
 bash scripts/kt.sh $TAG/resnet50 "--config resnet50" > $OUT/resnet50/kernel_categories.md 2>/dev/null
 ( cd /tmp; export TMPDIR=/tmp
-  rocprofv3 --kernel-trace --output-format csv -d $OUT/kt_csv -o kt -- python $R/bench.py --config resnet50 --steps 6 --warmup 3 --no-cpu-baseline > $OUT/kt_csv.log 2>&1 )
+  rocprofv3 --kernel-trace --output-format csv -d $OUT/kt_csv -o kt -- python $R/bench.py --full --config resnet50 --steps 6 --warmup 3 --no-cpu-baseline > $OUT/kt_csv.log 2>&1 )
 python scripts/exposed_time.py "$OUT/kt_csv/*kernel_trace.csv" 6 > $OUT/resnet50/exposed_time.md
 rm -rf $OUT/kt_csv
 # counter passes for the ResNet-50 C4 configuration (FETCH_SIZE / WRITE_SIZE separately, then the MFMA pipe): PMC only + kernel trace
 ( cd /tmp; export TMPDIR=/tmp
   for c in FETCH_SIZE WRITE_SIZE; do
-    timeout 300 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $OUT/resnet50/pmc_$c -o pmc -- python $R/bench.py --config resnet50 --steps 2 --warmup 1 --no-cpu-baseline > $OUT/resnet50/pmc_$c.log 2>&1
+    timeout 300 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $OUT/resnet50/pmc_$c -o pmc -- python $R/bench.py --full --config resnet50 --steps 2 --warmup 1 --no-cpu-baseline > $OUT/resnet50/pmc_$c.log 2>&1
   done
-  timeout 300 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $OUT/resnet50/pmc_mfma -o pmc -- python $R/bench.py --config resnet50 --steps 2 --warmup 1 --no-cpu-baseline > $OUT/resnet50/pmc_mfma.log 2>&1 )
+  timeout 300 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $OUT/resnet50/pmc_mfma -o pmc -- python $R/bench.py --full --config resnet50 --steps 2 --warmup 1 --no-cpu-baseline > $OUT/resnet50/pmc_mfma.log 2>&1 )
 python scripts/pmc_summary.py $OUT/resnet50 $OUT/resnet50/pmc_traffic.md $OUT/resnet50/pmc_traffic.json resnet > /dev/null
 python scripts/pmc_mfma_summary.py $OUT/resnet50/pmc_mfma/pmc_counter_collection.csv $OUT/resnet50/pmc_mfma.md > /dev/null
 python scripts/host_budget_8ranks.py spin > $OUT/host_budget.txt 2>/dev/null

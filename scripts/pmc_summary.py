@@ -112,7 +112,7 @@ def main(d, out_md, out_json, which=None):
         like["traffic_over_algorithmic"] = round(like["traffic_bytes_per_launch"] / like["algorithmic_bytes_per_launch"], 3)
     with open(out_md, "w") as f:
         f.write("# rocprofv3 PMC: L2 memory-side traffic per launch\n\n")
-        f.write("Two passes of `python bench.py --steps 2 --warmup 1 --no-cpu-baseline" + (" --config resnet50" if which == "resnet" else "") + "`: `rocprofv3 --pmc FETCH_SIZE --kernel-trace` and\n"
+        f.write("Two passes of `python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline" + (" --config resnet50" if which == "resnet" else "") + "`: `rocprofv3 --pmc FETCH_SIZE --kernel-trace` and\n"
                 "`rocprofv3 --pmc WRITE_SIZE --kernel-trace` (counters never combined, no other trace domains).  read = 2 x FETCH_SIZE KB\n"
                 "(gfx950 counts 64 B per 128-byte request), write = WRITE_SIZE KB.  Infinity-Cache hits are counted, so these are\n"
                 "bytes leaving the L2, an upper bound on HBM bytes.\n\n")

@@ -4,7 +4,9 @@ resolves -- the replaced symbols come from this repository, everything else from
 callable accepts the reference's positional arguments (signatures compared against the reference sources by `ast`, because
 the reference's ffi-era modules cannot be imported on torch 2.x).  Runs in a subprocess: the import installs stubs for the
 third-party packages this image lacks (cv2, torchvision, the compiled pycocotools mask module) and sets the
-multiprocessing start method.  CPU only, skipped where /root/reference is absent (the GPU box)."""
+multiprocessing start method.  The import check needs the reference checkout and is skipped without it; the signature check
+compares with the reference's parameter names recorded in tests/golden/dropin_ref_params.json
+(tests/golden/make_golden_dropin.py) and runs everywhere.  CPU only."""
 import ast
 import json
 import os
@@ -17,7 +19,6 @@ import pytest
 from conftest import ROOT
 
 REF = os.environ.get("SCDA_REFERENCE", "/root/reference")
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout not present")
 
 PROBE = textwrap.dedent(r'''
     import inspect, json, os, sys, types
@@ -131,8 +132,30 @@ def reference_params(path, qual):
     return names[1:] if names and names[0] in ("self", "ctx") else names   # roi_pool.py:7 calls its `self` "ctx"
 
 
+# the replaced callables resolved from the drop-in alone (no reference on sys.path): the module at the reference file's path, the
+# attribute at its qualified name -- the objects PROBE reaches through the reference's driver (the focal-loss Functions' forward is
+# their __call__ there too)
+LOCAL_PROBE = textwrap.dedent(r'''
+    import importlib, inspect, json, os, sys
+    root, keys = sys.argv[1], json.loads(sys.argv[2])
+    sys.path[:0] = [os.path.join(root, "scda_amd", "dropin"), root]
+    out = {"files": {}, "sigs": {}}
+    for key in keys:
+        path, qual = key.split(":")
+        obj = importlib.import_module(path[:-3].replace("/", "."))
+        for part in qual.split("."):
+            obj = getattr(obj, "__call__" if path.startswith("extensions/_focal_loss/") and part == "forward" else part)
+        out["files"][key] = os.path.realpath(inspect.getsourcefile(obj))
+        out["sigs"][key] = [p.name for p in inspect.signature(obj).parameters.values()
+                            if p.kind in (p.POSITIONAL_ONLY, p.POSITIONAL_OR_KEYWORD) and p.name != "self"]
+    print("PROBE" + json.dumps(out))
+''')
+
+
 @pytest.fixture(scope="module")
 def probe():
+    if not os.path.isdir(REF):
+        pytest.skip("reference checkout not present")
     r = subprocess.run([sys.executable, "-c", PROBE, ROOT, REF], capture_output=True, text=True, timeout=600,
                        env=dict(os.environ, PYTHONPATH=""))
     line = [l for l in r.stdout.splitlines() if l.startswith("PROBE")]
@@ -153,13 +176,23 @@ def test_reference_driver_imports_with_dropin_first(probe):
         assert probe["files"][k].startswith(ref), (k, probe["files"][k])
 
 
-def test_replaced_callables_accept_the_reference_arguments(probe):
+def test_replaced_callables_accept_the_reference_arguments(golden_dir):
     """every positional parameter of the reference's definition exists, in the same position, in the replacement (the
     replacement may append optional ones, e.g. async_op / max_keep)"""
+    with open(os.path.join(golden_dir, "dropin_ref_params.json")) as f:
+        ref_params = json.load(f)
+    r = subprocess.run([sys.executable, "-c", LOCAL_PROBE, ROOT, json.dumps(sorted(ref_params))], capture_output=True, text=True,
+                       timeout=600, env=dict(os.environ, PYTHONPATH=""))
+    line = [l for l in r.stdout.splitlines() if l.startswith("PROBE")]
+    assert r.returncode == 0 and line, r.stdout[-2000:] + r.stderr[-4000:]
+    local = json.loads(line[0][5:])
+    mine = os.path.realpath(os.path.join(ROOT, "scda_amd", "dropin")) + os.sep
+    assert all(v.startswith(mine) for v in local["files"].values()), local["files"]
+    assert len(ref_params) == 37
     bad = {}
-    for key, got in probe["sigs"].items():
-        path, qual = key.split(":")
-        want = reference_params(path, qual)
+    for key, want in ref_params.items():
+        got = local["sigs"][key]
         if got[:len(want)] != want:
             bad[key] = (want, got)
     assert not bad, bad
+

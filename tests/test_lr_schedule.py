@@ -1,14 +1,13 @@
-"""FlatAdam is a torch.optim.Optimizer: the reference's per-iteration warm-up scheduler (utils/lr_helper.py, imported from the
-reference checkout where present), this repository's restatement of it, and torch's MultiStepLR all drive it; state_dict()
-round-trips.  CPU only (no kernel is launched: schedulers and state handling are host logic)."""
-import importlib.util
+"""FlatAdam is a torch.optim.Optimizer: the reference's per-iteration warm-up scheduler (utils/lr_helper.py; what it did driving
+FlatAdam is recorded in tests/golden/lr_warmup_ref.npz by tests/golden/make_golden_lr.py), this repository's restatement of it,
+and torch's MultiStepLR all drive it; state_dict() round-trips.  CPU only (no kernel is launched: schedulers and state handling
+are host logic)."""
 import os
 
+import numpy as np
 import pytest
 import torch
 import torch.nn as nn
-
-REF_LR = "/root/reference/utils/lr_helper.py"
 
 
 def small_flat():
@@ -33,18 +32,11 @@ def test_flat_adam_is_a_torch_optimizer_and_multisteplr_drives_it():
 
 
 @pytest.mark.parametrize("which", ["product", "reference"])
-def test_iter_exponential_warmup(which):
-    """(world_size * batch)**(1/(n-1)) per iteration: iteration k of n runs at base * gamma**(k-1); then initial_lr <- lr"""
-    from scda_amd.lr_schedule import warmup_gamma
-    if which == "reference":
-        if not os.path.exists(REF_LR):
-            pytest.skip("reference checkout not present")
-        spec = importlib.util.spec_from_file_location("ref_lr_helper", REF_LR)
-        mod = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(mod)
-        Sched = mod.IterExponentialLR       # type-checks `isinstance(optimizer, Optimizer)` (lr_helper.py:6-8)
-    else:
-        from scda_amd.lr_schedule import IterExponentialLR as Sched
+def test_iter_exponential_warmup(which, golden_dir):
+    """(world_size * batch)**(1/(n-1)) per iteration: iteration k of n runs at base * gamma**(k-1); then initial_lr <- lr.
+    `reference`: the product's scheduler reproduces, on FlatAdam, exactly what the reference's IterExponentialLR did on it
+    (recorded values; the reference type-checks `isinstance(optimizer, Optimizer)`, lr_helper.py:6-8)"""
+    from scda_amd.lr_schedule import IterExponentialLR as Sched, warmup_gamma
     net, flat, opt = small_flat()
     gamma = warmup_gamma(8, 1, 4)
     s = Sched(opt, gamma)
@@ -56,6 +48,11 @@ def test_iter_exponential_warmup(which):
     assert seen == pytest.approx([1e-3, 2e-3, 4e-3, 8e-3])
     with pytest.raises(TypeError):
         Sched(object(), gamma)
+    if which == "reference":
+        g = np.load(os.path.join(golden_dir, "lr_warmup_ref.npz"))
+        assert float(g["gamma"]) == gamma and bool(g["type_error"])
+        assert float(g["lr0"]) == 1e-3 and float(g["initial_lr"]) == 1e-3
+        assert seen == g["seen"].tolist()
 
 
 def test_state_dict_round_trip_and_alias_checks():
