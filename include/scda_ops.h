@@ -229,6 +229,35 @@ int scda_box_predict_hip(const float *rois, const int *roi_counts, int B, int P,
                          const float *image_info, int info_stride, const double *stds_host, const double *means_host,
                          float score_thresh, float nms_thresh, int top_n, void *ws, float *det, int *det_counts, void *stream);
 
+/* ---- instance masks of the mask-branch detector (scda_amd/csrc/mask_ops.hip; opt-in: scda_amd.infer.Predictor(masks=True)) ----------
+ * The detections as RoIs of the mask head: det [B, top_n, 7] + det_counts i32 [B] (scda_box_predict_hip's outputs) ->
+ * rois5 [B * top_n, 5] = (b, x1, y1, x2, y2) and cls i32 [B * top_n]; rows past an image's count are (b, 0, 0, 0, 0), class -1. */
+int scda_det_rois_hip(const float *detections, const int *detection_counts, int B, int top_n, float *rois5, int *cls, void *stream);
+/* Each RoI's own class plane: logits [R, C, ph, pw] addressed by ELEMENT strides (the tall channel-major view of the mask head or
+ * NCHW) + cls i32 [R] -> out [R, ph, pw] contiguous.  sigmoid != 0: 1 / (1 + e), e = the correctly rounded float32 exp(-x), float32
+ * add and divide (the Mask R-CNN definition; parity-unpinned: the reference's use of the heat map is in its missing mask_rcnn.py).
+ * Rows of class < 0 (padding) or >= C give zeros. */
+int scda_mask_select_hip(const float *logits, long long stride_r, long long stride_c, long long stride_h, long long stride_w,
+                         const int *cls, int R, int C, int ph, int pw, int sigmoid, float *out, void *stream);
+/* functions/mask.py:21-49 (predict_masks) under Pillow >= 7, one plane of [H, W] per RoI.  rois [R, roi_stride >= 5] float32
+ * (b, x1, y1, x2, y2, ...), planes [R, ph, pw] float32 (ph, pw <= 32), out: packed == 0: float32 [R, H, W]; packed != 0: uint32
+ * [R, H, ceil(W / 32)], bit (c % 32) of word c / 32 = (the float form's value >= threshold) -- outside the windows that value is
+ * 0.0f --, bits past W zero.  Every element of `out` is written (no clear needed).  Per RoI:
+ *   x1, y1, x2, y2 = the float32 values truncated towards zero; roi_w = x2 - x1 + 1, roi_h = y2 - y1 + 1;
+ *   the plane is resized to roi_h x roi_w as Pillow resizes a mode-F image with its default filter (BICUBIC, a = -0.5, support 2):
+ *   a horizontal pass into a float32 intermediate [ph, roi_w], then a vertical pass; a pass whose sizes are equal is skipped.  Per
+ *   output index xx of an axis n_in -> n_out: scale = n_in / n_out, fs = max(scale, 1), support = 2 fs, center = (xx + 0.5) scale,
+ *   xmin = max((int)(center - support + 0.5), 0), xmax = min((int)(center + support + 0.5), n_in),
+ *   w[k] = bicubic((k + xmin - center + 0.5) * (1.0 / fs)), ww = their left-to-right sum, w[k] /= ww if ww != 0; the sample is (float)
+ *   of the left-to-right double sum of (double)pixel * w[k].  bicubic(x), x = |x|: ((a + 2) x - (a + 3)) x x + 1 below 1,
+ *   (((x - 5) x + 8) x - 4) a below 2, else 0.  All in IEEE double, one operation per operator (no FMA contraction): Pillow's result
+ *   bit for bit (tests/test_mask_infer_rules.py);
+ *   the result lands at rows y1.., columns x1.. of a zero plane.
+ * Where the reference would raise (the window leaves the plane) the part outside is DROPPED; roi_w <= 0 or roi_h <= 0, coordinates
+ * that are not finite or beyond +-5e8, and rows with cls_or_null[r] < 0 (padding) give an empty mask. */
+int scda_mask_paste_hip(const float *rois, int roi_stride, const int *cls_or_null, const float *planes, int R, int ph, int pw, int H,
+                        int W, int packed, float threshold, void *out, void *stream);
+
 /* ------------------------------------------------- convolution / GEMM ---- */
 /* The reference reaches these through torch.nn (cuDNN / cuBLAS): nn.Conv2d in
  * models/faster_rcnn/vgg_adver_expansion_cluster.py:101-114 (VGG body),

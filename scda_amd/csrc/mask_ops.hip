@@ -1,0 +1,255 @@
+// mask_ops.hip -- instance masks of the mask-branch detector on the device (gfx950): the detections' RoIs, the class plane of
+// each RoI's mask logits, and functions/mask.py:21-49 (`predict_masks`: the plane resized to the RoI by Pillow, pasted into the image).
+//
+// The resize is Pillow's ImagingResample on a mode-F image with its default filter since Pillow 7 (BICUBIC, a = -0.5, support 2):
+// a horizontal pass into a float32 intermediate, then a vertical pass; per output sample the double weights are normalised by their
+// left-to-right sum and the sample is (float) of the left-to-right double sum of (double)pixel * weight.  Every operation below is one
+// IEEE operation per source operator (compiled with -ffp-contract=off), which makes the result Pillow's bit for bit; the rule is
+// stated in include/scda_ops.h and restated in numpy by tests/test_mask_infer_rules.py.
+#include "common.h"
+
+namespace {
+using namespace scda;
+
+constexpr int kMaxIn = 32;                      // largest plane side (the mask head gives 28; the golden cases use 14)
+constexpr int kStrip = 128;                     // image columns per workgroup
+constexpr int kRows = 64;                       // image rows per vertical-table refill
+constexpr int kThreads = 256;
+constexpr int kTmpStride = kStrip + kStrip / 32;    // room for the bit form's one-in-32 padding
+// weights per axis and table: an up-scale (or identity) has at most 5 taps per sample, a down-scale at most n_in taps on at most
+// n_in - 1 samples
+constexpr int kTabH = kStrip * 5 > (kMaxIn - 1) * kMaxIn ? kStrip * 5 : (kMaxIn - 1) * kMaxIn;
+constexpr int kTabV = kRows * 5 > (kMaxIn - 1) * kMaxIn ? kRows * 5 : (kMaxIn - 1) * kMaxIn;
+
+__device__ inline double bicubic(double x) {
+    const double a = -0.5;
+    if (x < 0.0) x = -x;
+    if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1;
+    if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
+    return 0.0;
+}
+
+// the table stride of an axis n_in -> n_out: Pillow's ksize = ceil(support) * 2 + 1, never more than the n_in taps a sample can have
+__device__ inline int axis_ksize(int n_in, int n_out) {
+    if (n_in == n_out) return 1;
+    double fs = (double)n_in / n_out;
+    if (fs < 1.0) fs = 1.0;
+    const int ks = (int)ceil(2.0 * fs) * 2 + 1;
+    return ks < n_in ? ks : n_in;
+}
+
+// Pillow's precompute_coeffs for ONE output sample xx of an axis n_in -> n_out: first tap and tap count, normalised weights into w[]
+// (equal sizes: Pillow skips the pass -- one tap of weight 1 reproduces the sample)
+__device__ inline void axis_taps(int n_in, int n_out, int xx, int ks, int *first, int *count, double *w) {
+    if (n_in == n_out) {
+        *first = xx; *count = 1; w[0] = 1.0;
+        return;
+    }
+    const double scale = (double)n_in / n_out;
+    const double fs = scale < 1.0 ? 1.0 : scale;
+    const double support = 2.0 * fs, ss = 1.0 / fs;
+    const double center = (xx + 0.5) * scale;
+    int xmin = (int)(center - support + 0.5);
+    if (xmin < 0) xmin = 0;
+    int xmax = (int)(center + support + 0.5);
+    if (xmax > n_in) xmax = n_in;
+    int n = xmax - xmin;
+    if (n > ks) n = ks;
+    if (n < 0) n = 0;
+    double ww = 0.0;
+    for (int k = 0; k < n; ++k) {
+        const double v = bicubic((k + xmin - center + 0.5) * ss);
+        w[k] = v;
+        ww += v;
+    }
+    if (ww != 0.0)
+        for (int k = 0; k < n; ++k) w[k] /= ww;
+    *first = xmin; *count = n;
+}
+
+// float32 -> int as Python's int(): towards zero; what does not fit an int makes the RoI empty
+__device__ inline bool trunc_ok(float v, int *out) {
+    if (!(v > -5.0e8f && v < 5.0e8f)) return false;
+    *out = (int)v;
+    return true;
+}
+
+template <bool BITS> __device__ inline int tmp_col(int x) { return BITS ? x + (x >> 5) : x; }
+
+// grid (column strips, R), 256 threads.  A workgroup owns columns [c0, c0 + 128) of RoI r's plane and writes EVERY row of them.
+template <bool BITS>
+__global__ __launch_bounds__(kThreads) void mask_paste_kernel(const float *__restrict__ rois, int roi_stride, const int *__restrict__ cls,
+                                                              const float *__restrict__ planes, int ph, int pw, int H, int W, int Wd,
+                                                              float threshold, int vec4, void *__restrict__ out_) {
+    __shared__ float plane[kMaxIn * kMaxIn];
+    __shared__ __align__(16) float tmp[kMaxIn * kTmpStride];       // the horizontal pass: [ph][this strip's columns]
+    __shared__ double hw[kTabH], vw[kTabV];
+    __shared__ int hfirst[kStrip], hcount[kStrip], vfirst[kRows], vcount[kRows];
+    const int r = blockIdx.y, c0 = blockIdx.x * kStrip, t = threadIdx.x;
+    // ---- the RoI (uniform over the workgroup)
+    const float *roi = rois + (size_t)r * roi_stride;
+    int x1 = 0, y1 = 0, x2 = 0, y2 = 0;
+    bool live = !(cls && cls[r] < 0);
+    live = trunc_ok(roi[1], &x1) && live;
+    live = trunc_ok(roi[2], &y1) && live;
+    live = trunc_ok(roi[3], &x2) && live;
+    live = trunc_ok(roi[4], &y2) && live;
+    int roi_w = 0, roi_h = 0;
+    if (live) {
+        roi_w = x2 - x1 + 1; roi_h = y2 - y1 + 1;
+        live = roi_w > 0 && roi_h > 0;
+    }
+    // columns [ca, cb) of this strip and rows [ya, yb) of the plane lie inside the window
+    int ca = 0, cb = 0, ya = 0, yb = 0;
+    if (live) {
+        ca = x1 > c0 ? x1 : c0;
+        cb = min(min(x1 + roi_w, W), c0 + kStrip);
+        ya = y1 > 0 ? y1 : 0;
+        yb = min(y1 + roi_h, H);
+        live = ca < cb && ya < yb;
+    }
+    const int na = cb - ca;
+    int ksh = 1, ksv = 1;
+    if (live) {
+        ksh = axis_ksize(pw, roi_w); ksv = axis_ksize(ph, roi_h);
+        for (int i = t; i < ph * pw; i += kThreads) plane[i] = planes[(size_t)r * ph * pw + i];
+        for (int i = t; i < na; i += kThreads) axis_taps(pw, roi_w, ca + i - x1, ksh, &hfirst[i], &hcount[i], &hw[i * ksh]);
+        __syncthreads();
+        for (int i = t; i < ph * na; i += kThreads) {
+            const int row = i / na, xa = i - row * na;
+            const float *src = plane + row * pw + hfirst[xa];
+            const double *w = hw + xa * ksh;
+            double s = 0.0;
+            for (int k = 0; k < hcount[xa]; ++k) s += (double)src[k] * w[k];
+            tmp[row * kTmpStride + tmp_col<BITS>(ca - c0 + xa)] = (float)s;
+        }
+    }
+    for (int ybase = 0; ybase < H; ybase += kRows) {
+        const bool hit = live && ybase < yb && ybase + kRows > ya;
+        const int tv0 = ya > ybase ? ya : ybase;               // the first table row of this refill
+        __syncthreads();                                       // tmp is complete / the previous refill has been read
+        if (hit) {
+            const int nv = min(yb, ybase + kRows) - tv0;
+            for (int i = t; i < nv; i += kThreads) axis_taps(ph, roi_h, tv0 + i - y1, ksv, &vfirst[i], &vcount[i], &vw[i * ksv]);
+        }
+        __syncthreads();
+        if (BITS) {
+            // one row and one 32-column word per thread
+            const int y = ybase + (t >> 2), word = (c0 >> 5) + (t & 3);
+            if (y < H && word < Wd) {
+                // outside the window the plane is 0.0f: its bit is (0.0f >= threshold) like any other value's; columns past W stay clear
+                const int left = W - word * 32;
+                unsigned int bits = 0.f >= threshold ? (left >= 32 ? 0xffffffffu : (1u << left) - 1u) : 0u;
+                if (hit && y >= ya && y < yb) {
+                    const int ty = y - tv0, n = vcount[ty];
+                    const double *w = vw + ty * ksv;
+                    const float *col = tmp + vfirst[ty] * kTmpStride;
+                    const int cl = word * 32 - c0;
+                    for (int j = 0; j < 32; ++j) {
+                        const int c = word * 32 + j;
+                        if (c >= ca && c < cb) {
+                            double s = 0.0;
+                            for (int k = 0; k < n; ++k) s += (double)col[k * kTmpStride + tmp_col<true>(cl + j)] * w[k];
+                            bits = (float)s >= threshold ? bits | (1u << j) : bits & ~(1u << j);
+                        }
+                    }
+                }
+                ((unsigned int *)out_)[((size_t)r * H + y) * Wd + word] = bits;
+            }
+        } else {
+            // four adjacent columns per thread, eight rows per step
+            const int cl = (t & 31) * 4, c = c0 + cl;
+            float *out = (float *)out_;
+            for (int y = ybase + (t >> 5); y < min(ybase + kRows, H); y += kThreads / 32) {
+                float v[4] = {0.f, 0.f, 0.f, 0.f};
+                if (hit && y >= ya && y < yb && c < cb && c + 3 >= ca) {
+                    const int ty = y - tv0, n = vcount[ty];
+                    const double *w = vw + ty * ksv;
+                    const float *col = tmp + vfirst[ty] * kTmpStride + cl;
+                    double s[4] = {0.0, 0.0, 0.0, 0.0};
+                    for (int k = 0; k < n; ++k) {              // (columns outside the window read what LDS holds and are dropped below)
+                        const float4 p = *(const float4 *)(col + k * kTmpStride);
+                        s[0] += (double)p.x * w[k]; s[1] += (double)p.y * w[k]; s[2] += (double)p.z * w[k]; s[3] += (double)p.w * w[k];
+                    }
+                    for (int q = 0; q < 4; ++q)
+                        if (c + q >= ca && c + q < cb) v[q] = (float)s[q];
+                }
+                float *dst = out + ((size_t)r * H + y) * W + c;
+                if (vec4 && c + 3 < W) {
+                    *(float4 *)dst = make_float4(v[0], v[1], v[2], v[3]);
+                } else {
+                    for (int q = 0; q < 4; ++q)
+                        if (c + q < W) dst[q] = v[q];
+                }
+            }
+        }
+    }
+}
+
+__global__ void det_rois_kernel(const float *__restrict__ det, const int *__restrict__ counts, int B, int top_n, float *__restrict__ rois,
+                                int *__restrict__ cls) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= B * top_n) return;
+    const int b = i / top_n, j = i - b * top_n;
+    const float *d = det + (size_t)i * 7;
+    const bool real = j < counts[b];
+    float *o = rois + (size_t)i * 5;
+    o[0] = (float)b;
+    for (int q = 1; q < 5; ++q) o[q] = real ? d[q] : 0.f;
+    cls[i] = real ? (int)d[6] : -1;
+}
+
+// sigmoid(x) = 1 / (1 + e) with e = the correctly rounded float32 exp(-x) (float64 exp rounded once) and float32 IEEE add and divide
+__global__ void mask_select_kernel(const float *__restrict__ logits, long long sr, long long sc, long long sh, long long sw,
+                                   const int *__restrict__ cls, int R, int C, int ph, int pw, int sigmoid, float *__restrict__ out) {
+    const long long n = (long long)R * ph * pw;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        const int x = (int)(i % pw), y = (int)((i / pw) % ph), r = (int)(i / ((long long)ph * pw));
+        const int c = cls[r];
+        float v = 0.f;
+        if (c >= 0 && c < C) {
+            v = logits[r * sr + c * sc + y * sh + x * sw];
+            if (sigmoid) v = 1.0f / (1.0f + (float)exp(-(double)v));
+        }
+        out[i] = v;
+    }
+}
+
+}  // namespace
+
+#define MASK_CHECK(cond, name) if (!(cond)) { set_error(name ": bad arguments"); return SCDA_EINVAL; }
+
+SCDA_API int scda_det_rois_hip(const float *detections, const int *detection_counts, int B, int top_n, float *rois5, int *cls,
+                               void *stream) {
+    MASK_CHECK(detections && detection_counts && rois5 && cls && B > 0 && top_n > 0 && (long long)B * top_n < 0x7fffffffLL,
+               "scda_det_rois_hip")
+    hipLaunchKernelGGL(det_rois_kernel, dim3(cdiv((long long)B * top_n, 256)), dim3(256), 0, as_stream(stream), detections,
+                       detection_counts, B, top_n, rois5, cls);
+    return launch_status("det_rois_kernel");
+}
+
+SCDA_API int scda_mask_select_hip(const float *logits, long long stride_r, long long stride_c, long long stride_h, long long stride_w,
+                                  const int *cls, int R, int C, int ph, int pw, int sigmoid, float *out, void *stream) {
+    MASK_CHECK(logits && cls && out && R > 0 && C > 0 && ph > 0 && pw > 0 && stride_r >= 0 && stride_c >= 0 && stride_h >= 0 &&
+               stride_w >= 0, "scda_mask_select_hip")
+    hipLaunchKernelGGL(mask_select_kernel, dim3(ew_grid((long long)R * ph * pw)), dim3(256), 0, as_stream(stream), logits, stride_r,
+                       stride_c, stride_h, stride_w, cls, R, C, ph, pw, sigmoid, out);
+    return launch_status("mask_select_kernel");
+}
+
+SCDA_API int scda_mask_paste_hip(const float *rois, int roi_stride, const int *cls_or_null, const float *planes, int R, int ph, int pw,
+                                 int H, int W, int packed, float threshold, void *out, void *stream) {
+    MASK_CHECK(rois && planes && out && R > 0 && R <= 65535 && roi_stride >= 5 && ph > 0 && pw > 0 && ph <= kMaxIn && pw <= kMaxIn &&
+               H > 0 && W > 0, "scda_mask_paste_hip")
+    const int Wd = (W + 31) / 32;
+    const dim3 grid(cdiv(W, kStrip), R);
+    if (packed) {
+        hipLaunchKernelGGL(mask_paste_kernel<true>, grid, dim3(kThreads), 0, as_stream(stream), rois, roi_stride, cls_or_null, planes, ph,
+                           pw, H, W, Wd, threshold, 0, out);
+    } else {
+        const int vec4 = W % 4 == 0 && (uintptr_t)out % 16 == 0;
+        hipLaunchKernelGGL(mask_paste_kernel<false>, grid, dim3(kThreads), 0, as_stream(stream), rois, roi_stride, cls_or_null, planes,
+                           ph, pw, H, W, Wd, threshold, vec4, out);
+    }
+    return launch_status("mask_paste_kernel");
+}

@@ -212,3 +212,29 @@ def predict_masks(rois, heatmap, image_info, cfg=None):
         image[y1:y1 + roi_h, x1:x1 + roi_w] = plane
         out.append(image)
     return out
+
+
+def predict_masks_device(rois, heatmap, image_info, out=None):
+    """`predict_masks` on the device: rois [R, >=7] (b, x1, y1, x2, y2, score, class) and heatmap [R, num_classes, h, w] (h, w <= 32)
+    on the HIP device -> float32 [R, image_h, image_w] on the device, row r = predict_masks(...)[r] bit for bit (the resize is Pillow
+    >= 7's BICUBIC float resize restated in scda_amd/csrc/mask_ops.hip; include/scda_ops.h states the rule).  All images of the call
+    must share (image_h, image_w).  Where `predict_masks` would raise because a window leaves the image, the part outside is dropped;
+    an empty window (x2 < x1 or y2 < y1) gives an empty mask.  `out`: an optional [R, image_h, image_w] buffer to fill."""
+    import PIL
+    from scda_amd import native
+    if int(PIL.__version__.split(".")[0]) < 7:
+        raise ValueError("device mask path: Pillow %s resizes with NEAREST by default; the device path restates Pillow >= 7's BICUBIC "
+                         "default -- use predict_masks" % PIL.__version__)
+    info = np.asarray(_np(image_info))
+    sizes = {(int(h), int(w)) for h, w in info[:, :2]}
+    if len(sizes) != 1:
+        raise ValueError("predict_masks_device: all images of a call must share (h, w), got %s" % sorted(sizes))
+    (image_h, image_w), = sizes
+    if not (torch.is_tensor(rois) and rois.is_cuda and torch.is_tensor(heatmap) and heatmap.is_cuda):
+        raise native.ScdaNativeError("predict_masks_device: rois and heatmap must live on the HIP device (predict_masks is the host path)")
+    if rois.shape[0] != heatmap.shape[0] or rois.shape[1] < 7:
+        raise ValueError("predict_masks_device: rois must be [R, >=7] and heatmap [R, num_classes, h, w]")
+    rois = rois.detach().float().contiguous()
+    cls = rois[:, 6].to(torch.int32)                                          # int() of the class column: towards zero
+    planes = native.mask_select(heatmap.detach().float(), cls)
+    return native.mask_paste(rois, planes, image_h, image_w, out=out)

@@ -10,7 +10,14 @@ synchronises: it turns the device results into the row layout of the eval forwar
 Tie rules (include/scda_ops.h): RPN top-k by score, ties by ascending anchor index; per-class lists and the per-image top_n by
 score, ties as numpy's argsort()[::-1] leaves them (later row first).  Where numpy's order is defined, the results are the eval
 forward's; the RPN's exp of the size deltas is the correctly rounded float32 exp (numpy's is its own routine), so proposal
-coordinates can differ from the eval forward's in their last bits."""
+coordinates can differ from the eval forward's in their last bits.
+
+Instance masks (opt-in, `Predictor(model, cfg, masks=True)`, the detector built with the mask branch): behind the box prediction the
+detections become the mask head's RoIs, `model.mask_predictor` gives the per-class logits, each detection's own class plane goes through
+the sigmoid and functions/mask.py:21-49 (`predict_masks`: the plane resized to the box as Pillow >= 7 resizes it, pasted into the image;
+scda_amd/csrc/mask_ops.hip, bit for bit) runs on the device into bit-packed planes, bit = probability >= mask_threshold.  The paste is
+pinned against the reference; the sigmoid and the 0.5 threshold are the Mask R-CNN definition and parity-unpinned (the reference's own
+use of the heat map is in its missing models/mask_rcnn/mask_rcnn.py).  `mask_rows` turns the words into boolean arrays."""
 import numpy as np
 import torch
 
@@ -40,11 +47,23 @@ class Predictor:
         pred.capture(images, image_info)      # after that first call: record one pass into a graph
         pred.images.copy_(...); pred.image_info.copy_(...); pred.replay()   # -> the same four tensors, refilled
 
-    The returned tensors are the Predictor's own: a later call overwrites them."""
+    The returned tensors are the Predictor's own: a later call overwrites them.
 
-    def __init__(self, model, cfg):
+    masks=True (a detector with the mask branch only): the result grows by mask_bits int32 [B, top_n, H, ceil(W/32)] at the batch's
+    padded (H, W): bit (c % 32) of word c // 32 of row y = (mask probability at (y, c) >= mask_threshold); the planes of padding rows
+    are zero.  One more fixed buffer per shape (13.4 MB per image for 100 detections at 800 x 1344), no additional wait for the host."""
+
+    def __init__(self, model, cfg, masks=False, mask_threshold=0.5):
         if model.training:
             raise ValueError("Predictor: put the detector in eval mode first (model.eval())")
+        self.masks, self.mask_threshold = bool(masks), float(mask_threshold)
+        if self.masks:
+            if not getattr(model, 'with_mask', False):
+                raise ValueError("Predictor: masks=True needs a detector with the mask branch (cfg with_mask)")
+            import PIL
+            if int(PIL.__version__.split(".")[0]) < 7:
+                raise ValueError("device mask path: Pillow %s resizes with NEAREST by default; the device path restates Pillow >= 7's "
+                                 "BICUBIC default -- use predict_masks on the host" % PIL.__version__)
         self.model, self.cfg = model, cfg
         self.rpn_cfg, self.box_cfg = _sections(cfg)
         if not self.box_cfg.get('bbox_normalize_stats_precomputed', False):
@@ -74,6 +93,25 @@ class Predictor:
         self.box_ws = torch.empty(max(N.box_predict_workspace_bytes(B, P, C), 8), **u8)
         self.anchors64 = device_boxes.anchors_on_device(fh, fw, self.rpn_cfg, dev)[1]
 
+    def _allocate_masks(self, B, H, W, dev):
+        R = B * self.top_n
+        self.mask_rois = torch.zeros(R, 5, dtype=torch.float32, device=dev)
+        self.mask_cls = torch.zeros(R, dtype=torch.int32, device=dev)
+        self.mask_planes = None                                               # [R, h, w] once the head's output size is known
+        self.mask_bits = torch.zeros(B, self.top_n, H, (W + 31) // 32, dtype=torch.int32, device=dev)
+
+    def _masks(self, feat, B, H, W):
+        """detections -> RoIs -> mask head -> own class plane through the sigmoid -> resized, pasted and packed"""
+        N.det_rois(self.det, self.det_counts, self.mask_rois, self.mask_cls)
+        logits = self.model.mask_predictor(feat, self.mask_rois).detach()
+        R, _, h, w = logits.shape
+        if self.mask_planes is None or self.mask_planes.shape != (R, h, w):
+            self.mask_planes = torch.empty(R, h, w, dtype=torch.float32, device=logits.device)
+        N.mask_select(logits, self.mask_cls, sigmoid=True, out=self.mask_planes)
+        N.mask_paste(self.mask_rois, self.mask_planes, H, W, cls=self.mask_cls, packed=True, threshold=self.mask_threshold,
+                     out=self.mask_bits.view(R, H, -1))
+        return self.mask_bits
+
     def _info(self, image_info, B, dev):
         if torch.is_tensor(image_info) and image_info.is_cuda and image_info.dtype == torch.float32 and image_info.is_contiguous():
             return image_info
@@ -100,6 +138,8 @@ class Predictor:
         if self.shape != shape:
             C = int(self.box_cfg['num_classes'])
             self._allocate(B, fh, fw, A4 // 4, C, dev)
+            if self.masks:
+                self._allocate_masks(B, images.shape[2], images.shape[3], dev)
             self.shape = shape
             self.graph = None
         N.rpn_proposals_batched(prob, loc, self.anchors64, info, int(rc['pre_nms_top_n']), float(rc['roi_min_size']),
@@ -112,6 +152,8 @@ class Predictor:
                       bc['bbox_normalize_means'], float(bc['score_thresh']), float(bc['nms_iou_thresh']), self.top_n, self.box_ws,
                       self.det, self.det_counts)
         self._out = (self.props.view(B, self.P, 6), self.counts, self.det, self.det_counts)
+        if self.masks:
+            self._out += (self._masks(feat, B, images.shape[2], images.shape[3]),)
         return self._out
 
     def capture(self, images, image_info):
@@ -138,15 +180,16 @@ class Predictor:
 _PREDICTORS = {}
 
 
-def predict(model, images, image_info, cfg):
+def predict(model, images, image_info, cfg, masks=False, mask_threshold=0.5):
     """images [B,3,H,W] on the device, image_info [B,>=2] (host or device) -> device tensors
     (proposals [B,P,6] = (b, x1, y1, x2, y2, score), proposal_counts int32 [B], detections [B,top_n,7] =
     (b, x1, y1, x2, y2, score, class), detection_counts int32 [B]); rows past an image's count are padding.
-    One Predictor per (model, cfg) is kept and reused; its buffers are overwritten by the next call."""
-    key = (id(model), id(cfg))
+    masks=True: a fifth tensor, mask_bits int32 [B,top_n,H,ceil(W/32)] (see Predictor).
+    One Predictor per (model, cfg, masks, mask_threshold) is kept and reused; its buffers are overwritten by the next call."""
+    key = (id(model), id(cfg)) if not masks else (id(model), id(cfg), True, float(mask_threshold))
     p = _PREDICTORS.get(key)
     if p is None or p.model is not model:
-        p = _PREDICTORS[key] = Predictor(model, cfg)
+        p = _PREDICTORS[key] = Predictor(model, cfg, masks=masks, mask_threshold=mask_threshold)
     return p(images, image_info)
 
 
@@ -157,3 +200,21 @@ def rows(proposals, proposal_counts, detections, detection_counts):
     props = np.concatenate([p[b, :pc[b]] for b in range(p.shape[0])], 0).reshape(-1, 6)
     dets = np.concatenate([d[b, :dc[b]] for b in range(d.shape[0])], 0).reshape(-1, 7)
     return props, dets
+
+
+def mask_rows(mask_bits, detection_counts, width=None):
+    """mask_bits [B, top_n, H, ceil(W/32)] + detection_counts [B] -> a list of B boolean arrays [n_b, H, W]: each image's real
+    detections in `rows`' order.  width: W when it is not a multiple of 32 (default: every stored column).  Like `rows`, this waits for
+    the device."""
+    words = mask_bits.cpu().numpy().view(np.uint32)
+    counts = detection_counts.cpu().numpy()
+    B, _, H, Wd = words.shape
+    W = Wd * 32 if width is None else int(width)
+    if not 0 < W <= Wd * 32:
+        raise ValueError("mask_rows: width must be in (0, %d]" % (Wd * 32))
+    out = []
+    for b in range(B):
+        w = np.ascontiguousarray(words[b, :int(counts[b])])
+        bits = np.unpackbits(w.view(np.uint8), axis=-1, bitorder='little')        # [n, H, Wd * 32]: bit j of a word = column 32 i + j
+        out.append(bits[:, :, :W].astype(bool))
+    return out

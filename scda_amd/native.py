@@ -362,6 +362,76 @@ def box_predict(rois, roi_counts, prob, loc, image_info, stds, means, score_thre
     return det, det_counts
 
 
+# ------------------------------------------------- instance masks ------------
+def det_rois(det, det_counts, rois5=None, cls=None):
+    """det [B, top_n, 7] + det_counts int32 [B] (box_predict's outputs) -> rois5 [B*top_n, 5], cls int32 [B*top_n]; padding rows are
+    (b, 0, 0, 0, 0), class -1"""
+    _req(det, "det"); _req(det_counts, "det_counts", torch.int32)
+    if det.dim() != 3 or det.shape[2] != 7 or det_counts.numel() != det.shape[0]:
+        raise ValueError("det_rois: det must be [B, top_n, 7] and det_counts [B]")
+    B, top_n = det.shape[:2]
+    if rois5 is None:
+        rois5 = torch.empty(B * top_n, 5, dtype=torch.float32, device=det.device)
+    if cls is None:
+        cls = torch.empty(B * top_n, dtype=torch.int32, device=det.device)
+    _req(rois5, "rois5"); _req(cls, "cls", torch.int32)
+    if rois5.shape != (B * top_n, 5) or cls.numel() != B * top_n:
+        raise ValueError("det_rois: inconsistent shapes")
+    _check(lib().scda_det_rois_hip(_p(det), _p(det_counts), i32(B), i32(top_n), _p(rois5), _p(cls), _stream()), "scda_det_rois_hip")
+    return rois5, cls
+
+
+def mask_select(logits, cls, sigmoid=False, out=None):
+    """logits [R, C, h, w] in any strided order (not required contiguous) + cls int32 [R] -> [R, h, w] contiguous: each row's own class
+    plane, optionally through the sigmoid; rows of class < 0 give zeros"""
+    if not isinstance(logits, torch.Tensor) or not logits.is_cuda or logits.dtype != torch.float32:
+        raise ScdaNativeError("logits must be a float32 tensor on the HIP device; there is no CPU path")
+    _req(cls, "cls", torch.int32)
+    if logits.dim() != 4 or cls.numel() != logits.shape[0]:
+        raise ValueError("mask_select: logits must be [R, C, h, w] and cls [R]")
+    R, C, h, w = logits.shape
+    if min(logits.stride()) < 0:
+        raise ValueError("mask_select: negative strides")
+    if out is None:
+        out = torch.empty(R, h, w, dtype=torch.float32, device=logits.device)
+    _req(out, "out")
+    if out.shape != (R, h, w):
+        raise ValueError("mask_select: out must be [R, h, w]")
+    sr, sc, sh, sw = (ctypes.c_longlong(v) for v in logits.stride())
+    _check(lib().scda_mask_select_hip(_p(logits), sr, sc, sh, sw, _p(cls), i32(R), i32(C), i32(h), i32(w), i32(1 if sigmoid else 0),
+                                      _p(out), _stream()), "scda_mask_select_hip")
+    return out
+
+
+MASK_PLANE_MAX = 32
+
+
+def mask_paste(rois, planes, H, W, cls=None, packed=False, threshold=0.5, out=None):
+    """functions/mask.py:21-49 on the device (include/scda_ops.h states the rule): rois [R, >=5] (b, x1, y1, x2, y2, ...), planes
+    [R, h, w] -> float32 [R, H, W], or with packed=True uint32 [R, H, ceil(W/32)] of (value >= threshold), stored as int32.  Rows
+    with cls < 0 give an empty mask; the part of a window outside the plane is dropped.  Every element of `out` is written."""
+    _req(rois, "rois"); _req(planes, "planes")
+    if rois.dim() != 2 or rois.shape[1] < 5 or planes.dim() != 3 or planes.shape[0] != rois.shape[0]:
+        raise ValueError("mask_paste: rois must be [R, >=5] and planes [R, h, w]")
+    R, h, w = planes.shape
+    if h > MASK_PLANE_MAX or w > MASK_PLANE_MAX:
+        raise ValueError("mask_paste: planes of at most %d x %d" % (MASK_PLANE_MAX, MASK_PLANE_MAX))
+    if cls is not None:
+        _req(cls, "cls", torch.int32)
+        if cls.numel() != R:
+            raise ValueError("mask_paste: cls must be [R]")
+    H, W = int(H), int(W)
+    shape, dtype = ((R, H, (W + 31) // 32), torch.int32) if packed else ((R, H, W), torch.float32)
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device=rois.device)
+    _req(out, "out", dtype)
+    if tuple(out.shape) != shape:
+        raise ValueError("mask_paste: out must be %s" % (shape,))
+    _check(lib().scda_mask_paste_hip(_p(rois), i32(rois.shape[1]), _p(cls), _p(planes), i32(R), i32(h), i32(w), i32(H), i32(W),
+                                     i32(1 if packed else 0), f32(threshold), _p(out), _stream()), "scda_mask_paste_hip")
+    return out
+
+
 # ------------------------------------------------- convolution / GEMM -------
 _WS = {}
 
