@@ -258,6 +258,52 @@ int scda_mask_select_hip(const float *logits, long long stride_r, long long stri
 int scda_mask_paste_hip(const float *rois, int roi_stride, const int *cls_or_null, const float *planes, int R, int ph, int pw, int H,
                         int W, int packed, float threshold, void *out, void *stream);
 
+/* ---- COCO run-length results from packed masks (scda_amd/csrc/mask_rle.hip; opt-in: scda_amd.infer.Predictor(masks=True, rle=True)) ----
+ * The per-mask primitives of the reference's datasets/pycocotools/common/maskApi.c on scda_mask_paste_hip's packed planes, bit for bit
+ * (integers below 2^32 and one IEEE double division; no atomics: two runs give the same bytes).  tests/mask_rle_np.py restates the
+ * rules in numpy; tests/golden/mask_rle_ref.npz holds what the reference's C gives.
+ *
+ * scda_mask_rle_hip: bits uint32 [R, H, Wd] (bit c % 32 of word c / 32 of row y = pixel (y, c)).  The image of mask r is the top-left
+ * h_r x w_r sub-plane, 1 <= h_r <= H, 1 <= w_r <= 32 Wd; bits outside it do not count.  (h_r, w_r) = image_info[r / masks_per_image]
+ * [0:2] (float32 DEVICE rows of info_stride floats, truncated and clamped to that range), or (h_all, w_all) for every mask when
+ * image_info is NULL.  rois_or_null [R, roi_stride >= 5] = the rows given to scda_mask_paste_hip, a HINT: a pasted mask is zero outside
+ * the columns of its truncated window, so only those are read.  That holds for planes pasted with threshold > 0 only (at threshold
+ * <= 0 the outside is set); for such planes the result is the same with and without the hint.  Outputs per mask r:
+ *   n_runs int32 [R]             the TRUE number of runs, also when it exceeds cap_runs -- n_runs[r] > cap_runs is the overflow flag;
+ *   counts uint32 [R, cap_runs]  rleEncode (maskApi.c:32-42): pixels in column-major order (index = x * h_r + y); the first run counts
+ *                                zeros and may be 0, runs alternate; an empty mask is the single run h_r * w_r;
+ *   chars uint8 [R, cap_bytes], n_bytes int32 [R]   rleToString (maskApi.c:203-215) of those counts, no terminator: for run i,
+ *                                x = counts[i] - (i > 2 ? counts[i - 2] : 0) as a signed value; repeat c = x & 0x1f, x >>= 5 (arithmetic),
+ *                                more = (c & 0x10) ? x != -1 : x != 0, if (more) c |= 0x20, emit c + 48, while more;
+ *   area uint32 [R]              rleArea: the sum of the odd runs (= the set pixels of the sub-plane);
+ *   bbox uint32 [R, 4]           (x, y, w, h) as rleToBbox (maskApi.c:133-146) computes it FROM THE RUN END POINTS: over every run of
+ *                                ones, x and y of its first and of its last pixel enter the min / max, nothing in between.  A run that
+ *                                wraps from the bottom of one column into the top of the next therefore contributes only its end points'
+ *                                rows: the 10 x 6 mask with [5:, 1] and [:4, 2] set gives (1, 3, 2, 3), not rows 0..9.  This is what
+ *                                this pycocotools version computes and what rleIou's box gate sees; it is reproduced on purpose, a
+ *                                "tight" box is not what the reference returns.  The columns (x, w) are exact.  Empty mask: 0, 0, 0, 0.
+ * counts [r, i >= n_runs[r]] and chars [r, i >= n_bytes[r]] are not written and hold nothing.  On overflow n_bytes[r] = 0 and counts /
+ * chars of that mask hold nothing a caller may use; n_runs, area and bbox are exact all the same; the other masks are unaffected.
+ * A count difference takes at most scda_mask_rle_max_chars(h, w) = ceil((bitlength(h * w) + 1) / 5) characters (a signed value of
+ * bitlength + 1 bits, 5 bits per character; 5 for every plane below 2^24 pixels); cap_bytes >= cap_runs *
+ * scda_mask_rle_max_chars(H, 32 Wd) is required, so the string of a mask that fits cap_runs always fits cap_bytes.
+ * ws: scda_mask_rle_workspace_bytes(R, H, Wd, cap_runs) bytes, 16-byte aligned.  R, H <= 65535, H * 32 Wd < 2^31.  Four launches, no
+ * host wait, no allocation: graph-capturable. */
+int scda_mask_rle_max_chars(int h, int w);
+size_t scda_mask_rle_workspace_bytes(int R, int H, int Wd, int cap_runs);
+int scda_mask_rle_hip(const uint32_t *bits, int R, int H, int Wd, const float *image_info, int info_stride, int masks_per_image,
+                      int h_all, int w_all, const float *rois_or_null, int roi_stride, int cap_runs, int cap_bytes, void *ws,
+                      int *n_runs, uint32_t *counts, int *n_bytes, unsigned char *chars, uint32_t *area, uint32_t *bbox, void *stream);
+/* rleIou (maskApi.c:77-96) of packed masks: dt_bits [M, H, Wd], gt_bits [N, H, Wd], one image size (h, w) for all, iscrowd uint8 [N]
+ * (device) or NULL -> iou float64 [N, M] in the reference's layout o[g * M + d] and inter uint32 [N, M], the raw |dt & gt| inside the
+ * h x w sub-plane.  i = |dt & gt|; u = iscrowd[g] ? area(dt) : area(dt) + area(gt) - i; o = (double) i / (double) u; o = 0 when i == 0,
+ * AND o = 0 wherever the reference's box gate gives 0: bbIou (maskApi.c:110-121) of the two rleToBbox boxes above -- end-point rows
+ * included -- has w <= 0 or h <= 0.  (The wrapped mask above as dt and gt = [7:9, 1] give 0.0 although 2 pixels intersect; inter
+ * still says 2.)  ws: scda_mask_iou_workspace_bytes(M, N, H, Wd) bytes, 16-byte aligned. */
+size_t scda_mask_iou_workspace_bytes(int M, int N, int H, int Wd);
+int scda_mask_iou_hip(const uint32_t *dt_bits, int M, const uint32_t *gt_bits, int N, int H, int Wd, int h, int w,
+                      const unsigned char *iscrowd_or_null, void *ws, double *iou, uint32_t *inter, void *stream);
+
 /* ------------------------------------------------- convolution / GEMM ---- */
 /* The reference reaches these through torch.nn (cuDNN / cuBLAS): nn.Conv2d in
  * models/faster_rcnn/vgg_adver_expansion_cluster.py:101-114 (VGG body),

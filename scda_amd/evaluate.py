@@ -6,6 +6,7 @@ image, clipped, divided by the resize scale), then score them with utils.cal_mAP
 The model forward is the HIP path (scda_amd.dropin.models...FasterRCNN_AdEx in eval mode: backbone + RPN + RoIPool + FC on
 the MI355X, NMS through scda_nms_hip); this module is only the loop around it.
 """
+import json
 import logging
 import os
 import time
@@ -96,3 +97,41 @@ def validate(val_loader, model, cfg, results_dir, val_meta_file=None, dataset='c
     if was_training:
         model.train()
     return total_rc / total_gt
+
+
+def write_segm_results(writer, image_info, image_ids, out, category_of=None, input_resolution=False, keep_num=100):
+    """The JSON lines of the reference's write_results_to_file (tools/mask_rcnn_train_val.py:381-430) from one
+    scda_amd.infer.Predictor(masks=True, rle=True) pass: per image the `keep_num` best detections by score (ties in the detections'
+    order), one line each with `image_id`, `bbox` = [x, y, w, h] of the detection box, `score`, `category_id` (category_of(class), default
+    the class index) and `segmentation` = {'size': [h, w], 'counts': str}, the mask's compressed RLE as the device encoded it.
+    image_info [B, >=3] rows (h, w, resize_scale, ...); image_ids: B ids.  Returns the number of masks the host had to encode.
+
+    The masks are at the NETWORK-INPUT resolution.  The reference resizes each mask once more to the original image size before it
+    thresholds (:422); that resize is not done here, so an image with resize_scale != 1 raises ValueError -- unless the caller passes
+    input_resolution=True and then gets box AND mask of such an image at the network-input resolution (the box NOT divided by
+    resize_scale, so the two agree) and rescales them himself."""
+    from scda_amd import infer
+    info = _np(image_info)
+    if info.ndim != 2 or info.shape[1] < 3 or len(image_ids) != info.shape[0]:
+        raise ValueError("write_segm_results: image_info [B, >=3] and B image ids")
+    if not input_resolution:
+        bad = [b for b in range(info.shape[0]) if float(info[b, 2]) != 1.0]
+        if bad:
+            raise ValueError("write_segm_results: images %s have resize_scale != 1; the masks are encoded at the network-input "
+                             "resolution (pass input_resolution=True to get box and mask at that resolution)" % bad)
+    segs, fallbacks = infer.segm_rows(out, with_fallbacks=True)
+    det, det_counts = _np(out[2]), _np(out[3])
+    for b in range(info.shape[0]):
+        d = det[b, :int(det_counts[b])]
+        order = np.argsort(-d[:, 5], kind='stable')[:keep_num]
+        scale = 1.0 if input_resolution else float(info[b, 2])
+        for ix in order:
+            box = (d[ix, 1:5] / np.float32(scale)).tolist()
+            cls = int(d[ix, 6])
+            seg = segs[b][ix]
+            res = {'image_id': int(image_ids[b]), 'bbox': [box[0], box[1], box[2] - box[0], box[3] - box[1]], 'score': d[ix, 5].tolist(),
+                   'category_id': category_of(cls) if category_of is not None else cls,
+                   'segmentation': {'size': seg['size'], 'counts': seg['counts']}}
+            writer.write(json.dumps(res) + '\n')
+        writer.flush()
+    return fallbacks

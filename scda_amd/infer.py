@@ -17,7 +17,13 @@ detections become the mask head's RoIs, `model.mask_predictor` gives the per-cla
 the sigmoid and functions/mask.py:21-49 (`predict_masks`: the plane resized to the box as Pillow >= 7 resizes it, pasted into the image;
 scda_amd/csrc/mask_ops.hip, bit for bit) runs on the device into bit-packed planes, bit = probability >= mask_threshold.  The paste is
 pinned against the reference; the sigmoid and the 0.5 threshold are the Mask R-CNN definition and parity-unpinned (the reference's own
-use of the heat map is in its missing models/mask_rcnn/mask_rcnn.py).  `mask_rows` turns the words into boolean arrays."""
+use of the heat map is in its missing models/mask_rcnn/mask_rcnn.py).  `mask_rows` turns the words into boolean arrays.
+
+COCO results (opt-in on top, `Predictor(model, cfg, masks=True, rle=True)`): behind the paste every detection's plane is run-length encoded
+on the device at its image's (h, w) (scda_amd/csrc/mask_rle.hip: pycocotools' rleEncode / rleToString / rleArea / rleToBbox bit for bit),
+so what leaves the device is the result -- a few kilobytes per mask -- not the raster.  `segm_rows` is the call that waits and returns
+the `{'size', 'counts'}` dictionaries; a mask with more runs than the device capacity is encoded on the host from its own plane
+(scda_amd/mask_rle_host.py, the same rule) and counted."""
 import numpy as np
 import torch
 
@@ -51,12 +57,24 @@ class Predictor:
 
     masks=True (a detector with the mask branch only): the result grows by mask_bits int32 [B, top_n, H, ceil(W/32)] at the batch's
     padded (H, W): bit (c % 32) of word c // 32 of row y = (mask probability at (y, c) >= mask_threshold); the planes of padding rows
-    are zero.  One more fixed buffer per shape (13.4 MB per image for 100 detections at 800 x 1344), no additional wait for the host."""
+    are zero.  One more fixed buffer per shape (13.4 MB per image for 100 detections at 800 x 1344), no additional wait for the host.
 
-    def __init__(self, model, cfg, masks=False, mask_threshold=0.5):
+    rle=True (with masks=True): the result grows by ONE more element, a dict of device tensors per detection -- n_runs int32 [B, top_n]
+    (the true run count; > the capacity = overflow), counts int32 [B, top_n, cap] (uint32 values), n_bytes int32 [B, top_n], chars uint8
+    [B, top_n, cap * chars per count], area int32 [B, top_n], bbox int32 [B, top_n, 4] = (x, y, w, h) of the MASK as rleToBbox gives it,
+    size int32 [B, 2] = the (h, w) every mask of the image was encoded at (image_info[b, 0:2], read on the device).  Padding detections
+    carry the empty-mask code.  rle_capacity: runs kept per detection, default 4 * W (two segments per column on average over the whole
+    width); a default, not a guarantee: segm_rows encodes an overflowing mask on the host."""
+
+    def __init__(self, model, cfg, masks=False, mask_threshold=0.5, rle=False, rle_capacity=None):
         if model.training:
             raise ValueError("Predictor: put the detector in eval mode first (model.eval())")
         self.masks, self.mask_threshold = bool(masks), float(mask_threshold)
+        self.rle, self.rle_capacity = bool(rle), None if rle_capacity is None else int(rle_capacity)
+        if self.rle and not self.masks:
+            raise ValueError("Predictor: rle=True encodes the instance masks; it needs masks=True")
+        if self.rle_capacity is not None and self.rle_capacity < 1:
+            raise ValueError("Predictor: rle_capacity must be >= 1")
         if self.masks:
             if not getattr(model, 'with_mask', False):
                 raise ValueError("Predictor: masks=True needs a detector with the mask branch (cfg with_mask)")
@@ -100,6 +118,29 @@ class Predictor:
         self.mask_planes = None                                               # [R, h, w] once the head's output size is known
         self.mask_bits = torch.zeros(B, self.top_n, H, (W + 31) // 32, dtype=torch.int32, device=dev)
 
+    def _allocate_rle(self, B, H, W, dev):
+        R, Wd = B * self.top_n, (W + 31) // 32
+        cap = 4 * W if self.rle_capacity is None else self.rle_capacity
+        i32 = dict(dtype=torch.int32, device=dev)
+        self.rle_cap = cap
+        self.rle_ws = torch.empty(max(N.mask_rle_workspace_bytes(R, H, Wd, cap), 8), dtype=torch.uint8, device=dev)
+        self.rle_flat = {'n_runs': torch.zeros(R, **i32), 'counts': torch.zeros(R, cap, **i32), 'n_bytes': torch.zeros(R, **i32),
+                         'chars': torch.zeros(R, cap * N.mask_rle_max_chars(H, 32 * Wd), dtype=torch.uint8, device=dev),
+                         'area': torch.zeros(R, **i32), 'bbox': torch.zeros(R, 4, **i32)}
+        self.rle_out = {k: v.view(B, self.top_n, *v.shape[1:]) for k, v in self.rle_flat.items()}
+        self.rle_out['size'] = torch.zeros(B, 2, **i32)
+
+    def _rle(self, info, B, H, W):
+        """every detection's packed plane -> its run-length code at the image's (h, w); the paste's windows limit the columns read
+        (valid for a positive threshold: outside its window a pasted plane is 0.0)"""
+        N.mask_rle(self.mask_bits.view(B * self.top_n, H, -1), image_info=info,
+                   rois=self.mask_rois if self.mask_threshold > 0 else None, cap_runs=self.rle_cap, ws=self.rle_ws, out=self.rle_flat)
+        size = self.rle_out['size']
+        size.copy_(info[:, :2])                                               # float32 -> int32 truncates like the kernel
+        size[:, 0].clamp_(1, H)
+        size[:, 1].clamp_(1, 32 * ((W + 31) // 32))
+        return self.rle_out
+
     def _masks(self, feat, B, H, W):
         """detections -> RoIs -> mask head -> own class plane through the sigmoid -> resized, pasted and packed"""
         N.det_rois(self.det, self.det_counts, self.mask_rois, self.mask_cls)
@@ -140,6 +181,8 @@ class Predictor:
             self._allocate(B, fh, fw, A4 // 4, C, dev)
             if self.masks:
                 self._allocate_masks(B, images.shape[2], images.shape[3], dev)
+            if self.rle:
+                self._allocate_rle(B, images.shape[2], images.shape[3], dev)
             self.shape = shape
             self.graph = None
         N.rpn_proposals_batched(prob, loc, self.anchors64, info, int(rc['pre_nms_top_n']), float(rc['roi_min_size']),
@@ -154,6 +197,8 @@ class Predictor:
         self._out = (self.props.view(B, self.P, 6), self.counts, self.det, self.det_counts)
         if self.masks:
             self._out += (self._masks(feat, B, images.shape[2], images.shape[3]),)
+        if self.rle:
+            self._out += (self._rle(info, B, images.shape[2], images.shape[3]),)
         return self._out
 
     def capture(self, images, image_info):
@@ -180,16 +225,19 @@ class Predictor:
 _PREDICTORS = {}
 
 
-def predict(model, images, image_info, cfg, masks=False, mask_threshold=0.5):
+def predict(model, images, image_info, cfg, masks=False, mask_threshold=0.5, rle=False, rle_capacity=None):
     """images [B,3,H,W] on the device, image_info [B,>=2] (host or device) -> device tensors
     (proposals [B,P,6] = (b, x1, y1, x2, y2, score), proposal_counts int32 [B], detections [B,top_n,7] =
     (b, x1, y1, x2, y2, score, class), detection_counts int32 [B]); rows past an image's count are padding.
-    masks=True: a fifth tensor, mask_bits int32 [B,top_n,H,ceil(W/32)] (see Predictor).
-    One Predictor per (model, cfg, masks, mask_threshold) is kept and reused; its buffers are overwritten by the next call."""
+    masks=True: a fifth tensor, mask_bits int32 [B,top_n,H,ceil(W/32)] (see Predictor); rle=True on top: a sixth element, the dict of
+    run-length results (see Predictor, segm_rows).
+    One Predictor per (model, cfg, masks, mask_threshold, rle, rle_capacity) is kept and reused; its buffers are overwritten by the next call."""
     key = (id(model), id(cfg)) if not masks else (id(model), id(cfg), True, float(mask_threshold))
+    if rle:
+        key += ('rle', rle_capacity)
     p = _PREDICTORS.get(key)
     if p is None or p.model is not model:
-        p = _PREDICTORS[key] = Predictor(model, cfg, masks=masks, mask_threshold=mask_threshold)
+        p = _PREDICTORS[key] = Predictor(model, cfg, masks=masks, mask_threshold=mask_threshold, rle=rle, rle_capacity=rle_capacity)
     return p(images, image_info)
 
 
@@ -218,3 +266,57 @@ def mask_rows(mask_bits, detection_counts, width=None):
         bits = np.unpackbits(w.view(np.uint8), axis=-1, bitorder='little')        # [n, H, Wd * 32]: bit j of a word = column 32 i + j
         out.append(bits[:, :, :W].astype(bool))
     return out
+
+
+def pack_masks(masks):
+    """bool [N, H, W] (host) -> int32 words [N, H, ceil(W/32)], bit (c % 32) of word c // 32 = masks[n, y, c]: the layout of mask_bits
+    and the inverse of mask_rows' unpacking, so that ground-truth masks can be given to native.mask_iou / native.mask_rle"""
+    m = np.asarray(masks, dtype=bool)
+    if m.ndim != 3:
+        raise ValueError("pack_masks: masks must be [N, H, W]")
+    n, H, W = m.shape
+    Wd = (W + 31) // 32
+    padded = np.zeros((n, H, Wd * 32), dtype=np.uint8)
+    padded[:, :, :W] = m
+    words = np.packbits(padded, axis=-1, bitorder='little').reshape(n, H, Wd, 4)
+    words = (words[..., 0].astype(np.uint32) | (words[..., 1].astype(np.uint32) << 8) | (words[..., 2].astype(np.uint32) << 16)
+             | (words[..., 3].astype(np.uint32) << 24))
+    return torch.from_numpy(words.view(np.int32))
+
+
+def segm_rows(out, with_fallbacks=False):
+    """the result of a Predictor(masks=True, rle=True) pass -> per image a list with one dict per real detection, in `rows`' order:
+    {'size': [h, w], 'counts': str, 'area': int, 'bbox': [x, y, w, h]} -- 'size' and 'counts' are pycocotools' compressed RLE of the mask
+    at the network-input resolution, 'area' / 'bbox' its rleArea / rleToBbox.  A detection whose run count exceeded the device capacity
+    is encoded here from its own plane of mask_bits by scda_amd.mask_rle_host (the same rule, the same bytes); their number is logged and,
+    with with_fallbacks=True, returned as a second value.  This call waits for the device.  What crosses to the host: 28 bytes per
+    detection slot, 12 per image, each image's strings (its real detections x the longest of them) and one plane per fallback."""
+    import logging
+    from scda_amd import mask_rle_host
+    det_counts, mask_bits, rle = out[3], out[4], out[5]
+    dc = det_counts.cpu().numpy()
+    n_runs, n_bytes, area = (rle[k].cpu().numpy() for k in ('n_runs', 'n_bytes', 'area'))
+    bbox, size = rle['bbox'].cpu().numpy(), rle['size'].cpu().numpy()
+    cap = rle['counts'].shape[2]
+    res, fallbacks = [], 0
+    for b in range(dc.shape[0]):
+        n = int(dc[b])
+        h, w = int(size[b, 0]), int(size[b, 1])
+        over = n_runs[b, :n] > cap
+        longest = int(n_bytes[b, :n][~over].max()) if n and not over.all() else 0
+        chars = rle['chars'][b, :n, :longest].cpu().numpy() if longest else None
+        rows_b = []
+        for j in range(n):
+            if over[j]:
+                plane = mask_bits[b, j].cpu().numpy().view(np.uint32)
+                bits = np.unpackbits(np.ascontiguousarray(plane).view(np.uint8), axis=-1, bitorder='little')
+                rows_b.append(mask_rle_host.encode(bits[:h, :w].astype(bool)))
+                fallbacks += 1
+            else:
+                rows_b.append({'size': [h, w], 'counts': chars[j, :n_bytes[b, j]].tobytes().decode('ascii'),
+                               'area': int(area[b, j].view(np.uint32)), 'bbox': [int(v) for v in bbox[b, j].view(np.uint32)]})
+        res.append(rows_b)
+    if fallbacks:
+        logging.getLogger('global').info("segm_rows: %d masks exceeded the device run capacity of %d and were encoded on the host"
+                                         % (fallbacks, cap))
+    return (res, fallbacks) if with_fallbacks else res

@@ -32,7 +32,8 @@ def lib():
         _lib = ctypes.CDLL(LIB_PATH)
         _lib.scda_last_error.restype = ctypes.c_char_p
         _lib.scda_nms_workspace_bytes.restype = ctypes.c_size_t
-        for f in ("scda_rpn_topk_workspace_bytes", "scda_rpn_proposals_workspace_bytes", "scda_box_predict_workspace_bytes"):
+        for f in ("scda_rpn_topk_workspace_bytes", "scda_rpn_proposals_workspace_bytes", "scda_box_predict_workspace_bytes",
+                  "scda_mask_rle_workspace_bytes", "scda_mask_iou_workspace_bytes"):
             getattr(_lib, f).restype = ctypes.c_size_t
     return _lib
 
@@ -430,6 +431,109 @@ def mask_paste(rois, planes, H, W, cls=None, packed=False, threshold=0.5, out=No
     _check(lib().scda_mask_paste_hip(_p(rois), i32(rois.shape[1]), _p(cls), _p(planes), i32(R), i32(h), i32(w), i32(H), i32(W),
                                      i32(1 if packed else 0), f32(threshold), _p(out), _stream()), "scda_mask_paste_hip")
     return out
+
+
+# ------------------------------------------------- COCO run-length results ---
+def mask_rle_max_chars(h, w):
+    """characters one count of an h x w plane can take in the 6-bit string: ceil((bitlength(h * w) + 1) / 5)"""
+    return int(lib().scda_mask_rle_max_chars(i32(int(h)), i32(int(w))))
+
+
+def mask_rle_workspace_bytes(R, H, Wd, cap_runs):
+    return int(lib().scda_mask_rle_workspace_bytes(i32(R), i32(H), i32(Wd), i32(cap_runs)))
+
+
+def _words(t, name):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise ScdaNativeError(f"{name} must live on the HIP device; there is no CPU path")
+    if t.dtype != torch.int32 or t.dim() != 3 or not t.is_contiguous():
+        raise ValueError(f"{name} must be contiguous int32 [R, H, ceil(W/32)] words")
+    return t
+
+
+def mask_rle(bits, size=None, image_info=None, rois=None, cap_runs=None, ws=None, out=None):
+    """maskApi.c's rleEncode / rleToString / rleArea / rleToBbox of packed masks on the device (include/scda_ops.h states the rules).
+    bits int32 [R, H, Wd] words as mask_paste(packed=True) writes them.  The image of each mask: size=(h, w) for all, or image_info
+    float32 [B, >=2] on the device with R % B == 0 (mask r belongs to image r // (R // B)); default: the whole plane.  rois [R, >=5]: the
+    rows given to mask_paste, a hint that limits the columns read (planes pasted with threshold > 0 only).  cap_runs: runs kept per mask
+    (default 4 * 32 * Wd).  -> dict of device tensors n_runs int32 [R] (the true count; > cap_runs = overflow), counts int32 [R, cap_runs]
+    (uint32 values), n_bytes int32 [R], chars uint8 [R, cap_runs * mask_rle_max_chars(H, 32 Wd)], area int32 [R], bbox int32 [R, 4]
+    (x, y, w, h).  ws / out: buffers of an earlier call of the same shape, reused.  No wait for the host."""
+    _words(bits, "bits")
+    R, H, Wd = bits.shape
+    cap_runs = 4 * 32 * Wd if cap_runs is None else int(cap_runs)
+    if cap_runs < 1:
+        raise ValueError("mask_rle: cap_runs must be >= 1")
+    cap_bytes = cap_runs * mask_rle_max_chars(H, 32 * Wd)
+    h_all = w_all = per = stride = 0
+    if image_info is not None:
+        if size is not None:
+            raise ValueError("mask_rle: give size or image_info, not both")
+        _req(image_info, "image_info")
+        if image_info.dim() != 2 or image_info.shape[1] < 2 or R % image_info.shape[0]:
+            raise ValueError("mask_rle: image_info must be [B, >=2] with R a multiple of B")
+        per, stride = R // image_info.shape[0], image_info.shape[1]
+    else:
+        h_all, w_all = (H, 32 * Wd) if size is None else (int(size[0]), int(size[1]))
+        if not (1 <= h_all <= H and 1 <= w_all <= 32 * Wd):
+            raise ValueError("mask_rle: size must lie in [1, %d] x [1, %d]" % (H, 32 * Wd))
+    rstride = 0
+    if rois is not None:
+        _req(rois, "rois")
+        if rois.dim() != 2 or rois.shape[0] != R or rois.shape[1] < 5:
+            raise ValueError("mask_rle: rois must be [R, >=5]")
+        rstride = rois.shape[1]
+    need = mask_rle_workspace_bytes(R, H, Wd, cap_runs)
+    if need == 0:
+        raise ValueError("mask_rle: planes of at most 65535 masks x 65535 rows and fewer than 2^31 pixels")
+    dev = bits.device
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    _req(ws, "ws", torch.uint8)
+    if ws.numel() < need:
+        raise ValueError("mask_rle: workspace too small")
+    if out is None:
+        i = dict(dtype=torch.int32, device=dev)
+        out = {'n_runs': torch.empty(R, **i), 'counts': torch.empty(R, cap_runs, **i), 'n_bytes': torch.empty(R, **i),
+               'chars': torch.empty(R, cap_bytes, dtype=torch.uint8, device=dev), 'area': torch.empty(R, **i),
+               'bbox': torch.empty(R, 4, **i)}
+    for k, shape, dt in (('n_runs', (R,), torch.int32), ('counts', (R, cap_runs), torch.int32), ('n_bytes', (R,), torch.int32),
+                         ('chars', (R, cap_bytes), torch.uint8), ('area', (R,), torch.int32), ('bbox', (R, 4), torch.int32)):
+        _req(out[k], k, dt)
+        if out[k].numel() != R * (shape[1] if len(shape) > 1 else 1):
+            raise ValueError("mask_rle: out[%r] must hold %s" % (k, shape))
+    _check(lib().scda_mask_rle_hip(_p(bits), i32(R), i32(H), i32(Wd), _p(image_info), i32(stride), i32(per), i32(h_all), i32(w_all),
+                                   _p(rois), i32(rstride), i32(cap_runs), i32(cap_bytes), _p(ws), _p(out['n_runs']), _p(out['counts']),
+                                   _p(out['n_bytes']), _p(out['chars']), _p(out['area']), _p(out['bbox']), _stream()),
+           "scda_mask_rle_hip")
+    return out
+
+
+def mask_iou(dt_bits, gt_bits, size, iscrowd=None):
+    """maskApi.c's rleIou of packed masks on the device: dt_bits int32 [M, H, Wd], gt_bits int32 [N, H, Wd], size = (h, w) of the image
+    inside the planes, iscrowd uint8 [N] on the device or None -> (iou float64 [N, M], inter int32 [N, M] holding uint32 counts); the
+    box gate of the reference included (include/scda_ops.h)"""
+    _words(dt_bits, "dt_bits"); _words(gt_bits, "gt_bits")
+    M, H, Wd = dt_bits.shape
+    N = gt_bits.shape[0]
+    if tuple(gt_bits.shape[1:]) != (H, Wd) or M < 1 or N < 1:
+        raise ValueError("mask_iou: dt_bits [M, H, Wd] and gt_bits [N, H, Wd] with M, N >= 1")
+    h, w = int(size[0]), int(size[1])
+    if not (1 <= h <= H and 1 <= w <= 32 * Wd):
+        raise ValueError("mask_iou: size must lie in [1, %d] x [1, %d]" % (H, 32 * Wd))
+    if iscrowd is not None:
+        _req(iscrowd, "iscrowd", torch.uint8)
+        if iscrowd.numel() != N:
+            raise ValueError("mask_iou: iscrowd must be [N]")
+    need = int(lib().scda_mask_iou_workspace_bytes(i32(M), i32(N), i32(H), i32(Wd)))
+    if need == 0:
+        raise ValueError("mask_iou: planes of at most 65535 masks x 65535 rows and fewer than 2^31 pixels")
+    ws = torch.empty(need, dtype=torch.uint8, device=dt_bits.device)
+    iou = torch.empty(N, M, dtype=torch.float64, device=dt_bits.device)
+    inter = torch.empty(N, M, dtype=torch.int32, device=dt_bits.device)
+    _check(lib().scda_mask_iou_hip(_p(dt_bits), i32(M), _p(gt_bits), i32(N), i32(H), i32(Wd), i32(h), i32(w), _p(iscrowd), _p(ws),
+                                   _p(iou), _p(inter), _stream()), "scda_mask_iou_hip")
+    return iou, inter
 
 
 # ------------------------------------------------- convolution / GEMM -------
