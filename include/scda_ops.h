@@ -52,6 +52,16 @@ int scda_prof_collect(long long *launches, double *ms, double *flops, double *by
 /* test aid: {tile rows, tile cols, split-K count, 1 = direct-to-LDS kernel family} of the calling thread's most recent conv /
  * GEMM launch (the planner's choice, or the SCDA_PLAN_FORCE="bm,bn,splits" override when that is legal for the shape) */
 void scda_debug_last_plan(int *out4);
+/* test aid, no GPU needed: the complete launch decision (csrc/launch_plan.h LaunchDecision, its 16 ints in declaration order:
+ * family 0 register-staged / 1 direct-to-LDS / 2 bf16 x 9 / 3 small-Cin direct forward, x9 stream-K, bm, bn, splits, k_per_split, nx,
+ * ny, grid, swz, parity, nc, ncp, weight-gradient slab depth, reduce / fix-up launch follows, stream-K units per workgroup) the
+ * library takes for a convolution (dir 0 forward, 1 data gradient, 2 weight gradient, 3 weight + fused bias gradient) or a dense
+ * GEMM.  aligned: every pointer 16-byte aligned and a workspace present.  Nothing is launched or allocated; a 256-CU device is
+ * assumed, so the answer does not depend on the machine.  SCDA_PLAN_FORCE and the other plan variables act as in a real launch. */
+void scda_debug_plan_conv(int dir, int batch, int Cin, int IH, int IW, int Cout, int KH, int KW, int S, int P, int row_period,
+                          int aligned, size_t ws_bytes, int *out16);
+void scda_debug_plan_gemm(int M, int N, int K, int lda, int ldb, int ldc, int trans_a, int trans_b, int aligned, size_t ws_bytes,
+                          int *out16);
 /* test aid: launch order of the calling thread's most recent Winograd launches -- forward / data gradient {tile rows / 32,
  * 1 = contiguous pixel-block runs per XCD, gm (XCDs split gm x 8/gm over m-tile groups x runs; 1 = none), split-K count}, weight
  * gradient {K-splits, 0 = dealt as they come / 1 = whole splits per XCD / 2 = one split + one m-tile group per XCD} */

@@ -31,17 +31,11 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include <vector>
-
+#include "launch_plan.h"
 #include "mfma_tile.h"
 #include "wino_pack.h"
 
 namespace scda {
-
-static bool xcd_swizzle_enabled() {
-    static const bool on = [] { const char *v = getenv("SCDA_XCD_SWIZZLE"); return !(v && atoi(v) == 0); }();
-    return on;
-}
 
 // logical tile of this workgroup: (tx = N-tile, ty = M-tile, tz = K-split); grid is 1-D with nx*ny*nz workgroups
 __device__ __forceinline__ void tile_coords(const int nx, const int ny, const int swz, int &tx, int &ty, int &tz) {
@@ -2048,232 +2042,58 @@ SCDA_API long long scda_conv2d_pack_tiles(int Cout, int Cin, int KH, int KW, int
 }
 
 // ----------------------------- host-side dispatch --------------------------
-// Launch plan = (N-tile width, split-K count), chosen with a small occupancy model instead of fixed thresholds.
-// At these sizes a launch has only a few workgroups per CU, so WAVE QUANTISATION decides the speed: the direct-to-LDS
-// kernels keep 64 KB (128x128), 48 KB (128x64 / 64x128) or 32 KB (64x64) of LDS per workgroup = 2 / 3 / 4 resident per CU, a
-// CU needs >= 2 resident workgroups (2 waves per SIMD) to keep its MFMA pipe fed across the per-slab barrier, and a CU
-// that is left with ONE workgroup runs it at about half speed.  Measured: the conv3_2 weight gradient at 756 workgroups
-// (2.95 per CU -> a round of two, then a round of one) ran at 81 TFLOP/s, at 504 (one round of two) 101 TFLOP/s.
-//   time(plan) = flops / (model efficiency x 110 TFLOP/s) + split-K slab traffic (write + read) at 3 TB/s
-struct LaunchPlan { int bn, splits, bm; };
+// launch_plan.h DECIDES (kernel family, tile, split-K count, tile order, grid: the occupancy model and every rule live there, host
+// arithmetic only); the functions here build the geometry, ask for the decision, fill the geometry from it and launch the
+// instantiation it names.
+static_assert(lp::BK == BK && lp::X9_BM == GemmX9Cfg::BM && lp::X9_BN == GemmX9Cfg::BN, "launch_plan.h restates the kernels' constants");
 
 // tile shape / split count / kernel family of this thread's most recent GEMM-class launch (scda_debug_last_plan: the parity
 // tests force every instantiation through SCDA_PLAN_FORCE and must be able to tell that the forced one really ran)
 static thread_local int g_last_plan[4] = {0, 0, 0, 0};
-static void note_plan(int bm, int bn, int splits, int glds) { g_last_plan[0] = bm; g_last_plan[1] = bn; g_last_plan[2] = splits; g_last_plan[3] = glds; }
-
-static int resident_per_cu(int bm, int bn) { return bm == 256 ? 1 : ((bm == 128 && bn == 128) || bn == 256) ? 2 : (bm == 64 && bn == 64) ? 4 : 3; }
-static double tile_efficiency(int bm, int bn) { return bm == 256 ? 1.05 : ((bm == 128 && bn == 128) || bn == 256) ? 1.0 : (bm == 64 && bn == 64) ? 0.85 : 0.90; }
-// 1x1 convolutions (one filter tap): a K-slab never re-reads lines the previous slabs brought into L1 / L2 (a 3x3 layer's nine taps
-// of a channel group are consecutive slabs over the same input lines), every gather is a fresh L2 / HBM access, and what hides that
-// latency is the number of independent workgroups per CU, not the MFMA work per barrier: brute force over the ResNet-50 shapes
-// (scripts/tune_plans.py resnet) has the 64x64 tile (4 resident per CU) ahead of the 8-wave 256x128 tile by 7 - 23 % on EVERY 1x1
-// forward / data-gradient layer (head 512 -> 2048 on 25088 pixels: 470 vs 561 us), and level with it on every 3x3 layer.
-static double tile_efficiency_one_tap(int bm, int bn) { return (bm == 64 && bn == 64) ? 1.0 : (bm == 64 || (bm == 128 && bn == 64)) ? 0.9 : 0.85; }
-
-// time, in units of one workgroup running at full CU speed, for the busiest CU to finish c workgroups with p resident
-static double cu_rounds(int c, int p, bool eight_waves = false) {
-    if (eight_waves) return (double)c;   // an 8-wave workgroup keeps the CU's MFMA pipes fed on its own
-    double t = 0;
-    while (c > 0) {
-        const int r = c < p ? c : p;
-        t += r == 1 ? 2.0 : (double)r;
-        c -= r;
-    }
-    return t;
+static void note_plan(const lp::LaunchDecision &d) {
+    g_last_plan[0] = d.bm; g_last_plan[1] = d.bn;
+    g_last_plan[2] = d.x9_stream ? -1 : d.splits;      // -1: the bf16 x 9 kernel ran as a stream-K launch
+    g_last_plan[3] = lp::reported_family(d);
 }
 
-static double plan_cost(long long tiles, int splits, int bm, int bn, double flops, double out_bytes, bool one_tap = false) {
-    const long long wgs = tiles * splits;
-    const double ideal = (double)wgs / 256.0;
-    const double eff = ideal / cu_rounds(cdiv(wgs, 256), resident_per_cu(bm, bn), bm == 256) * (one_tap ? tile_efficiency_one_tap(bm, bn) : tile_efficiency(bm, bn));
-    double t = flops / (eff * 110e12);
-    if (splits > 1) t += 2.0 * splits * out_bytes / 3e12;
-    return t;
+// persistent workgroups of the bf16 x 9 kernel's stream-K form: the device's CU count
+static int x9_persistent_workgroups() {
+    static const int n_cu = [] { int d = 0, n = 0; if (hipGetDevice(&d) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d) != hipSuccess || n < 8) n = 256; return n / 8 * 8; }();
+    return n_cu;
 }
 
-// bn_lo..bn_hi: candidate N-tile widths (64 and/or 128); must_split: the kernel always writes slabs (weight gradient)
-static LaunchPlan plan_search(int M, int N, int K, int bm, bool allow64, bool allow128, bool must_split, size_t ws_bytes,
-                              int k_granule, bool allow256, bool allow_bm256, bool one_tap);
-
-// memoised per thread (the same ~60 shapes recur every iteration; launches come from the main and the autograd thread)
-static LaunchPlan plan_launch(int M, int N, int K, int bm, bool allow64, bool allow128, bool must_split, size_t ws_bytes,
-                              int k_granule, bool allow256 = false, bool allow_bm256 = false, bool one_tap = false) {
-    if (const char *f = getenv("SCDA_PLAN_FORCE")) {   // tuning aid: "bm,bn,splits" for every launch (scripts/tune_plans.py)
-        int fb = 0, fn = 0, fs = 0;
-        if (sscanf(f, "%d,%d,%d", &fb, &fn, &fs) == 3) {
-            const bool ok = (fb == bm || (fb == 256 && allow_bm256) || (fb == 64 && getenv("SCDA_PLAN_ALLOW_BM64"))) && ((fn == 64 && allow64) || (fn == 128 && allow128) || (fn == 256 && allow256)) &&
-                            !(fb == 256 && fn != 128) && fs >= 1 && (fs == 1 || (size_t)fs * M * N * sizeof(float) <= ws_bytes) &&
-                            fs <= (K / (k_granule * 2) > 0 ? K / (k_granule * 2) : 1);
-            if (ok) return LaunchPlan{fn, fs, fb};
-        }
-    }
-    if (const char *ov = getenv("SCDA_PLAN_OVERRIDE")) {   // tuning aid: "M,N,K:bm,bn,splits;..." for individual shapes, inside the real iteration
-        for (const char *q = ov; q && *q;) {
-            int m = 0, n = 0, k = 0, fb = 0, fn = 0, fs = 0;
-            if (sscanf(q, "%d,%d,%d:%d,%d,%d", &m, &n, &k, &fb, &fn, &fs) == 6 && m == M && n == N && k == K && !must_split) {
-                const bool ok = (fb == bm || (fb == 256 && allow_bm256) || fb == 64) && ((fn == 64 && allow64) || (fn == 128 && allow128) || (fn == 256 && allow256)) &&
-                                !(fb == 256 && fn != 128) && fs >= 1 && (fs == 1 || (size_t)fs * M * N * sizeof(float) <= ws_bytes);
-                if (ok) return LaunchPlan{fn, fs, fb};
-            }
-            q = strchr(q, ';');
-            if (q) ++q;
-        }
-    }
-    struct Key { int M, N, K, flags; size_t ws; };
-    struct Entry { Key k; LaunchPlan p; };
-    static thread_local std::vector<Entry> cache;
-    const Key key{M, N, K, bm | (allow64 << 8) | (allow128 << 9) | (must_split << 10) | (allow256 << 11) | (k_granule << 12) | (allow_bm256 << 20) | (one_tap << 21), ws_bytes};
-    for (const Entry &e : cache)
-        if (e.k.M == key.M && e.k.N == key.N && e.k.K == key.K && e.k.flags == key.flags && e.k.ws == key.ws) return e.p;
-    const LaunchPlan p = plan_search(M, N, K, bm, allow64, allow128, must_split, ws_bytes, k_granule, allow256, allow_bm256, one_tap);
-    if (getenv("SCDA_PLAN_LOG"))
-        fprintf(stderr, "[scda plan] M=%d N=%d K=%d %s-> tile %dx%d splits %d (%lld workgroups)\n", M, N, K, must_split ? "wgrad " : "",
-                p.bm, p.bn, p.splits, (long long)cdiv(M, p.bm) * cdiv(N, p.bn) * p.splits);
-    if (cache.size() < 512) cache.push_back(Entry{key, p});
-    return p;
-}
-
-static LaunchPlan plan_search(int M, int N, int K, int bm, bool allow64, bool allow128, bool must_split, size_t ws_bytes,
-                              int k_granule, bool allow256, bool allow_bm256, bool one_tap) {
-    const double flops = 2.0 * M * (double)N * K, out_bytes = (double)M * N * sizeof(float);
-    double best_t = 1e30;
-    int max_s = K / (k_granule * 4);   // at least 4 K-steps per split
-    if (max_s < 1) max_s = 1;
-    if (max_s > 256) max_s = 256;
-    while (max_s > 1 && (size_t)max_s * M * N * sizeof(float) > ws_bytes) --max_s;
-    LaunchPlan best{allow128 ? 128 : 64, 1, bm};
-    // tile-row candidates: the natural one; 256 (8 waves) where legal; 64 for 65..128-row problems (the decoder's 128-channel
-    // layers: 512 half-height tiles and no split-K beat 128 full tiles split four ways by ~6 %)
-    // ... and for 1x1 convolutions of any height (tile_efficiency_one_tap)
-    const bool allow_bm64 = bm == 128 && (M <= 128 || one_tap) && allow64 && !must_split && k_granule == BK;
-    for (int pass = 0; pass < 3; ++pass) {
-        if ((pass == 1 && !allow_bm256) || (pass == 2 && !allow_bm64)) continue;
-        const int tbm = pass == 1 ? 256 : pass == 2 ? 64 : bm;
-        for (int bn = 64; bn <= 256; bn *= 2) {
-            if ((bn == 64 && !allow64) || (bn == 128 && !allow128) || (bn == 256 && !allow256)) continue;
-            if (tbm == 256 && bn != 128) continue;
-            const long long tiles = (long long)cdiv(M, tbm) * cdiv(N, bn);
-            for (int sp = 1; sp <= max_s; ++sp) {
-                if (tiles * sp > 4096 && sp > 1) break;   // plenty of workgroups already: splitting only adds traffic
-                double t = plan_cost(tiles, sp, tbm, bn, flops, out_bytes, one_tap);
-                if (must_split && sp == 1) t += 2.0 * out_bytes / 3e12;
-                if (t < best_t) { best_t = t; best = LaunchPlan{bn, sp, tbm}; }
-            }
-        }
-    }
-    return best;
-}
-
-static int round_k_per_split(int K, int splits) {
-    int kps = (K + splits - 1) / splits;
-    kps = (kps + BK - 1) / BK * BK;
-    return kps;
-}
-
-template <int KH, int KW, int S, bool DGRAD>
-static int launch_conv(const float *Wm, const float *X, const ConvGeom &g0, Epi e, float *ws, size_t ws_bytes,
-                       hipStream_t st) {
-    ConvGeom g = g0;
-    // stride-2 data gradient on the direct-to-LDS kernel: class-major N axis, a quarter of the K-slabs per tile (ConvGeom::parity)
-    static const bool no_parity = getenv("SCDA_CONV_NO_PARITY") != nullptr;   // A/B knob
-    const bool parity = S == 2 && DGRAD && g.slab_aligned && (g.PH % 2) == 0 && (g.PW % 2) == 0 && KH * KW <= 32 && !no_parity;
-    g.parity = 0; g.nc = g.ncp = 0;
-    if (g.slab_aligned) {   // the LDS-DMA kernel addresses the images one tile touches with 32-bit lane offsets
-        const long long phw = (long long)g.PH * g.PW / (parity ? 4 : 1), per_image = (long long)g.CB * g.HB * g.WB * 4;
-        const long long images = std::min<long long>(g.batch, (256 + phw - 1) / phw + 1);
-        if (images * per_image >= (1LL << 31)) {
-            set_error("conv: %lld x %lld bytes of gathered tensor under one tile exceed the 2 GB a buffer descriptor addresses", images, per_image);
-            return SCDA_EINVAL;
-        }
-    }
-    const bool small_m = g.M <= 64;
-    const int BMv = small_m ? 64 : 128;
-    static const char *force = getenv("SCDA_CONV_BN");   // experiment knob: 64 | 128
-    const int fbn = force ? (atoi(force) == 64 ? 64 : 128) : 0;
-    const char *fbm = getenv("SCDA_CONV_BM");            // experiment / test knob: 256 forces the 8-wave tile where legal
-    const bool bm256_ok = g.slab_aligned && (g.M % 256) == 0 && !fbn;
-    static const bool no_one_tap = getenv("SCDA_PLAN_NO_ONE_TAP") != nullptr;   // A/B knob
-    // parity classes: a launch is four GEMMs of N / 4 pixels and (on average) K / 4 each
-    const int planN = parity ? g.N / 4 : g.N, planK = parity ? std::max(BK, g.K / 4 / BK * BK) : g.K;
-    LaunchPlan plan = plan_launch(g.M, planN, planK, BMv, fbn != 128, fbn != 64, false, ws_bytes / (parity ? 4 : 1), BK,
-                                  small_m && g.slab_aligned && !fbn, bm256_ok && !(fbm && atoi(fbm) != 256),
-                                  KH * KW == 1 && g.slab_aligned && !no_one_tap);
-    if (bm256_ok && fbm && atoi(fbm) == 256 && plan.bm != 256) {
-        plan.bm = 256; plan.bn = 128;
-        while (plan.splits > 1 && (size_t)plan.splits * g.M * g.N * sizeof(float) > ws_bytes) --plan.splits;
-    }
-    // <= 32 output rows on many pixels (the decoders' 64 -> 32 stage: 262144 pixels; the data gradient into the discriminators'
-    // 32-channel map): the 32 x 256 tile, one K pass.  SCDA_PLAN_FORCE=32,256,1 forces it wherever it is legal (tests),
-    // any other forced plan keeps it out.
-    {
-        static const bool no_bm32 = getenv("SCDA_CONV_NO_BM32") != nullptr;   // A/B knob
-        const char *f = getenv("SCDA_PLAN_FORCE");
-        int fb = 0, fnn = 0, fs = 0;
-        const bool forced = f && sscanf(f, "%d,%d,%d", &fb, &fnn, &fs) == 3;
-        const bool legal = g.M <= 32 && g.slab_aligned && !fbn;
-        if (legal && (forced ? (fb == 32 && fnn == 256 && fs == 1) : (!no_bm32 && planN >= (parity ? 64 * 256 : 256 * 256)))) plan = LaunchPlan{256, 1, 32};
-    }
-    const int BNv = plan.bn;
-    const int BMt = plan.bm;                             // tile rows of this launch (BMv unless the 8-wave tile was chosen)
-    int splits = plan.splits;
-    g.k_per_split = round_k_per_split(g.K, splits);
-    splits = cdiv(g.K, g.k_per_split);
-    g.nx = cdiv(g.N, BNv); g.ny = cdiv(g.M, BMt); g.swz = xcd_swizzle_enabled();
-    // many M-tiles whose weight panels together do not fit an XCD's L2 (the ResNet RoI head's 512 -> 2048 1x1: 32 panels = 4.2 MB,
-    // walked M-tile-fastest they were re-fetched for every pixel tile: 762 MB read for a 51 MB input): the grouped order of the
-    // dense GEMMs (tile_coords: 8 M-tiles at a time across all pixel tiles -- the input is read once per group instead)
-    static const bool no_group = getenv("SCDA_CONV_NO_MGROUP") != nullptr;   // A/B knob
-    if (!no_group && g.swz && !parity && g.ny >= 16 && (long long)g.nx * g.ny >= 1024 && (double)g.M * g.K * sizeof(float) > 4e6)
-        g.swz |= 2;
-    if (parity) {
-        const int pq = (g.PH / 2) * (g.PW / 2);
-        g.parity = 1;
-        g.nc = g.batch * pq;
-        g.ncp = cdiv(g.nc, BNv) * BNv;
-        g.dNCP = Div(g.ncp); g.dPQ = Div(pq); g.dPQW = Div(g.PW / 2);
-        g.nx = 4 * (g.ncp / BNv);
-        splits = std::max(1, std::min(plan.splits, (g.CB / BK) * KH * KW));   // the kernel divides each class's slabs evenly
-        while (splits > 1 && (size_t)splits * g.M * g.N * sizeof(float) > ws_bytes) --splits;
-    }
-    e.splits = splits;
-    e.ws = ws;
-    dim3 grid((unsigned)g.nx * g.ny * splits);
-    note_plan(BMt, BNv, splits, g.slab_aligned);
-    prof_begin(g.slab_aligned ? PK_CONV + ((DGRAD ? 2 : 0) + (BMt <= 64 ? 1 : 0)) * 3 + prof_shape(KH, S) : (int)PK_CONV_GATHER,
-               2.0 * g.M * (double)g.N * g.K, st,
-               4.0 * ((double)g.batch * g.CB * g.HB * g.WB + (double)g.M * g.K + (double)g.M * g.N));
-    g.mpad = conv_packed_mpad(g.M);
-#define CONV_LAUNCH(BM_, BN_)                                                                                            \
-    do {                                                                                                                 \
-        if (g.slab_aligned)                                                                                              \
-            hipLaunchKernelGGL((conv_igemm_glds_kernel<BM_, BN_, KH, KW, S, DGRAD>), grid, dim3(ConvGldsCfg<BM_, BN_>::THREADS), 0, st, Wm, X, g, e);  \
-        else                                                                                                             \
-            hipLaunchKernelGGL((conv_igemm_kernel<BM_, BN_, KH, KW, S, DGRAD>), grid, dim3(256), 0, st, Wm, X, g, e);        \
+static int gemm_x9_launch(const lp::LaunchDecision &d, const float *A, const float *B, float *C, int M, int N, int K, int lda, int ldb, int ldc,
+                          int trans_a, int trans_b, const float *bias, int bias_on_n, int act, float slope, int accumulate, void *ws, hipStream_t st) {
+    using X = GemmX9Cfg;
+    GemmGeom g{M, N, K, lda, ldb, ldc, d.k_per_split, zero_page(), d.nx, d.ny, d.swz};
+    if (!g.zp) { set_error("scda_gemm_hip: could not allocate the zero page"); return SCDA_ELAUNCH; }
+    Epi e{C, (float *)ws, bias, bias_on_n, act, slope, d.splits, accumulate, nullptr, 0.f};
+    X9Stream sk{d.x9_stream, K / BK, d.x9_r, x9_persistent_workgroups(), d.x9_stream ? (long long)d.nx * d.ny * (K / BK) : 0, (float *)ws};
+    const dim3 grid((unsigned)d.grid);
+    note_plan(d);
+    prof_begin(PK_GEMM, 2.0 * M * (double)N * K, st);
+#define X9_LAUNCH(TA_, TB_)                                                                                                       \
+    do {                                                                                                                          \
+        if (d.x9_stream) hipLaunchKernelGGL((gemm_x9_kernel<TA_, TB_, true>), grid, dim3(X::THREADS), 0, st, A, B, g, e, sk);     \
+        else hipLaunchKernelGGL((gemm_x9_kernel<TA_, TB_, false>), grid, dim3(X::THREADS), 0, st, A, B, g, e, sk);                \
     } while (0)
-    if (BMt == 256) hipLaunchKernelGGL((conv_igemm_glds_kernel<256, 128, KH, KW, S, DGRAD>), grid, dim3(ConvGldsCfg<256, 128>::THREADS), 0, st, Wm, X, g, e);
-    else if (BMt == 32) hipLaunchKernelGGL((conv_igemm_glds_kernel<32, 256, KH, KW, S, DGRAD>), grid, dim3(ConvGldsCfg<32, 256>::THREADS), 0, st, Wm, X, g, e);
-    else if (BMt == 64 && BNv == 256) hipLaunchKernelGGL((conv_igemm_glds_kernel<64, 256, KH, KW, S, DGRAD>), grid, dim3(ConvGldsCfg<64, 256>::THREADS), 0, st, Wm, X, g, e);
-    else if (BMt == 64 && BNv == 64) CONV_LAUNCH(64, 64);
-    else if (BMt == 64) CONV_LAUNCH(64, 128);
-    else if (BNv == 64) CONV_LAUNCH(128, 64);
-    else CONV_LAUNCH(128, 128);
-#undef CONV_LAUNCH
+    if (!trans_a && !trans_b) X9_LAUNCH(false, false);
+    else if (!trans_a && trans_b) X9_LAUNCH(false, true);
+    else if (trans_a && !trans_b) X9_LAUNCH(true, false);
+    else X9_LAUNCH(true, true);
+#undef X9_LAUNCH
     prof_end(st);
-    int rc = launch_status("conv_igemm_kernel");
-    if (rc || splits == 1) return rc;
-    const bool vec = (g.N & 3) == 0 && (g.dPHW.d & 3) == 0 && ((((uintptr_t)ws) | ((uintptr_t)e.out) | ((uintptr_t)e.mask_src)) & 15) == 0;
-    if (vec)
-        hipLaunchKernelGGL(conv_splitk_reduce_kernel<true>, dim3(ew_grid(((long long)g.M * g.N) >> 2)), dim3(256), 0, st, ws, splits, g.M,
-                           g.N, g.dPHW, e.bias, e.act, e.slope, e.out, e.mask_src, e.mask_slope);
-    else
-        hipLaunchKernelGGL(conv_splitk_reduce_kernel<false>, dim3(ew_grid((long long)g.M * g.N)), dim3(256), 0, st, ws, splits, g.M,
-                           g.N, g.dPHW, e.bias, e.act, e.slope, e.out, e.mask_src, e.mask_slope);
-    return launch_status("conv_splitk_reduce_kernel");
+    int rc = launch_status("gemm_x9_kernel");
+    if (rc || !d.reduce) return rc;
+    if (d.x9_stream) {   // tiles that a range boundary cut: summed in a fixed order
+        hipLaunchKernelGGL(gemm_x9_fixup_kernel, dim3((unsigned)(sk.G - 1), 4), dim3(256), 0, st, g, e, sk);
+        return launch_status("gemm_x9_fixup_kernel");
+    }
+    return launch_dense_reduce((const float *)ws, d.splits, (long long)M * N, N, bias, bias_on_n, act, slope, accumulate, C, nullptr, nullptr, 0, 0, st);
 }
 
-// the same combine for split-K slabs written by another translation unit (conv_wino.hip): ws [splits][M][N] in the natural
-// pixel order, N = batch * phw
+// the split-K combine of launch_conv, also for slabs written by another translation unit (conv_wino.hip): ws [splits][M][N] in
+// the natural pixel order, N = batch * phw
 int launch_conv_reduce(const float *ws, int splits, int M, int N, int phw, const float *bias, int act, float slope, float *out,
                        const float *mask_src, float mask_slope, hipStream_t st) {
     const Div d(phw);
@@ -2287,80 +2107,87 @@ int launch_conv_reduce(const float *ws, int splits, int M, int N, int phw, const
     return launch_status("conv_splitk_reduce_kernel");
 }
 
+template <int KH, int KW, int S, bool DGRAD>
+static int launch_conv(const lp::LaunchDecision &d, const float *Wm, const float *X, ConvGeom g, Epi e, float *ws, hipStream_t st) {
+    if (g.slab_aligned) {   // the LDS-DMA kernel addresses the images one tile touches with 32-bit lane offsets
+        const long long phw = (long long)g.PH * g.PW / (d.parity ? 4 : 1), per_image = (long long)g.CB * g.HB * g.WB * 4;
+        const long long images = std::min<long long>(g.batch, (256 + phw - 1) / phw + 1);
+        if (images * per_image >= (1LL << 31)) {
+            set_error("conv: %lld x %lld bytes of gathered tensor under one tile exceed the 2 GB a buffer descriptor addresses", images, per_image);
+            return SCDA_EINVAL;
+        }
+    }
+    g.k_per_split = d.k_per_split;
+    g.nx = d.nx; g.ny = d.ny; g.swz = d.swz;
+    g.parity = d.parity; g.nc = d.nc; g.ncp = d.ncp;
+    if (d.parity) {
+        const int pq = (g.PH / 2) * (g.PW / 2);
+        g.dNCP = Div(g.ncp); g.dPQ = Div(pq); g.dPQW = Div(g.PW / 2);
+    }
+    e.splits = d.splits;
+    e.ws = ws;
+    const dim3 grid((unsigned)d.grid);
+    note_plan(d);
+    prof_begin(g.slab_aligned ? PK_CONV + ((DGRAD ? 2 : 0) + (d.bm <= 64 ? 1 : 0)) * 3 + prof_shape(KH, S) : (int)PK_CONV_GATHER,
+               2.0 * g.M * (double)g.N * g.K, st,
+               4.0 * ((double)g.batch * g.CB * g.HB * g.WB + (double)g.M * g.K + (double)g.M * g.N));
+    g.mpad = conv_packed_mpad(g.M);
+#define CONV_LAUNCH(BM_, BN_)                                                                                            \
+    do {                                                                                                                 \
+        if (g.slab_aligned)                                                                                              \
+            hipLaunchKernelGGL((conv_igemm_glds_kernel<BM_, BN_, KH, KW, S, DGRAD>), grid, dim3(ConvGldsCfg<BM_, BN_>::THREADS), 0, st, Wm, X, g, e);  \
+        else                                                                                                             \
+            hipLaunchKernelGGL((conv_igemm_kernel<BM_, BN_, KH, KW, S, DGRAD>), grid, dim3(256), 0, st, Wm, X, g, e);        \
+    } while (0)
+    if (d.bm == 256) hipLaunchKernelGGL((conv_igemm_glds_kernel<256, 128, KH, KW, S, DGRAD>), grid, dim3(ConvGldsCfg<256, 128>::THREADS), 0, st, Wm, X, g, e);
+    else if (d.bm == 32) hipLaunchKernelGGL((conv_igemm_glds_kernel<32, 256, KH, KW, S, DGRAD>), grid, dim3(ConvGldsCfg<32, 256>::THREADS), 0, st, Wm, X, g, e);
+    else if (d.bm == 64 && d.bn == 256) hipLaunchKernelGGL((conv_igemm_glds_kernel<64, 256, KH, KW, S, DGRAD>), grid, dim3(ConvGldsCfg<64, 256>::THREADS), 0, st, Wm, X, g, e);
+    else if (d.bm == 64 && d.bn == 64) CONV_LAUNCH(64, 64);
+    else if (d.bm == 64) CONV_LAUNCH(64, 128);
+    else if (d.bn == 64) CONV_LAUNCH(128, 64);
+    else CONV_LAUNCH(128, 128);
+#undef CONV_LAUNCH
+    prof_end(st);
+    int rc = launch_status("conv_igemm_kernel");
+    if (rc || !d.reduce) return rc;
+    return launch_conv_reduce(ws, d.splits, g.M, g.N, (int)g.dPHW.d, e.bias, e.act, e.slope, e.out, e.mask_src, e.mask_slope, st);
+}
+
 // the weight gradients' combine (slabs [splits][M][N] + fused bias-gradient partials) for conv_wino.hip
 int launch_wgrad_reduce(const float *ws, int splits, long long total, int N, int accumulate, float *out, const float *db_ws, float *db,
                         int db_n, int db_accumulate, hipStream_t st) {
     return launch_dense_reduce(ws, splits, total, N, nullptr, 0, (int)ACT_NONE, 0.f, accumulate, out, db_ws, db, db_n, db_accumulate, st);
 }
 
+// ws_bytes: what the slabs may use (with db: the room of the bias-gradient partials [splits <= 256][M] behind them already taken off)
 template <int KH, int KW, int S>
-static int launch_wgrad(const float *dY, const float *X, WgradGeom g, float *dW, int accumulate, float *ws,
+static int launch_wgrad(const lp::LaunchDecision &d, const float *dY, const float *X, WgradGeom g, float *dW, int accumulate, float *ws,
                         size_t ws_bytes, hipStream_t st, float *db = nullptr, int db_accumulate = 0) {
-    if (db) {   // room for the bias-gradient partials [splits <= 256][M] behind the slabs
-        const size_t need = (size_t)256 * g.M * sizeof(float);
-        if (ws_bytes <= 2 * need) { set_error("conv wgrad: workspace too small for the fused bias gradient"); return SCDA_EINVAL; }
-        ws_bytes -= need;
-    }
-    const bool small = g.M <= 64;
-    const int BNv = (g.N <= 64) ? 64 : 128;
-    static const bool no_glds = getenv("SCDA_WGRAD_NO_GLDS") != nullptr;   // A/B knob
-    // the LDS-DMA kernel addresses one image of dY / X through a buffer descriptor with 32-bit lane offsets
-    const bool fits_2g = (long long)g.Cout * g.OH * g.OW * 4 < (1LL << 31) && (long long)g.Cin * g.IH * g.IW * 4 < (1LL << 31);
-    // K-slabs of 16 pixels must not straddle two images: OH*OW % 16 == 0.  (A partial last slab for batch-1 planes was built and
-    // measured: ResNet layer3's 50 x 84 weight gradients took 325 us on this kernel's general addressing path against 162 us on the
-    // register-staged one -- those layers have only 4200 pixels of K to amortise the pipeline over; removed.)
-    const bool glds = !no_glds && g.a_vec4 && (g.dOHW.d % BK) == 0 && fits_2g;
-    const char *fbm = getenv("SCDA_CONV_BM");                              // 256 forces the 8-wave tile where legal
-    const bool bm256_ok = glds && BNv == 128 && (g.M % 256) == 0;
-    LaunchPlan plan = plan_launch(g.M, g.N, g.K, small ? 64 : 128, BNv == 64, BNv == 128, true, ws_bytes, 32, false,
-                                  bm256_ok && !(fbm && atoi(fbm) != 256));
-    if (bm256_ok && fbm && atoi(fbm) == 256) plan.bm = 256;
-    // <= 32 output channels on the direct-to-LDS kernel: the 32 x 128 tile, same split count (SCDA_PLAN_FORCE=32,128,s forces it where
-    // legal; any other forced plan, or SCDA_WGRAD_NO_BM32, keeps it out)
-    {
-        static const bool no_bm32 = getenv("SCDA_WGRAD_NO_BM32") != nullptr;
-        const char *f = getenv("SCDA_PLAN_FORCE");
-        int fb = 0, fnn = 0, fs = 0;
-        const bool forced = f && sscanf(f, "%d,%d,%d", &fb, &fnn, &fs) == 3;
-        const bool legal = glds && g.M <= 32 && BNv == 128;
-        if (legal && (forced ? (fb == 32 && fnn == 128) : !no_bm32)) {
-            plan.bm = 32;
-            if (forced && fs >= 1 && (size_t)fs * g.M * g.N * sizeof(float) <= ws_bytes) plan.splits = fs;
-        }
-    }
-    const int BMv = plan.bm;
-    int splits = plan.splits;
-    if ((size_t)splits * g.M * g.N * sizeof(float) > ws_bytes) { set_error("conv wgrad: workspace too small"); return SCDA_EINVAL; }
-    g.k_per_split = (round_k_per_split(g.K, splits) + 31) / 32 * 32;
-    splits = cdiv(g.K, g.k_per_split);
-    g.nx = cdiv(g.N, BNv); g.ny = cdiv(g.M, BMv); g.swz = xcd_swizzle_enabled();
-    dim3 grid((unsigned)g.nx * g.ny * splits);
-    note_plan(BMv, BNv, splits, glds);
+    const bool glds = d.family == lp::FAM_GLDS;
+    if ((size_t)d.splits * g.M * g.N * sizeof(float) > ws_bytes) { set_error("conv wgrad: workspace too small"); return SCDA_EINVAL; }
+    if (db && !glds) { set_error("conv wgrad: the fused bias gradient needs OH*OW %% 16 == 0 and 16-byte aligned dy"); return SCDA_EINVAL; }
+    g.k_per_split = d.k_per_split;
+    g.nx = d.nx; g.ny = d.ny; g.swz = d.swz;
+    const dim3 grid((unsigned)d.grid);
+    note_plan(d);
     prof_begin(PK_CONV_WGRAD + prof_shape(KH, S), 2.0 * g.M * (double)g.N * g.K, st);
-    static const char *wbk_env = getenv("SCDA_WGRAD_BK");
-    // measured (SCDA_WGRAD_BK=16|32 A/B): 32-deep slabs gain 10-17 % for the 64-row tiles (conv1_x, decoder heads), lose
-    // up to 8 % for 128-row tiles
-    const bool bk32 = (wbk_env ? atoi(wbk_env) == 32 : small) && (g.k_per_split % 32) == 0;
 #define WGRAD_LAUNCH(BM_, BN_)                                                                                           \
     do {                                                                                                                 \
-        if (bk32) hipLaunchKernelGGL((conv_wgrad_kernel<BM_, BN_, KH, KW, S, 32>), grid, dim3(256), 0, st, dY, X, g, ws);   \
+        if (d.wbk == 32) hipLaunchKernelGGL((conv_wgrad_kernel<BM_, BN_, KH, KW, S, 32>), grid, dim3(256), 0, st, dY, X, g, ws);   \
         else hipLaunchKernelGGL((conv_wgrad_kernel<BM_, BN_, KH, KW, S, 16>), grid, dim3(256), 0, st, dY, X, g, ws);        \
     } while (0)
-    if (db && !glds) { set_error("conv wgrad: the fused bias gradient needs OH*OW %% 16 == 0 and 16-byte aligned dy"); return SCDA_EINVAL; }
-    float *db_ws = db ? ws + (size_t)splits * g.M * g.N : nullptr;
+    float *db_ws = db ? ws + (size_t)d.splits * g.M * g.N : nullptr;
 #define WGRAD_GLDS_LAUNCH(BM_, BN_) hipLaunchKernelGGL((conv_wgrad_glds_kernel<BM_, BN_, KH, KW, S>), grid, dim3(WgradGldsCfg<BM_, BN_>::THREADS), 0, st, dY, X, g, ws, db_ws)
-    if (glds && BMv == 256) {
-        hipLaunchKernelGGL((conv_wgrad_glds_kernel<256, 128, KH, KW, S>), grid, dim3(WgradGldsCfg<256, 128>::THREADS), 0, st, dY, X, g, ws, db_ws);
-    } else if (glds && BMv == 32) {
-        WGRAD_GLDS_LAUNCH(32, 128);
-    } else if (glds) {
-        if (small && BNv == 64) WGRAD_GLDS_LAUNCH(64, 64);
-        else if (small) WGRAD_GLDS_LAUNCH(64, 128);
-        else if (BNv == 64) WGRAD_GLDS_LAUNCH(128, 64);
+    if (glds) {
+        if (d.bm == 256) WGRAD_GLDS_LAUNCH(256, 128);
+        else if (d.bm == 32) WGRAD_GLDS_LAUNCH(32, 128);
+        else if (d.bm == 64 && d.bn == 64) WGRAD_GLDS_LAUNCH(64, 64);
+        else if (d.bm == 64) WGRAD_GLDS_LAUNCH(64, 128);
+        else if (d.bn == 64) WGRAD_GLDS_LAUNCH(128, 64);
         else WGRAD_GLDS_LAUNCH(128, 128);
-    } else if (small && BNv == 64) WGRAD_LAUNCH(64, 64);
-    else if (small) WGRAD_LAUNCH(64, 128);
-    else if (BNv == 64) WGRAD_LAUNCH(128, 64);
+    } else if (d.bm == 64 && d.bn == 64) WGRAD_LAUNCH(64, 64);
+    else if (d.bm == 64) WGRAD_LAUNCH(64, 128);
+    else if (d.bn == 64) WGRAD_LAUNCH(128, 64);
     else WGRAD_LAUNCH(128, 128);
 #undef WGRAD_LAUNCH
 #undef WGRAD_GLDS_LAUNCH
@@ -2368,7 +2195,7 @@ static int launch_wgrad(const float *dY, const float *X, WgradGeom g, float *dW,
     int rc = launch_status("conv_wgrad_kernel");
     if (rc) return rc;
     const long long total = (long long)g.M * g.N;
-    return launch_dense_reduce(ws, splits, total, g.N, nullptr, 0, (int)ACT_NONE, 0.f, accumulate, dW, db_ws, db, g.M,
+    return launch_dense_reduce(ws, d.splits, total, g.N, nullptr, 0, (int)ACT_NONE, 0.f, accumulate, dW, db_ws, db, g.M,
                                db_accumulate, st);
 }
 
@@ -2384,7 +2211,7 @@ using namespace scda;
     set_error("conv: unsupported kernel %dx%d stride %d (supported: 3x3 s1, 3x3 s2, 1x1 s1, 1x1 s2; forward also 7x7 s2)", KH, KW, S); \
     return SCDA_EINVAL;
 
-static int conv_out_dim(int in, int k, int s, int p) { return (in + 2 * p - k) / s + 1; }
+static bool aligned16(const void *a, const void *b, const void *c) { return ((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)c)) & 15) == 0; }
 
 // row_period argument of the conv entry points: the image is a stack of independent maps of `period` rows (ConvGeom::row_period).
 // validated period (0: plain image); -1 = illegal for this convolution
@@ -2400,7 +2227,7 @@ static int take_row_period(const char *who, int period, int IH, int KH, int KW, 
 SCDA_API size_t scda_conv2d_workspace_bytes(int batch, int Cin, int IH, int IW, int Cout, int KH, int KW, int S, int P) {
     // enough for: fwd/dgrad split-K slabs and wgrad slabs (<= 64 splits of the weight matrix,
     // bounded by 8 output-sized slabs)
-    const int OH = conv_out_dim(IH, KH, S, P), OW = conv_out_dim(IW, KW, S, P);
+    const int OH = lp::conv_out_dim(IH, KH, S, P), OW = lp::conv_out_dim(IW, KW, S, P);
     size_t out_elems = (size_t)batch * Cout * OH * OW, in_elems = (size_t)batch * Cin * IH * IW;
     size_t w_elems = (size_t)Cout * Cin * KH * KW;
     size_t a = 8 * (out_elems > in_elems ? out_elems : in_elems);
@@ -2412,9 +2239,6 @@ SCDA_API size_t scda_conv2d_workspace_bytes(int batch, int Cin, int IH, int IW, 
     return need > minimum ? need : minimum;
 }
 
-static int conv1x1_as_x9(const float *A, const float *B, float *C, int M, int N, int K, int lda, int ldb, int trans_a, int trans_b,
-                         const float *bias, int act, float slope, int accumulate, void *ws, size_t ws_bytes, hipStream_t st);
-
 SCDA_API int scda_conv2d_fwd_hip(const float *x, const float *w, const float *bias, float *y, int batch, int Cin, int IH,
                                  int IW, int Cout, int KH, int KW, int S, int P, int row_period_arg, int act, float slope, void *ws,
                                  size_t ws_bytes, void *stream) {
@@ -2422,7 +2246,8 @@ SCDA_API int scda_conv2d_fwd_hip(const float *x, const float *w, const float *bi
     if (row_period < 0) return SCDA_EINVAL;
     if (!x || !w || !y || batch <= 0 || Cin <= 0 || Cout <= 0) { set_error("scda_conv2d_fwd_hip: bad arguments"); return SCDA_EINVAL; }
     if (!zero_page()) { set_error("scda_conv2d_fwd_hip: could not allocate the zero page"); return SCDA_ELAUNCH; }
-    const int OH = conv_out_dim(IH, KH, S, P), OW = conv_out_dim(IW, KW, S, P);
+    const lp::ConvShape c{batch, Cin, IH, IW, Cout, KH, KW, S, P, row_period};
+    const int OH = c.OH(), OW = c.OW();
     if (OH <= 0 || OW <= 0) { set_error("scda_conv2d_fwd_hip: empty output"); return SCDA_EINVAL; }
     ConvGeom g;
     g.batch = batch; g.CB = Cin; g.HB = IH; g.WB = IW; g.PH = OH; g.PW = OW; g.pad = P;
@@ -2431,16 +2256,14 @@ SCDA_API int scda_conv2d_fwd_hip(const float *x, const float *w, const float *bi
     g.slab_aligned = (Cin % BK) == 0;
     g.zp = zero_page();
     g.row_period = row_period;
-    if (batch == 1 && KH == 1 && KW == 1 && S == 1 && P == 0 && g.slab_aligned) {      // w is packed [Cin][mpad]: the GEMM's A stored [K][M]
-        const int rc = conv1x1_as_x9(w, x, y, Cout, IH * IW, Cin, conv_packed_mpad(Cout), IH * IW, 1, 1, bias, act, slope, 0, ws, ws_bytes, as_stream(stream));
-        if (rc <= 0) return rc;
-    }
-    static const bool no_direct = getenv("SCDA_CONV_NO_SMALL_CIN_FWD") != nullptr;      // A/B knob
-    if (!no_direct && KH == 3 && KW == 3 && S == 1 && P == 1 && Cin <= 4 && !g.slab_aligned && row_period == 0 && IW >= 64) {
+    hipStream_t st = as_stream(stream);
+    const lp::LaunchDecision d = lp::decide_conv(c, false, ws && aligned16(w, x, y), false, ws_bytes, x9_persistent_workgroups(), lp::read_plan_env());
+    if (d.family == lp::FAM_X9)      // w is packed [Cin][mpad]: the GEMM's A stored [K][M]
+        return gemm_x9_launch(d, w, x, y, Cout, IH * IW, Cin, conv_packed_mpad(Cout), IH * IW, IH * IW, 1, 1, bias, 0, act, slope, 0, ws, st);
+    if (d.family == lp::FAM_SMALL_CIN) {
         // image-side 3x3 layer (VGG conv1_1): direct kernel on the tap-major [Cout][9 Cin] weights the gather kernel takes
         const dim3 grid((unsigned)cdiv(IW, 256), (unsigned)IH, (unsigned)batch);
-        hipStream_t st = as_stream(stream);
-        note_plan(0, 0, 1, 0);
+        note_plan(d);
         prof_begin(PK_CONV_GATHER, 2.0 * Cout * (double)g.N * g.K, st);
         if (Cin == 1) hipLaunchKernelGGL((conv3x3_small_cin_fwd_kernel<1>), grid, dim3(256), 0, st, x, w, bias, y, IH, IW, Cout, act, slope);
         else if (Cin == 2) hipLaunchKernelGGL((conv3x3_small_cin_fwd_kernel<2>), grid, dim3(256), 0, st, x, w, bias, y, IH, IW, Cout, act, slope);
@@ -2451,8 +2274,8 @@ SCDA_API int scda_conv2d_fwd_hip(const float *x, const float *w, const float *bi
     }
     Epi e{y, nullptr, bias, 0, act, slope, 1, 0, nullptr, 0.f};
     if (KH == 7 && KW == 7 && S == 2)   // the ResNet stem (3 -> 64, frozen in the reference: models/mask_rcnn/resnet.py:230-238): forward only
-        return launch_conv<7, 7, 2, false>(w, x, g, e, (float *)ws, ws_bytes, as_stream(stream));
-    CONV_DISPATCH(launch_conv, , false > (w, x, g, e, (float *)ws, ws_bytes, as_stream(stream)))
+        return launch_conv<7, 7, 2, false>(d, w, x, g, e, (float *)ws, st);
+    CONV_DISPATCH(launch_conv, , false > (d, w, x, g, e, (float *)ws, st))
 }
 
 // dx = dgrad(dy, wt) where wt = pack(w, for_dgrad=1) is [Cin][KH*KW][Cout] (scda_conv2d_pack_weight_hip)
@@ -2469,7 +2292,8 @@ SCDA_API int scda_conv2d_dgrad_act_hip(const float *dy, const float *wt, float *
     const int row_period = take_row_period("scda_conv2d_dgrad_hip", row_period_arg, IH, KH, KW, S, P);
     if (row_period < 0) return SCDA_EINVAL;
     if (!dy || !wt || !dx || batch <= 0) { set_error("scda_conv2d_dgrad_hip: bad arguments"); return SCDA_EINVAL; }
-    const int OH = conv_out_dim(IH, KH, S, P), OW = conv_out_dim(IW, KW, S, P);
+    const lp::ConvShape c{batch, Cin, IH, IW, Cout, KH, KW, S, P, row_period};
+    const int OH = c.OH(), OW = c.OW();
     ConvGeom g;
     g.batch = batch; g.CB = Cout; g.HB = OH; g.WB = OW; g.PH = IH; g.PW = IW; g.pad = P;
     g.M = Cin; g.N = batch * IH * IW; g.K = Cout * KH * KW; g.k_per_split = 0;
@@ -2478,19 +2302,19 @@ SCDA_API int scda_conv2d_dgrad_act_hip(const float *dy, const float *wt, float *
     g.zp = zero_page();
     g.row_period = row_period;
     if (!g.zp) { set_error("scda_conv2d_dgrad_hip: could not allocate the zero page"); return SCDA_ELAUNCH; }
-    if (batch == 1 && KH == 1 && KW == 1 && S == 1 && P == 0 && g.slab_aligned && !act_src) {   // wt is packed [Cout][mpad(Cin)]
-        const int rc = conv1x1_as_x9(wt, dy, dx, Cin, IH * IW, Cout, conv_packed_mpad(Cin), IH * IW, 1, 1, nullptr, (int)ACT_NONE, 0.f, 0, ws, ws_bytes, as_stream(stream));
-        if (rc <= 0) return rc;
-    }
+    hipStream_t st = as_stream(stream);
+    const lp::LaunchDecision d = lp::decide_conv(c, true, ws && aligned16(wt, dy, dx), act_src != nullptr, ws_bytes, x9_persistent_workgroups(), lp::read_plan_env());
+    if (d.family == lp::FAM_X9)      // wt is packed [Cout][mpad(Cin)]
+        return gemm_x9_launch(d, wt, dy, dx, Cin, IH * IW, Cout, conv_packed_mpad(Cin), IH * IW, IH * IW, 1, 1, nullptr, 0, (int)ACT_NONE, 0.f, 0, ws, st);
     Epi e{dx, nullptr, nullptr, 0, (int)ACT_NONE, 0.f, 1, 0, act_src, act_slope};
-    CONV_DISPATCH(launch_conv, , true > (wt, dy, g, e, (float *)ws, ws_bytes, as_stream(stream)))
+    CONV_DISPATCH(launch_conv, , true > (d, wt, dy, g, e, (float *)ws, st))
 }
 
 // dx [batch,Cin<=4,IH,IW] = data gradient of dy [batch,Cout,OH,OW]; w is the UNPACKED [Cout,Cin,KH,KW] weight
 SCDA_API int scda_conv2d_dgrad_small_cin_hip(const float *dy, const float *w, float *dx, int batch, int Cin, int IH, int IW,
                                              int Cout, int KH, int KW, int S, int P, void *stream) {
     if (!dy || !w || !dx || batch <= 0 || Cin <= 0 || Cin > 4 || Cout <= 0 || S <= 0) { set_error("scda_conv2d_dgrad_small_cin_hip: bad arguments"); return SCDA_EINVAL; }
-    const int OH = conv_out_dim(IH, KH, S, P), OW = conv_out_dim(IW, KW, S, P);
+    const int OH = lp::conv_out_dim(IH, KH, S, P), OW = lp::conv_out_dim(IW, KW, S, P);
     const size_t lds = (size_t)Cout * KH * KW * 4 * sizeof(float);
     if (lds > 64 * 1024) { set_error("scda_conv2d_dgrad_small_cin_hip: Cout=%d too large", Cout); return SCDA_EINVAL; }
     const long long total = (long long)batch * IH * IW;
@@ -2526,13 +2350,14 @@ SCDA_API int scda_conv2d_pack_weights_batched_hip(const float *base, float *out,
     return launch_status("pack_weights_batched_kernel");
 }
 
-SCDA_API int scda_conv2d_wgrad_hip(const float *dy, const float *x, float *dw, int batch, int Cin, int IH, int IW,
-                                   int Cout, int KH, int KW, int S, int P, int row_period_arg, int accumulate, void *ws, size_t ws_bytes,
-                                   void *stream) {
-    const int row_period = take_row_period("scda_conv2d_wgrad_hip", row_period_arg, IH, KH, KW, S, P);
+// both weight-gradient entry points (db: the fused bias gradient rides along)
+static int conv2d_wgrad(const char *who, const float *dy, const float *x, float *dw, float *db, int batch, int Cin, int IH, int IW, int Cout,
+                        int KH, int KW, int S, int P, int row_period_arg, int accumulate, int db_accumulate, void *ws, size_t ws_bytes,
+                        void *stream) {
+    const int row_period = take_row_period(who, row_period_arg, IH, KH, KW, S, P);
     if (row_period < 0) return SCDA_EINVAL;
-    if (!dy || !x || !dw || !ws) { set_error("scda_conv2d_wgrad_hip: bad arguments"); return SCDA_EINVAL; }
-    const int OH = conv_out_dim(IH, KH, S, P), OW = conv_out_dim(IW, KW, S, P);
+    const lp::ConvShape c{batch, Cin, IH, IW, Cout, KH, KW, S, P, row_period};
+    const int OH = c.OH(), OW = c.OW();
     WgradGeom g;
     g.batch = batch; g.Cin = Cin; g.IH = IH; g.IW = IW; g.Cout = Cout; g.OH = OH; g.OW = OW; g.pad = P;
     g.M = Cout; g.N = Cin * KH * KW; g.K = batch * OH * OW; g.k_per_split = 0;
@@ -2540,44 +2365,62 @@ SCDA_API int scda_conv2d_wgrad_hip(const float *dy, const float *x, float *dw, i
     g.a_vec4 = ((OH * OW) % 4) == 0 && (((uintptr_t)dy) & 15) == 0;
     g.zp = zero_page();
     g.row_period = row_period;
-    if (!g.zp) { set_error("scda_conv2d_wgrad_hip: could not allocate the zero page"); return SCDA_ELAUNCH; }
-    if (batch == 1 && KH == 1 && KW == 1 && S == 1 && P == 0) {      // dW[Cout][Cin] (+)= dY[Cout][HW] X[Cin][HW]^T: both K-contiguous
-        const int rc = conv1x1_as_x9(dy, x, dw, Cout, Cin, IH * IW, IH * IW, IH * IW, 0, 0, nullptr, (int)ACT_NONE, 0.f, accumulate, ws, ws_bytes, as_stream(stream));
-        if (rc <= 0) return rc;
+    if (!g.zp) { set_error("%s: could not allocate the zero page", who); return SCDA_ELAUNCH; }
+    if (db) {   // room for the bias-gradient partials [splits <= 256][M] behind the slabs
+        const size_t need = (size_t)256 * g.M * sizeof(float);
+        if (ws_bytes <= 2 * need) { set_error("conv wgrad: workspace too small for the fused bias gradient"); return SCDA_EINVAL; }
+        ws_bytes -= need;
     }
-    CONV_DISPATCH(launch_wgrad, > (dy, x, g, dw, accumulate, (float *)ws, ws_bytes, as_stream(stream)))
+    hipStream_t st = as_stream(stream);
+    const lp::LaunchDecision d = lp::decide_wgrad(c, (((uintptr_t)dy) & 15) == 0, aligned16(dy, x, dw), db != nullptr, ws_bytes,
+                                                  x9_persistent_workgroups(), lp::read_plan_env());
+    if (d.family == lp::FAM_X9)      // dW[Cout][Cin] (+)= dY[Cout][HW] X[Cin][HW]^T: both K-contiguous
+        return gemm_x9_launch(d, dy, x, dw, Cout, Cin, IH * IW, IH * IW, IH * IW, Cin, 0, 0, nullptr, 0, (int)ACT_NONE, 0.f, accumulate, ws, st);
+    CONV_DISPATCH(launch_wgrad, > (d, dy, x, g, dw, accumulate, (float *)ws, ws_bytes, st, db, db_accumulate))
+}
+
+SCDA_API int scda_conv2d_wgrad_hip(const float *dy, const float *x, float *dw, int batch, int Cin, int IH, int IW,
+                                   int Cout, int KH, int KW, int S, int P, int row_period, int accumulate, void *ws, size_t ws_bytes,
+                                   void *stream) {
+    if (!dy || !x || !dw || !ws) { set_error("scda_conv2d_wgrad_hip: bad arguments"); return SCDA_EINVAL; }
+    return conv2d_wgrad("scda_conv2d_wgrad_hip", dy, x, dw, nullptr, batch, Cin, IH, IW, Cout, KH, KW, S, P, row_period, accumulate, 0, ws,
+                        ws_bytes, stream);
 }
 
 SCDA_API int scda_conv2d_wgrad_bias_fusable(int batch, int Cout, int OH, int OW, const float *dy) {
     (void)batch; (void)Cout;
-    return ((OH * OW) % BK) == 0 && (((uintptr_t)dy) & 15) == 0 && !getenv("SCDA_WGRAD_NO_GLDS") && !getenv("SCDA_WGRAD_NO_BIAS_FUSE");
+    return ((OH * OW) % BK) == 0 && (((uintptr_t)dy) & 15) == 0;
 }
 
 SCDA_API int scda_conv2d_wgrad_bias_hip(const float *dy, const float *x, float *dw, float *db, int batch, int Cin, int IH,
-                                        int IW, int Cout, int KH, int KW, int S, int P, int row_period_arg, int accumulate, int db_accumulate,
+                                        int IW, int Cout, int KH, int KW, int S, int P, int row_period, int accumulate, int db_accumulate,
                                         void *ws, size_t ws_bytes, void *stream) {
-    const int row_period = take_row_period("scda_conv2d_wgrad_bias_hip", row_period_arg, IH, KH, KW, S, P);
-    if (row_period < 0) return SCDA_EINVAL;
     if (!dy || !x || !dw || !db || !ws) { set_error("scda_conv2d_wgrad_bias_hip: bad arguments"); return SCDA_EINVAL; }
-    const int OH = conv_out_dim(IH, KH, S, P), OW = conv_out_dim(IW, KW, S, P);
-    WgradGeom g;
-    g.batch = batch; g.Cin = Cin; g.IH = IH; g.IW = IW; g.Cout = Cout; g.OH = OH; g.OW = OW; g.pad = P;
-    g.M = Cout; g.N = Cin * KH * KW; g.K = batch * OH * OW; g.k_per_split = 0;
-    g.dOHW = Div(OH * OW); g.dOW = Div(OW);
-    g.a_vec4 = ((OH * OW) % 4) == 0 && (((uintptr_t)dy) & 15) == 0;
-    g.zp = zero_page();
-    g.row_period = row_period;
-    if (!g.zp) { set_error("scda_conv2d_wgrad_bias_hip: could not allocate the zero page"); return SCDA_ELAUNCH; }
-    CONV_DISPATCH(launch_wgrad, > (dy, x, g, dw, accumulate, (float *)ws, ws_bytes, as_stream(stream), db, db_accumulate))
+    return conv2d_wgrad("scda_conv2d_wgrad_bias_hip", dy, x, dw, db, batch, Cin, IH, IW, Cout, KH, KW, S, P, row_period, accumulate,
+                        db_accumulate, ws, ws_bytes, stream);
 }
 
 SCDA_API void scda_debug_last_plan(int *out4) {
     for (int i = 0; i < 4; ++i) out4[i] = g_last_plan[i];
 }
 
-static int x9_persistent_workgroups() {
-    static const int n_cu = [] { int d = 0, n = 0; if (hipGetDevice(&d) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d) != hipSuccess || n < 8) n = 256; return n / 8 * 8; }();
-    return n_cu;
+// the launch decision of a convolution (dir 0 forward, 1 data gradient, 2 weight gradient, 3 weight + fused bias gradient) /
+// of a dense GEMM, as lp::LaunchDecision's ints in declaration order.  Nothing is launched or allocated; 256 CUs are assumed, so
+// the answer does not depend on the machine.  aligned: every pointer 16-byte aligned and a workspace present
+static_assert(sizeof(lp::LaunchDecision) == 16 * sizeof(int), "scda_ops.h documents 16 ints");
+static void write_decision(const lp::LaunchDecision &d, int *out) { memcpy(out, &d, sizeof d); }
+
+SCDA_API void scda_debug_plan_conv(int dir, int batch, int Cin, int IH, int IW, int Cout, int KH, int KW, int S, int P, int row_period,
+                                   int aligned, size_t ws_bytes, int *out16) {
+    const lp::ConvShape c{batch, Cin, IH, IW, Cout, KH, KW, S, P, KH == 1 ? 0 : row_period};
+    if (dir == 3) ws_bytes -= std::min(ws_bytes, (size_t)256 * Cout * sizeof(float));
+    write_decision(dir < 2 ? lp::decide_conv(c, dir == 1, aligned != 0, false, ws_bytes, 256, lp::read_plan_env())
+                           : lp::decide_wgrad(c, aligned != 0, aligned != 0, dir == 3, ws_bytes, 256, lp::read_plan_env()), out16);
+}
+
+SCDA_API void scda_debug_plan_gemm(int M, int N, int K, int lda, int ldb, int ldc, int trans_a, int trans_b, int aligned, size_t ws_bytes,
+                                   int *out16) {
+    write_decision(lp::decide_gemm(M, N, K, lda, ldb, ldc, trans_a, trans_b, aligned != 0, ws_bytes, 256, lp::read_plan_env()), out16);
 }
 
 SCDA_API size_t scda_gemm_workspace_bytes(int M, int N, int K) {
@@ -2586,122 +2429,22 @@ SCDA_API size_t scda_gemm_workspace_bytes(int M, int N, int K) {
     return std::max((size_t)16 * M * N * sizeof(float), (size_t)2 * x9_persistent_workgroups() * GemmX9Cfg::BM * GemmX9Cfg::BN * sizeof(float));
 }
 
-static int gemm_x9_launch(const float *A, const float *B, float *C, int M, int N, int K, int lda, int ldb, int ldc, int trans_a, int trans_b,
-                          const float *bias, int bias_on_n, int act, float slope, int accumulate, void *ws, size_t ws_bytes, hipStream_t st) {
-    using X = GemmX9Cfg;
-    const int nx = cdiv(N, X::BN), ny = cdiv(M, X::BM);
-    const long long tiles = (long long)nx * ny;
-    const int n_cu = x9_persistent_workgroups();
-    // more tiles than CUs: the persistent stream-K form (SCDA_GEMM_X9_SK=0 keeps one workgroup per tile, =2 forces it for any count)
-    const char *sk_env = getenv("SCDA_GEMM_X9_SK");
-    const int sk_mode = sk_env ? atoi(sk_env) : 1;
-    const size_t slot_bytes = (size_t)2 * n_cu * X::BM * X::BN * sizeof(float);
-    const bool stream = !getenv("SCDA_GEMM_X9_SPLITS") && ws_bytes >= slot_bytes && (sk_mode == 2 || (sk_mode == 1 && tiles > n_cu));
-    // split-K (one workgroup per (tile, split)): fill the CUs when there are fewer tiles than CUs (>= 32 slabs per split);
-    // SCDA_GEMM_X9_SPLITS forces a count
-    int splits = 1;
-    if (const char *f = getenv("SCDA_GEMM_X9_SPLITS")) splits = atoi(f);
-    else if (!stream && tiles < 200) splits = (int)std::min<long long>((256 + tiles / 2) / tiles, std::max(1, K / BK / 32));
-    if (splits < 1) splits = 1;
-    if (ldc != N) splits = 1;
-    while (splits > 1 && (size_t)splits * M * N * sizeof(float) > ws_bytes) --splits;
-    GemmGeom g{M, N, K, lda, ldb, ldc, round_k_per_split(K, splits), zero_page(), nx, ny, xcd_swizzle_enabled()};
-    if (!g.zp) { set_error("scda_gemm_hip: could not allocate the zero page"); return SCDA_ELAUNCH; }
-    splits = cdiv(K, g.k_per_split);
-    static const bool no_mpart = getenv("SCDA_GEMM_NO_MPART") != nullptr;
-    if (!no_mpart && g.swz && g.ny >= 16 && (long long)g.nx * g.ny >= 1024 && (double)M * K * sizeof(float) > 4e6) g.swz |= 2;
-    Epi e{C, (float *)ws, bias, bias_on_n, act, slope, splits, accumulate, nullptr, 0.f};
-    X9Stream sk{0, K / BK, 0, n_cu, 0, (float *)ws};
-    if (stream) {
-        sk.sk = 1;
-        sk.U = tiles * sk.spt;
-        sk.R = (int)((sk.U + n_cu - 1) / n_cu);
-    }
-    dim3 grid(stream ? (unsigned)n_cu : (unsigned)(tiles * splits));
-    note_plan(X::BM, X::BN, stream ? -1 : splits, 2);      // [3] = 2: the bf16 x 9 kernel ran; [2] = -1: as a stream-K launch
-    prof_begin(PK_GEMM, 2.0 * M * (double)N * K, st);
-#define X9_LAUNCH(TA_, TB_)                                                                                                       \
-    do {                                                                                                                          \
-        if (stream) hipLaunchKernelGGL((gemm_x9_kernel<TA_, TB_, true>), grid, dim3(X::THREADS), 0, st, A, B, g, e, sk);          \
-        else hipLaunchKernelGGL((gemm_x9_kernel<TA_, TB_, false>), grid, dim3(X::THREADS), 0, st, A, B, g, e, sk);                \
-    } while (0)
-    if (!trans_a && !trans_b) X9_LAUNCH(false, false);
-    else if (!trans_a && trans_b) X9_LAUNCH(false, true);
-    else if (trans_a && !trans_b) X9_LAUNCH(true, false);
-    else X9_LAUNCH(true, true);
-#undef X9_LAUNCH
-    prof_end(st);
-    int rc = launch_status("gemm_x9_kernel");
-    if (rc) return rc;
-    if (stream) {
-        if (sk.U % sk.R == 0 && sk.R % sk.spt == 0) return SCDA_OK;      // every range is whole tiles: nothing was cut
-        hipLaunchKernelGGL(gemm_x9_fixup_kernel, dim3((unsigned)(n_cu - 1), 4), dim3(256), 0, st, g, e, sk);
-        return launch_status("gemm_x9_fixup_kernel");
-    }
-    if (splits == 1) return rc;
-    return launch_dense_reduce((const float *)ws, splits, (long long)M * N, N, bias, bias_on_n, act, slope, accumulate, C, nullptr, nullptr, 0, 0, st);
-}
-
-// may this product run on the direct-to-LDS GEMM kernels (whole 16-deep slabs, 16-byte addressable rows, 32-bit lane offsets)?
-static bool gemm_glds_operands_ok(const float *A, const float *B, int M, int N, int K, int lda, int ldb, int trans_a, int trans_b) {
-    return (K % BK) == 0 && (lda % 4) == 0 && (ldb % 4) == 0 && ((((uintptr_t)A) | ((uintptr_t)B)) & 15) == 0 &&
-           (!trans_a || (M % 4) == 0) && (!trans_b || (N % 4) == 0) && (long long)lda * 1024 + (long long)M * 4 < (1LL << 31) &&
-           (long long)ldb * 1024 + (long long)N * 4 < (1LL << 31);
-}
-
-// should it take the exact-product bf16 x 9 kernel?  SCDA_GEMM_X9: 0 never, 2 whatever its size (tests), default: the FC-sized ones
-static bool gemm_x9_wanted(int M, int N, int K) {
-    if (getenv("SCDA_PLAN_FORCE")) return false;      // a forced (tile, split) plan names an fp32-MFMA instantiation: that one runs
-    const char *x9_env = getenv("SCDA_GEMM_X9");      // (read per call: tests switch it)
-    const int x9_mode = x9_env ? atoi(x9_env) : 1;
-    return x9_mode == 2 || (x9_mode == 1 && M >= 256 && N >= 128 && K >= 256 && (double)M * N * K >= 4e9);
-}
-
-// A batch-1 1x1 convolution IS a dense GEMM on the NCHW tensors as they lie: Y[Cout][HW] = W[Cout][Cin] X[Cin][HW] (and its two
-// gradients likewise).  The ones that are large in every dimension -- the ResNet-50 C4 detector's layer3 / RoI-head bottlenecks
-// (models/mask_rcnn/resnet.py:111-148: 1024 <-> 512 <-> 2048 channels on 25088 stacked pixels) -- take the bf16 x 9 kernel; returns
-// +1 (not a status code) when the call is not one of them (the caller goes on to the convolution kernels).  SCDA_CONV1X1_X9=0 turns the routing off.
-static int conv1x1_as_x9(const float *A, const float *B, float *C, int M, int N, int K, int lda, int ldb, int trans_a, int trans_b,
-                         const float *bias, int act, float slope, int accumulate, void *ws, size_t ws_bytes, hipStream_t st) {
-    static const bool off = [] { const char *v = getenv("SCDA_CONV1X1_X9"); return v && atoi(v) == 0; }();
-    if (off || !ws || (((uintptr_t)C) & 15) || !gemm_glds_operands_ok(A, B, M, N, K, lda, ldb, trans_a, trans_b) || !gemm_x9_wanted(M, N, K)) return 1;
-    return gemm_x9_launch(A, B, C, M, N, K, lda, ldb, N, trans_a, trans_b, bias, 0, act, slope, accumulate, ws, ws_bytes, st);
-}
-
 // C[M][N] (ldc) = op(A) op(B) (+bias) -> act ; trans_a: A stored [K][M]; trans_b: B stored [K][N]
 SCDA_API int scda_gemm_hip(const float *A, const float *B, float *C, int M, int N, int K, int lda, int ldb, int ldc,
                            int trans_a, int trans_b, const float *bias, int bias_on_n, int act, float slope,
                            int accumulate, void *ws, size_t ws_bytes, void *stream) {
     if (!A || !B || !C || M <= 0 || N <= 0 || K <= 0) { set_error("scda_gemm_hip: bad arguments"); return SCDA_EINVAL; }
     hipStream_t st = as_stream(stream);
-    // direct-to-LDS kernel: whole 16-deep slabs, 16-byte addressable rows
-    static const bool no_glds = getenv("SCDA_GEMM_NO_GLDS") != nullptr;   // A/B knob
-    // (+ 32-bit lane offsets inside a descriptor: 256 rows of either operand stay below 2 GB)
-    const bool glds = !no_glds && gemm_glds_operands_ok(A, B, M, N, K, lda, ldb, trans_a, trans_b);
+    const lp::LaunchDecision d = lp::decide_gemm(M, N, K, lda, ldb, ldc, trans_a, trans_b, aligned16(A, B, nullptr), ws_bytes,
+                                                 x9_persistent_workgroups(), lp::read_plan_env());
     // exact-product bf16 x 9 form (gemm_x9_kernel): the FC-sized products; SCDA_GEMM_X9=0 keeps them on the fp32 MFMA
-    if (glds && gemm_x9_wanted(M, N, K))
-        return gemm_x9_launch(A, B, C, M, N, K, lda, ldb, ldc, trans_a, trans_b, bias, bias_on_n, act, slope, accumulate, ws, ws_bytes, st);
-    const char *fbm = getenv("SCDA_CONV_BM");                              // 256 forces the 8-wave tile where legal
-    // (not for the [K][M] x [K][N] form -- the FC weight gradient: measured 112 vs 115 TFLOP/s)
-    const bool bm256_ok = glds && (M % 256) == 0 && N > 64 && !(trans_a && trans_b);
-    // (FC6 dgrad: 784 128-wide tiles = 3.06 per CU, the busiest CU carries 4 -> the plan takes another tile shape)
-    LaunchPlan plan = plan_launch(M, N, K, (M <= 64) ? 64 : 128, true, N > 64, false, ldc == N ? ws_bytes : 0, BK, false,
-                                  bm256_ok && !(fbm && atoi(fbm) != 256));
-    if (bm256_ok && fbm && atoi(fbm) == 256) { plan.bm = 256; plan.bn = 128; }
-    const int BMv = plan.bm;
-    const int BNv = plan.bn;
-    int splits = plan.splits;
-    if (splits > 1 && ldc != N) { set_error("scda_gemm_hip: split-K needs ldc == N"); return SCDA_EINVAL; }
-    GemmGeom g{M, N, K, lda, ldb, ldc, round_k_per_split(K, splits), zero_page(), cdiv(N, BNv), cdiv(M, BMv),
-               xcd_swizzle_enabled()};
+    if (d.family == lp::FAM_X9)
+        return gemm_x9_launch(d, A, B, C, M, N, K, lda, ldb, ldc, trans_a, trans_b, bias, bias_on_n, act, slope, accumulate, ws, st);
+    if (d.splits > 1 && ldc != N) { set_error("scda_gemm_hip: split-K needs ldc == N"); return SCDA_EINVAL; }
+    GemmGeom g{M, N, K, lda, ldb, ldc, d.k_per_split, zero_page(), d.nx, d.ny, d.swz};
     if (!g.zp) { set_error("scda_gemm_hip: could not allocate the zero page"); return SCDA_ELAUNCH; }
-    splits = cdiv(K, g.k_per_split);
-    static const bool no_mpart = getenv("SCDA_GEMM_NO_MPART") != nullptr;   // A/B knob
-    // the A operand does not fit one XCD's L2 but a quarter of it does: grouped tile order (see tile_coords)
-    if (!no_mpart && g.swz && g.ny >= 16 && (long long)g.nx * g.ny >= 1024 && (double)M * K * sizeof(float) > 4e6)
-        g.swz |= 2;
-    Epi e{C, (float *)ws, bias, bias_on_n, act, slope, splits, accumulate, nullptr, 0.f};
-    dim3 grid((unsigned)g.nx * g.ny * splits);
+    Epi e{C, (float *)ws, bias, bias_on_n, act, slope, d.splits, accumulate, nullptr, 0.f};
+    const dim3 grid((unsigned)d.grid);
 #define GEMM_LAUNCH(BM_, BN_)                                                                            \
     do {                                                                                                 \
         if (!trans_a && !trans_b) hipLaunchKernelGGL((gemm_kernel<BM_, BN_, false, false>), grid, dim3(256), 0, st, A, B, g, e); \
@@ -2716,22 +2459,22 @@ SCDA_API int scda_gemm_hip(const float *A, const float *B, float *C, int M, int 
         else if (trans_a && !trans_b) hipLaunchKernelGGL((gemm_glds_kernel<BM_, BN_, true, false>), grid, dim3(GemmGldsCfg<BM_, BN_>::THREADS), 0, st, A, B, g, e); \
         else hipLaunchKernelGGL((gemm_glds_kernel<BM_, BN_, true, true>), grid, dim3(GemmGldsCfg<BM_, BN_>::THREADS), 0, st, A, B, g, e);  \
     } while (0)
-    note_plan(BMv, BNv, splits, glds);
+    note_plan(d);
     prof_begin(PK_GEMM, 2.0 * M * (double)N * K, st);
-    if (glds) {
-        if (BMv == 256) GEMM_GLDS_LAUNCH(256, 128);
-        else if (BMv == 64 && BNv == 64) GEMM_GLDS_LAUNCH(64, 64);
-        else if (BMv == 64) GEMM_GLDS_LAUNCH(64, 128);
-        else if (BNv == 64) GEMM_GLDS_LAUNCH(128, 64);
+    if (d.family == lp::FAM_GLDS) {
+        if (d.bm == 256) GEMM_GLDS_LAUNCH(256, 128);
+        else if (d.bm == 64 && d.bn == 64) GEMM_GLDS_LAUNCH(64, 64);
+        else if (d.bm == 64) GEMM_GLDS_LAUNCH(64, 128);
+        else if (d.bn == 64) GEMM_GLDS_LAUNCH(128, 64);
         else GEMM_GLDS_LAUNCH(128, 128);
-    } else if (BMv == 64 && BNv == 64) GEMM_LAUNCH(64, 64);
-    else if (BMv == 64) GEMM_LAUNCH(64, 128);
-    else if (BNv == 64) GEMM_LAUNCH(128, 64);
+    } else if (d.bm == 64 && d.bn == 64) GEMM_LAUNCH(64, 64);
+    else if (d.bm == 64) GEMM_LAUNCH(64, 128);
+    else if (d.bn == 64) GEMM_LAUNCH(128, 64);
     else GEMM_LAUNCH(128, 128);
     prof_end(st);
     int rc = launch_status("gemm_kernel");
-    if (rc || splits == 1) return rc;
+    if (rc || !d.reduce) return rc;
     const long long total = (long long)M * N;
-    return launch_dense_reduce((const float *)ws, splits, total, N, bias, bias_on_n, act, slope, accumulate, C, nullptr, nullptr,
+    return launch_dense_reduce((const float *)ws, d.splits, total, N, bias, bias_on_n, act, slope, accumulate, C, nullptr, nullptr,
                                0, 0, st);
 }

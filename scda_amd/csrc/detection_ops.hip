@@ -983,8 +983,8 @@ SCDA_API int scda_roi_pool_fwd_hip(const float *features, const float *rois, int
     if (R == 0) return SCDA_OK;
     if (!features || !rois || !out) { set_error("scda_roi_pool_fwd_hip: null pointer"); return SCDA_EINVAL; }
     const long long total = (long long)R * C * PH * PW;
-    static const bool flat_form = getenv("SCDA_ROIPOOL_FWD_FLAT") != nullptr;      // A/B knob: one thread per output element, 64-bit index math
-    if (!flat_form && R <= 65535 && (long long)C * PH * PW < (1LL << 30)) {
+    // one block column per RoI; past the grid's y limit: one thread per output element, 64-bit index math
+    if (R <= 65535 && (long long)C * PH * PW < (1LL << 30)) {
         const int per_roi = C * PH * PW;
         const dim3 grid((unsigned)std::min((per_roi + 255) / 256, 64), (unsigned)R);
         if (PH == 7 && PW == 7)
@@ -1010,14 +1010,13 @@ SCDA_API int scda_roi_pool_bwd_hip(const float *top_grad, const int32_t *argmax,
         return e == hipSuccess ? SCDA_OK : SCDA_ELAUNCH;
     }
     if (!top_grad || !argmax || !rois) { set_error("scda_roi_pool_bwd_hip: null pointer"); return SCDA_EINVAL; }
-    static const bool force_gather = getenv("SCDA_ROIPOOL_BWD_GATHER") != nullptr;   // A/B knob
     const size_t per = ((size_t)H * W + kScatterBands - 1) / kScatterBands;
     const size_t scatter_lds = per * 8 * kScatterBands + (size_t)2 * kScatterChunk * 64 * 8;
     // more than 64 KB of dynamic LDS must be asked for once per kernel; if the runtime refuses, the gather kernel below takes the shape
     static const bool big_lds_ok = hipFuncSetAttribute(reinterpret_cast<const void *>(roi_pool_bwd_scatter_kernel),
                                                        hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) == hipSuccess;
     if (!big_lds_ok) (void)hipGetLastError();
-    if (PH * PW <= 64 && scatter_lds <= (big_lds_ok ? 96 : 64) * (size_t)1024 && !force_gather) {
+    if (PH * PW <= 64 && scatter_lds <= (big_lds_ok ? 96 : 64) * (size_t)1024) {
         hipLaunchKernelGGL(roi_pool_bwd_scatter_kernel, dim3(B * C), dim3(64 * kScatterBands), scatter_lds, as_stream(stream),
                            top_grad, argmax, rois, R, C, H * W, PH * PW, bottom_grad);
         return launch_status("roi_pool_bwd_scatter_kernel");

@@ -1393,6 +1393,33 @@ def last_plan():
     return out[0], out[1], out[2], (2 if out[3] == 2 else bool(out[3]))
 
 
+PLAN_FIELDS = ("family", "x9_stream", "bm", "bn", "splits", "k_per_split", "nx", "ny", "grid", "swz", "parity", "nc", "ncp", "wbk",
+               "reduce", "x9_r")
+
+
+def plan_conv(direction, batch, cin, ih, iw, cout, k, stride, pad, row_period=0, aligned=True, ws_bytes=None):
+    """the launch decision (PLAN_FIELDS, see scda_ops.h) of a convolution: direction "fwd" | "dgrad" | "wgrad" | "wgrad_bias".  No GPU
+    needed; ws_bytes defaults to what the operators pass (scda_conv2d_workspace_bytes)"""
+    L = lib()
+    if ws_bytes is None:
+        L.scda_conv2d_workspace_bytes.restype = ctypes.c_size_t
+        ws_bytes = L.scda_conv2d_workspace_bytes(i32(batch), i32(cin), i32(ih), i32(iw), i32(cout), i32(k), i32(k), i32(stride), i32(pad))
+    out = (ctypes.c_int * 16)()
+    L.scda_debug_plan_conv(i32(("fwd", "dgrad", "wgrad", "wgrad_bias").index(direction)), i32(batch), i32(cin), i32(ih), i32(iw), i32(cout),
+                           i32(k), i32(k), i32(stride), i32(pad), i32(row_period), i32(int(aligned)), _sz(ws_bytes), out)
+    return dict(zip(PLAN_FIELDS, out))
+
+
+def plan_gemm(M, N, K, lda, ldb, trans_a=False, trans_b=False, aligned=True, ws_bytes=None, ldc=None):
+    """the launch decision of a dense GEMM as gemm() would issue it, for a 256-CU device.  No GPU needed"""
+    if ws_bytes is None:      # scda_gemm_workspace_bytes at 256 CUs (the entry itself asks the device)
+        ws_bytes = max(16 * M * N * 4, 2 * 256 * 256 * 128 * 4)
+    out = (ctypes.c_int * 16)()
+    lib().scda_debug_plan_gemm(i32(M), i32(N), i32(K), i32(lda), i32(ldb), i32(N if ldc is None else ldc), i32(int(trans_a)), i32(int(trans_b)),
+                               i32(int(aligned)), _sz(ws_bytes), out)
+    return dict(zip(PLAN_FIELDS, out))
+
+
 def wino_last_persistent():
     """was this thread's most recent Winograd forward / data-gradient launch the persistent form (one workgroup per CU walking the tiles)?"""
     return bool(lib().scda_debug_wino_last_persistent())
