@@ -62,6 +62,21 @@ void scda_debug_plan_conv(int dir, int batch, int Cin, int IH, int IW, int Cout,
                           int aligned, size_t ws_bytes, int *out16);
 void scda_debug_plan_gemm(int M, int N, int K, int lda, int ldb, int ldc, int trans_a, int trans_b, int aligned, size_t ws_bytes,
                           int *out16);
+/* which kernels a convolution takes (csrc/launch_plan.h route_conv; no GPU needed): dir 0 forward, 1 data gradient, 2 weight gradient,
+ * the shape as the forward convolution has it -> 0 implicit GEMM, 1 Winograd, 2 Winograd on stacked 7 x 7 maps.  *pool (may be NULL):
+ * the forward may run conv + activation + 2x2 max-pool as one launch (scda_conv2d_wino_pool_hip); *maps (may be NULL): the image is a
+ * stack of that many 7 x 7 maps (row_period 7, IW 7, batch 1), else 0.  SCDA_WINOGRAD=0, SCDA_WINO_STACKED=0 and
+ * SCDA_CONV_POOL_FUSE=0 keep the respective path out (the tests' reference paths); scda_conv2d_wino_enabled: SCDA_WINOGRAD is not 0. */
+int scda_conv2d_route(int dir, int batch, int Cin, int IH, int IW, int Cout, int KH, int KW, int S, int P, int row_period, int *pool,
+                      int *maps);
+int scda_conv2d_wino_enabled(void);
+/* test aid, no GPU needed: both Winograd launch decisions (csrc/launch_plan.h WinoDecision: tile rows / 32, pixel-block-major XCD order,
+ * gm, splits, slabs per split, items per XCD, workgroup slots, persistent form, epilogue 0 plain / 1 mask / 2 pool / 3 split-K slab;
+ * WinoWgradDecision: K-slabs, splits, slabs per split, splits per XCD, order as scda_debug_wino_last_order, grid) for
+ * y [batch, M, H, W] from x [batch, C, H, W] (stack > 0: that many 7 x 7 maps) and for the weight gradient of the layer with
+ * (Cin, Cout) = (C, M), on a 256-CU device.  The SCDA_WINO_* variables act as in a real launch. */
+void scda_debug_plan_wino(int batch, int C, int H, int W, int M, int stack, int pool, int masked, int with_db, size_t ws_bytes, int *fwd9,
+                          int *wgrad6);
 /* test aid: launch order of the calling thread's most recent Winograd launches -- forward / data gradient {tile rows / 32,
  * 1 = contiguous pixel-block runs per XCD, gm (XCDs split gm x 8/gm over m-tile groups x runs; 1 = none), split-K count}, weight
  * gradient {K-splits, 0 = dealt as they come / 1 = whole splits per XCD / 2 = one split + one m-tile group per XCD} */
@@ -339,7 +354,8 @@ int scda_conv2d_pack_weight_hip(const float *w, float *out, int Cout, int Cin, i
  * offset in floats from `out`, Cout, Cin, KH*KW, for_dgrad, first tile id}, destinations ascending and back to back, tile ids
  * consecutive: a row owns scda_conv2d_pack_tiles(...) of them; n_tiles = their sum.  for_dgrad 2 / 3 in a row (and in
  * scda_conv2d_packed_elems / scda_conv2d_pack_tiles): the Winograd kernel's transformed filters for the forward / the data gradient
- * (3x3 only; see scda_conv2d_wino_pack_hip below). */
+ * (see scda_conv2d_wino_pack_hip below; scda_conv2d_packed_elems returns 0 for a weight that has no such packing: not 3x3, or the
+ * reduced channel count is not a multiple of 8). */
 long long scda_conv2d_pack_tiles(int Cout, int Cin, int KH, int KW, int for_dgrad);
 int scda_conv2d_pack_weights_batched_hip(const float *base, float *out, const long long *desc, int n, long long n_tiles,
                                          void *stream);
@@ -397,8 +413,7 @@ int scda_conv2d_wino_hip(const float *x, const float *u, const float *bias, floa
  * full-resolution map is never written.  The pools of vgg_adver_expansion_cluster.py:101-114 behind conv1_2 / 2_2 / 3_3 / 4_3. */
 /* the same on x [1, C, maps * 7, 7] read as a vertical STACK of `maps` independent 7 x 7 maps (row period 7, see scda_conv2d_fwd_hip's
  * row_period: the channel-major RoI head of models/mask_rcnn/resnet.py:131-148): four maps per pixel block, as 8 x 8 each with row /
- * column 7 discarded; y [1, M, maps * 7, 7].  scda_conv2d_wino_stacked_supported: C % 8 == 0, tensors below 2 GB. */
-int scda_conv2d_wino_stacked_supported(int maps, int C, int M);
+ * column 7 discarded; y [1, M, maps * 7, 7].  Needs C % 8 == 0 and tensors below 2 GB. */
 int scda_conv2d_wino_stacked_hip(const float *x, const float *u, const float *bias, float *y, int maps, int C, int M, int act, float slope,
                                  const float *mask_src, float mask_slope, int for_dgrad, void *ws, size_t ws_bytes, void *stream);
 int scda_conv2d_wino_pool_hip(const float *x, const float *u, const float *bias, float *pool_y, unsigned char *pool_idx, int batch, int C,
@@ -410,8 +425,7 @@ int scda_conv2d_wino_wgrad_supported(int batch, int Cin, int H, int W, int Cout)
 int scda_conv2d_wino_wgrad_hip(const float *dy, const float *x, float *dw, float *db, int batch, int Cin, int H, int W, int Cout,
                                int accumulate, int db_accumulate, void *ws, size_t ws_bytes, void *stream);
 /* ... on dy [1, Cout, maps * 7, 7] / x [1, Cin, maps * 7, 7] read as stacks of `maps` independent 7 x 7 maps (row period 7, see
- * scda_conv2d_wino_stacked_hip): a K-slab is one tile row of a pair of maps */
-int scda_conv2d_wino_wgrad_stacked_supported(int maps, int Cin, int Cout);
+ * scda_conv2d_wino_stacked_hip): a K-slab is one tile row of a pair of maps; >= 64 channels on both sides */
 int scda_conv2d_wino_wgrad_stacked_hip(const float *dy, const float *x, float *dw, float *db, int maps, int Cin, int Cout, int accumulate,
                                        int db_accumulate, void *ws, size_t ws_bytes, void *stream);
 

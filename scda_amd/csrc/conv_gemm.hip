@@ -2328,7 +2328,8 @@ SCDA_API int scda_conv2d_dgrad_small_cin_hip(const float *dy, const float *w, fl
 }
 
 SCDA_API size_t scda_conv2d_packed_elems(int Cout, int Cin, int KH, int KW, int for_dgrad) {
-    if (for_dgrad >= 2) return (KH == 3 && KW == 3) ? (size_t)wino_packed_elems(for_dgrad == 3 ? Cin : Cout, for_dgrad == 3 ? Cout : Cin) : 0;
+    // (0: no Winograd packing -- not 3x3, or the reduced channel count is not whole K-slabs)
+    if (for_dgrad >= 2) return (KH == 3 && KW == 3 && ((for_dgrad == 3 ? Cout : Cin) % WINO_BK) == 0) ? (size_t)wino_packed_elems(for_dgrad == 3 ? Cin : Cout, for_dgrad == 3 ? Cout : Cin) : 0;
     const int C = for_dgrad ? Cout : Cin, M = for_dgrad ? Cin : Cout;
     const int mpad = (C % BK) == 0 ? conv_packed_mpad(M) : M;
     return (size_t)mpad * C * KH * KW;

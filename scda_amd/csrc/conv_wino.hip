@@ -33,6 +33,7 @@
 #include <algorithm>
 #include <type_traits>
 
+#include "launch_plan.h"
 #include "mfma_tile.h"
 #include "wino_pack.h"
 
@@ -980,9 +981,25 @@ __global__ __launch_bounds__(256) void wino_pack_kernel(const float *__restrict_
 
 using namespace scda;
 
-SCDA_API int scda_conv2d_wino_supported(int batch, int C, int H, int W, int M) {
-    return batch > 0 && M > 0 && C >= WBK && (C % WBK) == 0 && (H % 2) == 0 && (W % 2) == 0 && (long long)C * H * W * 4 < (1LL << 31) &&
-           (long long)M * H * W * 4 < (1LL << 31);
+// launch_plan.h DECIDES (route_conv: which convolutions come here; decide_wino / decide_wino_wgrad: tile rows, XCD order, split-K, the
+// persistent form); the launchers below check their arguments, build the kernels' geometry from the decision, launch and reduce.
+static_assert(lp::WINO_SLAB == WBK && lp::WINO_EPI_PLAIN == WEPI_PLAIN && lp::WINO_EPI_MASK == WEPI_MASK && lp::WINO_EPI_POOL == WEPI_POOL &&
+              lp::WINO_EPI_SPLIT == WEPI_SPLIT, "launch_plan.h restates the kernels' constants");
+
+SCDA_API int scda_conv2d_wino_supported(int batch, int C, int H, int W, int M) { return lp::wino_kernel_ok(batch, C, H, W, M, 0); }
+
+SCDA_API int scda_conv2d_wino_wgrad_supported(int batch, int Cin, int H, int W, int Cout) {
+    return lp::wino_wgrad_kernel_ok(batch, Cin, H, W, Cout, 0);
+}
+
+SCDA_API int scda_conv2d_wino_enabled(void) { return lp::read_wino_env().enabled; }
+
+SCDA_API int scda_conv2d_route(int dir, int batch, int Cin, int IH, int IW, int Cout, int KH, int KW, int S, int P, int row_period,
+                               int *pool, int *maps) {
+    const lp::ConvRoute r = lp::route_conv(dir, lp::ConvShape{batch, Cin, IH, IW, Cout, KH, KW, S, P, row_period}, lp::read_wino_env());
+    if (pool) *pool = r.pool;
+    if (maps) *maps = r.maps;
+    return r.family;
 }
 
 SCDA_API size_t scda_conv2d_wino_packed_elems(int Cout, int Cin, int for_dgrad) {
@@ -996,141 +1013,95 @@ SCDA_API int scda_conv2d_wino_pack_hip(const float *w, float *out, int Cout, int
     return launch_status("wino_pack_kernel");
 }
 
-// y [batch, M, H, W] = act(conv3x3(x [batch, C, H, W], stride 1, pad 1) + bias) (* act'(mask_src)); u = scda_conv2d_wino_pack_hip
-// test aid (scda_debug_wino_last_order): the launch order the calling thread's most recent launches took
-static thread_local int g_wino_last[4] = {0, 0, 0, 0};          // forward / data gradient: tile rows / 32, pixel-block-major?, gm, splits
-static thread_local int g_wino_last_persist = 0;
-static thread_local int g_wino_wgrad_last[2] = {0, 0};          // weight gradient: splits, 0 as they come / 1 whole splits per XCD / 2 split + m-tile group
+// test aid (scda_debug_wino_last_order / _last_persistent): what the calling thread's most recent launches were decided to be
+static thread_local struct { lp::WinoDecision fwd; lp::WinoWgradDecision wgrad; } g_wino_last;
+
+SCDA_API int scda_debug_wino_last_persistent(void) { return g_wino_last.fwd.persist; }
+
+SCDA_API void scda_debug_wino_last_order(int *out6) {
+    const lp::WinoDecision &d = g_wino_last.fwd;
+    out6[0] = d.mb; out6[1] = d.pixel_major; out6[2] = d.gm; out6[3] = d.splits;
+    out6[4] = g_wino_last.wgrad.splits; out6[5] = g_wino_last.wgrad.order;
+}
+
+// both decisions of one layer for a 256-CU device, their ints in declaration order; nothing is launched or allocated
+SCDA_API void scda_debug_plan_wino(int batch, int C, int H, int W, int M, int stack, int pool, int masked, int with_db, size_t ws_bytes,
+                                   int *fwd9, int *wgrad6) {
+    static_assert(sizeof(lp::WinoDecision) == 9 * sizeof(int) && sizeof(lp::WinoWgradDecision) == 6 * sizeof(int), "scda_ops.h documents 9 + 6 ints");
+    const lp::WinoEnv env = lp::read_wino_env();
+    const lp::WinoDecision f = lp::decide_wino(batch, C, H, W, M, stack, pool != 0, masked != 0, ws_bytes, 256, env);
+    const lp::WinoWgradDecision w = lp::decide_wino_wgrad(batch, C, H, W, M, stack, with_db != 0, ws_bytes, env);
+    memcpy(fwd9, &f, sizeof f);
+    memcpy(wgrad6, &w, sizeof w);
+}
 
 // evidence aid (scripts/pmc_summary.py): SCDA_WINO_LOG=<file> appends one line per launch of the three kernels, in launch order --
 // kind, tile rows / 32, workgroups, shape, split count and the launch's ALGORITHMIC bytes (operands once + result once) -- so that
-// a counter pass's dispatches can be joined with the layers they ran
-static void wino_log(const char *kind, int mb, long long wgs, int batch, int C, int H, int W, int M, int splits, double bytes, double flops) {
-    static FILE *f = [] { const char *p = getenv("SCDA_WINO_LOG"); return p && *p ? fopen(p, "a") : (FILE *)nullptr; }();
+// a counter pass's dispatches can be joined with the layers they ran.  The file named at the first launch is the one kept.
+static void wino_log(const char *path, const char *kind, int mb, long long wgs, int batch, int C, int H, int W, int M, int splits, double bytes,
+                     double flops) {
+    static FILE *f = path && *path ? fopen(path, "a") : nullptr;
     if (!f) return;
     fprintf(f, "%s %d %lld %d %d %d %d %d %d %.0f %.0f\n", kind, mb, wgs, batch, C, H, W, M, splits, bytes, flops);
     fflush(f);
 }
 
-SCDA_API int scda_conv2d_wino_stacked_supported(int maps, int C, int M);
-
+// y [batch, M, H, W] = act(conv3x3(x [batch, C, H, W], stride 1, pad 1) + bias) (* act'(mask_src)); u = scda_conv2d_wino_pack_hip
 static int wino_launch(const float *x, const float *u, const float *bias, float *y, int batch, int C, int H, int W, int M, int act,
                        float slope, const float *mask_src, float mask_slope, int for_dgrad, void *ws, size_t ws_bytes, void *stream,
                        float *pool_y, unsigned char *pool_idx, int stack = 0) {
     if (!x || !u || (!y && !pool_y)) { set_error("scda_conv2d_wino_hip: bad arguments"); return SCDA_EINVAL; }
-    if (stack > 0 ? !(scda_conv2d_wino_stacked_supported(stack, C, M) && batch == 1 && H == stack * 7 && W == 7 && !pool_y)
-                  : !scda_conv2d_wino_supported(batch, C, H, W, M)) {
+    if (!lp::wino_kernel_ok(batch, C, H, W, M, stack) || (stack && pool_y)) {
         set_error("scda_conv2d_wino_hip: needs C %% 8 == 0, even H and W (or a stack of 7 x 7 maps) and tensors below 2 GB per image (C=%d H=%d W=%d)", C, H, W);
         return SCDA_EINVAL;
     }
     hipStream_t st = as_stream(stream);
+    static const int n_cu = [] { int d = 0, n = 0; if (hipGetDevice(&d) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d) != hipSuccess || n < 8) n = 256; return n / 8 * 8; }();
+    const lp::WinoEnv env = lp::read_wino_env();
+    const lp::WinoDecision d = lp::decide_wino(batch, C, H, W, M, stack, pool_y != nullptr, mask_src != nullptr, ws_bytes, n_cu, env);
+    g_wino_last.fwd = d;
+    const lp::WinoBlocks b = lp::wino_blocks(batch, H, W, stack);      // blocks on the right / bottom edge may be partial
     WinoGeom g;
     g.batch = batch; g.C = C; g.H = H; g.W = W; g.M = M; g.stack = stack;
-    // tile rows: 64 (every fragment feeds two MFMAs), or 32 for layers with <= 32 output rows (the decoders' 64 -> 32 stage: half of
-    // a 64-row tile would multiply padding).  Measured on every VGG / decoder layer (scripts/bench_wino.py, SCDA_WINO_MB=1|2): the
-    // two are within 3 % of each other everywhere else -- two co-resident 32-row workgroups start and finish together, so one's
-    // start-up and epilogue do NOT hide under the other's K loop.
-    static const int force_mb = getenv("SCDA_WINO_MB") ? atoi(getenv("SCDA_WINO_MB")) : 0;
-    // ... and for launches that would not fill the chip with 64-row tiles (the decoders' batch-4 residual convolutions: 128 tiles;
-    // conv5_x / the RPN: 64): twice the workgroups first, split-K (slabs + a reduce launch) only for what is still missing
-    // (a stack of 7 x 7 maps: one block column, a block row per four maps)
-    const int nbx = stack ? 1 : (W + 31) / 32, nby = stack ? (stack + 3) / 4 : (H + 7) / 8, npb = batch * nby * nbx;   // blocks on the right / bottom edge may be partial
-    const long long tiles64 = (long long)((M + 63) / 64) * npb;
-    const int MBv = force_mb == 1 || force_mb == 2 ? force_mb : ((M <= 32 || tiles64 < 200) ? 1 : 2);
     g.n_mbg = (M + 63) / 64 * 2;
-    g.n_mt = (M + 32 * MBv - 1) / (32 * MBv); g.n_slab = C / WBK;
-    g.dNMT = Div(g.n_mt); g.dNPB = Div(npb); g.dNB = Div(nby * nbx); g.dNBX = Div(nbx);
-    // XCD order: pixel-block-major when all m-tiles' filters can stream through one XCD's 4 MB L2 beside the patches (<= 4.5 MB: every
-    // layer below 512 output channels; conv3_2's 4.2 MB: 290 -> 109 MB read per launch), m-tile-major otherwise
-    // (SCDA_WINO_ORDER=m|p forces one: A/B, counter passes).  ALSO with a single m-tile (conv1_2, the decoders' up-sampling stages):
-    // dealt round-robin, row neighbours run on different XCDs and each fetches the two extra 128-byte lines its 136-byte patch rows
-    // straddle -- conv1_2 read 422 MB for a 134 MB input, 183 MB as contiguous runs (and the decoders' stages run 4 - 9 % faster).
-    static const char *order_env = getenv("SCDA_WINO_ORDER");
-    g.npb = npb; g.per_xcd = 0;
-    // (... and only for launches of >= 16 pixel blocks per XCD: the runs leave up to 7 idle workgroups per m-tile, and a small
-    // launch -- the decoders' 64 blocks -- lost 13 % to the imbalance)
-    const double u_bytes = 16.0 * g.n_mbg * 32 * C * 4, in_bytes = 4.0 * batch * C * H * W;
-    g.pixel_major = order_env ? (order_env[0] == 'p') : (npb >= 128 && u_bytes <= 4.5e6);
-    // filters beyond one L2: split the XCDs gm x (8 / gm) over m-tile groups x pixel-block runs where that moves fewer bytes than
-    // m-tile-major (filters x (8 / gm) + input x gm against filters + input x min(n_mt, 8)) and every XCD still streams <= 4.5 MB
-    // of filters (SCDA_WINO_GM=2|4 forces a split, 0 none)
-    int gm = 1;
-    if (!g.pixel_major && !order_env) {
-        const char *gm_env = getenv("SCDA_WINO_GM");      // (read per launch: tests/test_conv_wino_gpu.py forces every split)
-        const int gm_legacy = g.n_mt >= 8 ? 8 : g.n_mt;
-        // (fewer than 8 m-tiles: a block's row neighbours land on different XCDs and each fetches the straddled lines itself)
-        double best = u_bytes * (8.0 / gm_legacy) + in_bytes * gm_legacy * (g.n_mt >= 8 ? 1.0 : 2.0);
-        for (int c = 2; c <= 4; c *= 2) {
-            const long long items = (long long)npb;     // (the split count is not known yet: launches that split are small, see below)
-            if (g.n_mt % c != 0 || items % (8 / c) != 0 || items / (8 / c) < 8 || u_bytes / c > 4.5e6) continue;
-            const double cost = u_bytes * (8.0 / c) + in_bytes * c;
-            if (gm_env ? atoi(gm_env) == c : cost < best) { best = cost; gm = c; }
-        }
-        if (gm_env && atoi(gm_env) == 0) gm = 1;
-        if (gm > 1) g.pixel_major = 1;
-    }
-    g.gm_mask = gm - 1; g.gm_shift = gm == 4 ? 2 : gm == 2 ? 1 : 0;
-    g.dNML = Div(g.n_mt / gm);
-    // split-K: a launch below one workgroup per CU splits the channel loop (>= 4 slabs per split), slabs in the natural pixel order
-    const long long tiles = (long long)g.n_mt * npb;
-    int splits = 1;
-    if (const char *f = getenv("SCDA_WINO_SPLITS")) splits = atoi(f);
-    else if (tiles < 200) splits = (int)std::min<long long>((256 * (3 - MBv) + tiles / 2) / tiles, g.n_slab / 4 > 0 ? g.n_slab / 4 : 1);   // two 32-row workgroups per CU: conv5_x 65 -> 61 us   // (32-row tiles at one per CU: the decoders' 256-tile launches run 10 % faster unsplit, and without a reduce launch)
-    if (splits < 1) splits = 1;
-    while (splits > 1 && (size_t)splits * M * batch * H * W * sizeof(float) > ws_bytes) --splits;
-    if (pool_y) splits = 1;      // (the fused pool needs finished values in the epilogue; its callers are the 256+-tile VGG layers)
-    if ((size_t)M * batch * H * W * sizeof(float) >= ((size_t)1 << 31)) splits = 1;      // (a slab is addressed with 32-bit byte offsets)
-    g.slabs_per_split = (g.n_slab + splits - 1) / splits;
-    splits = (g.n_slab + g.slabs_per_split - 1) / g.slabs_per_split;
-    static const int dbg = getenv("SCDA_WINO_DBG") ? atoi(getenv("SCDA_WINO_DBG")) : 0;
-    WinoEpi e{y, (float *)ws, bias, act, slope, splits, mask_src, mask_slope, dbg, pool_y, pool_idx};
+    g.n_mt = (M + 32 * d.mb - 1) / (32 * d.mb); g.n_slab = C / WBK; g.slabs_per_split = d.slabs_per_split;
+    g.dNMT = Div(g.n_mt); g.dNPB = Div(b.npb); g.dNB = Div(b.nby * b.nbx); g.dNBX = Div(b.nbx);
+    g.pixel_major = d.pixel_major; g.npb = b.npb; g.per_xcd = d.per_xcd; g.n_wg = d.n_wg;
+    g.gm_mask = d.gm - 1; g.gm_shift = d.gm == 4 ? 2 : d.gm == 2 ? 1 : 0;
+    g.dNML = Div(g.n_mt / d.gm);
+    WinoEpi e{y, (float *)ws, bias, act, slope, d.splits, mask_src, mask_slope, env.dbg, pool_y, pool_idx};
     // flops = the MFMA work the kernel EXECUTES (16 products per 2x2 tile and channel pair: the direct form's 36 / 2.25)
     // algorithmic bytes: input once, filters once, result once (fused pool: the pooled map and its winners instead of the full map)
-    const double out_bytes = pool_y ? 1.25 * batch * M * H * W : 4.0 * batch * M * H * W;
+    const double out_bytes = pool_y ? 1.25 * batch * M * H * W : 4.0 * batch * M * H * W, flops = 2.0 * M * (double)batch * H * W * C * 4;
     const double alg_bytes = 4.0 * ((double)batch * C * H * W + 9.0 * M * C) + out_bytes + (mask_src ? 4.0 * batch * M * H * W : 0.0);   // (+ the activation mask)
-    prof_begin(for_dgrad ? PK_WINO_DGRAD : PK_WINO_FWD, 2.0 * M * (double)batch * H * W * C * 4, st, alg_bytes);
-    long long wgs = tiles * splits;
-    if (g.pixel_major) {      // 8 / gm runs of per_xcd (split, pixel block) items x n_mt m-tiles; the last run may hold idle workgroups
-        const int gp = 8 / gm;
-        g.per_xcd = (int)(((long long)npb * splits + gp - 1) / gp);
-        wgs = 8LL * g.per_xcd * (g.n_mt / gm);
-    }
-    g_wino_last[0] = MBv; g_wino_last[1] = g.pixel_major; g_wino_last[2] = gm; g_wino_last[3] = splits;
-    wino_log(pool_y ? "fwd_pool" : for_dgrad ? (mask_src ? "dgrad_mask" : "dgrad") : "fwd", MBv, wgs, batch, C, H, W, M, splits, alg_bytes, 2.0 * M * (double)batch * H * W * C * 4);
-    // more 64-row tiles than CUs: one persistent workgroup per CU walks them (see the kernel); SCDA_WINO_PERSIST=0 turns it off
-    static const int n_cu = [] { int d = 0, n = 0; if (hipGetDevice(&d) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d) != hipSuccess || n < 8) n = 256; return n / 8 * 8; }();
-    const char *pe = getenv("SCDA_WINO_PERSIST");
-    // (a split launch is never persistent: the automatic heuristic only splits launches below one workgroup per CU, but
-    //  SCDA_WINO_SPLITS / SCDA_WINO_MB can force both at once -- the split-slab epilogue exists in the one-tile form only)
-    const bool persist = MBv == 2 && splits == 1 && wgs > n_cu && g.slabs_per_split >= 2 && g.n_slab >= 2 && !(pe && pe[0] == '0') &&
-                         (size_t)M * batch * H * W * sizeof(float) < ((size_t)1 << 31);
-    g.n_wg = (int)wgs;
-    g_wino_last_persist = persist ? 1 : 0;
-    const int epi = splits > 1 ? WEPI_SPLIT : pool_y ? WEPI_POOL : mask_src ? WEPI_MASK : WEPI_PLAIN;
-#define WINO_LAUNCH(MB_, P_, E_) hipLaunchKernelGGL((conv_wino_kernel<MB_, P_, E_>), dim3((unsigned)((P_) ? n_cu : wgs)), dim3(512), 0, st, u, x, g, e)
+    prof_begin(for_dgrad ? PK_WINO_DGRAD : PK_WINO_FWD, flops, st, alg_bytes);
+    wino_log(env.log, pool_y ? "fwd_pool" : for_dgrad ? (mask_src ? "dgrad_mask" : "dgrad") : "fwd", d.mb, d.n_wg, batch, C, H, W, M, d.splits, alg_bytes, flops);
+#define WINO_LAUNCH(MB_, P_, E_) hipLaunchKernelGGL((conv_wino_kernel<MB_, P_, E_>), dim3((unsigned)((P_) ? n_cu : d.n_wg)), dim3(512), 0, st, u, x, g, e)
 #define WINO_LAUNCH_EPI(MB_, P_)                                                      \
     do {                                                                              \
-        if (epi == WEPI_SPLIT) {                                                      \
+        if (d.epi == WEPI_SPLIT) {                                                    \
             if (P_) { prof_end(st); set_error("conv_wino_kernel: a split launch cannot be persistent"); return SCDA_EINVAL; } \
             WINO_LAUNCH(MB_, false, WEPI_SPLIT);                                      \
         }                                                                             \
-        else if (epi == WEPI_POOL) WINO_LAUNCH(MB_, P_, WEPI_POOL);                   \
-        else if (epi == WEPI_MASK) WINO_LAUNCH(MB_, P_, WEPI_MASK);                   \
+        else if (d.epi == WEPI_POOL) WINO_LAUNCH(MB_, P_, WEPI_POOL);                 \
+        else if (d.epi == WEPI_MASK) WINO_LAUNCH(MB_, P_, WEPI_MASK);                 \
         else WINO_LAUNCH(MB_, P_, WEPI_PLAIN);                                        \
     } while (0)
-    if (persist) WINO_LAUNCH_EPI(2, true);       // (a persistent launch never splits: it has more tiles than CUs)
-    else if (MBv == 2) WINO_LAUNCH_EPI(2, false);
+    if (d.persist) WINO_LAUNCH_EPI(2, true);       // (a persistent launch never splits: it has more tiles than CUs)
+    else if (d.mb == 2) WINO_LAUNCH_EPI(2, false);
     else WINO_LAUNCH_EPI(1, false);
 #undef WINO_LAUNCH_EPI
 #undef WINO_LAUNCH
     prof_end(st);
     int rc = launch_status("conv_wino_kernel");
-    if (rc || splits == 1) return rc;
-    return launch_conv_reduce((const float *)ws, splits, M, batch * H * W, H * W, bias, act, slope, y, mask_src, mask_slope, st);
+    if (rc || d.splits == 1) return rc;
+    return launch_conv_reduce((const float *)ws, d.splits, M, batch * H * W, H * W, bias, act, slope, y, mask_src, mask_slope, st);
 }
 
-SCDA_API int scda_conv2d_wino_stacked_supported(int maps, int C, int M) {
-    return maps > 0 && M > 0 && C >= WBK && (C % WBK) == 0 && (long long)C * maps * 49 * 4 < (1LL << 31) && (long long)M * maps * 49 * 4 < (1LL << 31);
+SCDA_API int scda_conv2d_wino_hip(const float *x, const float *u, const float *bias, float *y, int batch, int C, int H, int W, int M,
+                                  int act, float slope, const float *mask_src, float mask_slope, int for_dgrad, void *ws, size_t ws_bytes,
+                                  void *stream) {
+    return wino_launch(x, u, bias, y, batch, C, H, W, M, act, slope, mask_src, mask_slope, for_dgrad, ws, ws_bytes, stream, nullptr, nullptr);
 }
 
 // the same on x [1, C, maps * 7, 7] read as a vertical stack of `maps` independent 7 x 7 maps (row period 7: no tap reaches from one
@@ -1141,62 +1112,50 @@ SCDA_API int scda_conv2d_wino_stacked_hip(const float *x, const float *u, const 
     return wino_launch(x, u, bias, y, 1, C, maps * 7, 7, M, act, slope, mask_src, mask_slope, for_dgrad, ws, ws_bytes, stream, nullptr, nullptr, maps);
 }
 
-SCDA_API int scda_conv2d_wino_wgrad_supported(int batch, int Cin, int H, int W, int Cout) {
-    return batch > 0 && Cin >= 32 && Cout >= 32 && (H % 2) == 0 && (W % 2) == 0 && 64LL * H * W * 4 < (1LL << 31);
-}
-
-SCDA_API int scda_conv2d_wino_wgrad_stacked_supported(int maps, int Cin, int Cout) {
-    return maps > 0 && Cin >= 64 && Cout >= 64 && 64LL * maps * 49 * 4 < (1LL << 31);
+// conv3x3 + bias + activation + 2x2/2 max-pool in one launch: pool_y [batch, M, H/2, W/2] and pool_idx (uint8, winner 0..3 as
+// scda_maxpool2x2_fwd_hip writes it) -- the full-resolution map is never written (vgg_adver_expansion_cluster.py:101-114: the pools
+// behind conv1_2 / conv2_2 / conv3_3 / conv4_3).  A Winograd tile IS a pooling window.
+SCDA_API int scda_conv2d_wino_pool_hip(const float *x, const float *u, const float *bias, float *pool_y, unsigned char *pool_idx, int batch,
+                                       int C, int H, int W, int M, int act, float slope, void *stream) {
+    if (!pool_y || !pool_idx) { set_error("scda_conv2d_wino_pool_hip: bad arguments"); return SCDA_EINVAL; }
+    return wino_launch(x, u, bias, nullptr, batch, C, H, W, M, act, slope, nullptr, 0.f, 0, nullptr, 0, stream, pool_y, pool_idx);
 }
 
 static int wino_wgrad_launch(const float *dy, const float *x, float *dw, float *db, int batch, int Cin, int H, int W, int Cout,
                              int accumulate, int db_accumulate, void *ws, size_t ws_bytes, void *stream, int stack) {
     if (!dy || !x || !dw || !ws) { set_error("scda_conv2d_wino_wgrad_hip: bad arguments"); return SCDA_EINVAL; }
-    if (stack > 0 ? !(scda_conv2d_wino_wgrad_stacked_supported(stack, Cin, Cout) && batch == 1 && H == stack * 7 && W == 7)
-                  : !scda_conv2d_wino_wgrad_supported(batch, Cin, H, W, Cout)) {
+    if (!lp::wino_wgrad_kernel_ok(batch, Cin, H, W, Cout, stack)) {
         set_error("scda_conv2d_wino_wgrad_hip: needs >= 32 channels on both sides (>= 64 on stacked maps) and even H, W or a stack of 7 x 7 maps (Cin=%d Cout=%d H=%d W=%d)", Cin, Cout, H, W);
         return SCDA_EINVAL;
     }
+    if (ws_bytes < ((size_t)Cin * 9 + (db ? 1024 : 0)) * Cout * sizeof(float)) { set_error("scda_conv2d_wino_wgrad_hip: workspace too small"); return SCDA_EINVAL; }
     hipStream_t st = as_stream(stream);
+    const lp::WinoEnv env = lp::read_wino_env();
+    const lp::WinoWgradDecision d = lp::decide_wino_wgrad(batch, Cin, H, W, Cout, stack, db != nullptr, ws_bytes, env);
+    g_wino_last.wgrad = d;
+    const int n_mt = (Cout + 63) / 64;
     WinoWgradGeom g;
     g.batch = batch; g.C = Cin; g.H = H; g.W = W; g.M = Cout; g.stack = stack;
-    const int n_mt = (Cout + 63) / 64;
     g.n_ct = (Cin + 63) / 64; g.TY = stack ? 4 : H / 2; g.TX = stack ? 1 : (W + 15) / 16;
-    g.n_slab = stack ? (stack + 1) / 2 * 4 : batch * g.TY * g.TX;
+    g.n_slab = d.n_slab; g.slabs_per_split = d.slabs_per_split;
     g.dNMT = Div(n_mt); g.dNCT = Div(g.n_ct); g.dTX = Div(g.TX); g.dTY = Div(g.TY);
-    const long long tiles = (long long)n_mt * g.n_ct;
-    const size_t slab_bytes = (size_t)Cout * Cin * 9 * sizeof(float), db_bytes = db ? (size_t)1024 * Cout * sizeof(float) : 0;
-    if (ws_bytes < slab_bytes + db_bytes) { set_error("scda_conv2d_wino_wgrad_hip: workspace too small"); return SCDA_EINVAL; }
-    // one workgroup per CU and round: splits so that the launch has ~256 workgroups (>= 8 slabs each, <= 1024 splits)
-    int splits = (int)((256 + tiles - 1) / tiles);
-    if (const char *f = getenv("SCDA_WINO_WGRAD_SPLITS")) splits = atoi(f);
-    splits = std::max(1, std::min(std::min(splits, 1024), std::max(1, g.n_slab / 8)));
-    if (splits >= 8) splits = (splits + 7) / 8 * 8;      // whole runs per XCD (the last XCD's run would otherwise hold idle workgroups)
-    splits = std::min(splits, std::max(1, g.n_slab / 4));
-    while (splits > 1 && (size_t)splits * slab_bytes + db_bytes > ws_bytes) --splits;
-    g.slabs_per_split = (g.n_slab + splits - 1) / splits;
-    splits = (g.n_slab + g.slabs_per_split - 1) / g.slabs_per_split;
-    float *wsf = (float *)ws;
-    float *db_ws = db ? wsf + (size_t)splits * Cout * Cin * 9 : nullptr;
-    prof_begin(PK_WINO_WGRAD, 2.0 * Cout * (double)batch * H * W * Cin * 4, st);
-    g.splits = splits; g.splits_per_xcd = (splits % 8) == 0 ? splits / 8 : 0;
+    g.splits = d.splits; g.splits_per_xcd = d.splits_per_xcd;
     g.sp_mask = 0; g.sp_shift = -1; g.dNML = Div(1);
-    const bool no_groups = getenv("SCDA_WINO_WGRAD_NO_GROUPS") != nullptr;    // A/B knob (read per launch: the tests compare both orders)
-    if (!no_groups && (splits == 2 || splits == 4) && n_mt % (8 / splits) == 0) {
-        g.sp_mask = splits - 1; g.sp_shift = splits == 4 ? 2 : 1;
-        g.dNML = Div(n_mt / (8 / splits));
+    if (d.order == 2) {
+        g.sp_mask = d.splits - 1; g.sp_shift = d.splits == 4 ? 2 : 1;
+        g.dNML = Div(n_mt / (8 / d.splits));
     }
-    g_wino_wgrad_last[0] = splits; g_wino_wgrad_last[1] = g.splits_per_xcd > 0 ? 1 : g.sp_shift >= 0 ? 2 : 0;
-    wino_log("wgrad", 2, tiles * splits, batch, Cin, H, W, Cout, splits, 4.0 * ((double)batch * (Cin + Cout) * H * W + 9.0 * Cout * Cin),
-             2.0 * Cout * (double)batch * H * W * Cin * 4);
-    hipLaunchKernelGGL(conv_wino_wgrad_kernel, dim3((unsigned)(tiles * splits)), dim3(512), 0, st, dy, x, g, wsf, db_ws);
+    float *wsf = (float *)ws;
+    float *db_ws = db ? wsf + (size_t)d.splits * Cout * Cin * 9 : nullptr;
+    const double flops = 2.0 * Cout * (double)batch * H * W * Cin * 4;
+    prof_begin(PK_WINO_WGRAD, flops, st);
+    wino_log(env.log, "wgrad", 2, d.grid, batch, Cin, H, W, Cout, d.splits, 4.0 * ((double)batch * (Cin + Cout) * H * W + 9.0 * Cout * Cin), flops);
+    hipLaunchKernelGGL(conv_wino_wgrad_kernel, dim3((unsigned)d.grid), dim3(512), 0, st, dy, x, g, wsf, db_ws);
     prof_end(st);
     int rc = launch_status("conv_wino_wgrad_kernel");
     if (rc) return rc;
-    return launch_wgrad_reduce(wsf, splits, (long long)Cout * Cin * 9, Cin * 9, accumulate, dw, db_ws, db, Cout, db_accumulate, st);
+    return launch_wgrad_reduce(wsf, d.splits, (long long)Cout * Cin * 9, Cin * 9, accumulate, dw, db_ws, db, Cout, db_accumulate, st);
 }
-
-SCDA_API int scda_debug_wino_last_persistent(void) { return g_wino_last_persist; }
 
 // dw [Cout,Cin,3,3] (+)= weight gradient of the stride-1, pad-1 3x3 convolution; db [Cout] (+)= bias gradient (may be NULL)
 SCDA_API int scda_conv2d_wino_wgrad_hip(const float *dy, const float *x, float *dw, float *db, int batch, int Cin, int H, int W, int Cout,
@@ -1208,24 +1167,4 @@ SCDA_API int scda_conv2d_wino_wgrad_hip(const float *dy, const float *x, float *
 SCDA_API int scda_conv2d_wino_wgrad_stacked_hip(const float *dy, const float *x, float *dw, float *db, int maps, int Cin, int Cout,
                                                 int accumulate, int db_accumulate, void *ws, size_t ws_bytes, void *stream) {
     return wino_wgrad_launch(dy, x, dw, db, 1, Cin, maps * 7, 7, Cout, accumulate, db_accumulate, ws, ws_bytes, stream, maps);
-}
-
-SCDA_API void scda_debug_wino_last_order(int *out6) {
-    for (int i = 0; i < 4; ++i) out6[i] = g_wino_last[i];
-    out6[4] = g_wino_wgrad_last[0]; out6[5] = g_wino_wgrad_last[1];
-}
-
-SCDA_API int scda_conv2d_wino_hip(const float *x, const float *u, const float *bias, float *y, int batch, int C, int H, int W, int M,
-                                  int act, float slope, const float *mask_src, float mask_slope, int for_dgrad, void *ws, size_t ws_bytes,
-                                  void *stream) {
-    return wino_launch(x, u, bias, y, batch, C, H, W, M, act, slope, mask_src, mask_slope, for_dgrad, ws, ws_bytes, stream, nullptr, nullptr);
-}
-
-// conv3x3 + bias + activation + 2x2/2 max-pool in one launch: pool_y [batch, M, H/2, W/2] and pool_idx (uint8, winner 0..3 as
-// scda_maxpool2x2_fwd_hip writes it) -- the full-resolution map is never written (vgg_adver_expansion_cluster.py:101-114: the pools
-// behind conv1_2 / conv2_2 / conv3_3 / conv4_3).  A Winograd tile IS a pooling window.
-SCDA_API int scda_conv2d_wino_pool_hip(const float *x, const float *u, const float *bias, float *pool_y, unsigned char *pool_idx, int batch,
-                                       int C, int H, int W, int M, int act, float slope, void *stream) {
-    if (!pool_y || !pool_idx) { set_error("scda_conv2d_wino_pool_hip: bad arguments"); return SCDA_EINVAL; }
-    return wino_launch(x, u, bias, nullptr, batch, C, H, W, M, act, slope, nullptr, 0.f, 0, nullptr, 0, stream, pool_y, pool_idx);
 }

@@ -1,7 +1,9 @@
 // launch_plan.h -- which kernel family, tile, split-K count, tile order and grid every convolution, weight gradient and dense
-// GEMM runs with.  Host arithmetic only (plain C++17, no HIP): conv_gemm.hip asks one decide_* function per launch and launches
-// what the LaunchDecision names; scda_debug_plan_conv / scda_debug_plan_gemm return the same struct without a GPU
-// (tests/test_launch_plans.py pins it against tests/golden/launch_plans.json).
+// GEMM runs with; which convolutions take the Winograd kernels instead (route_conv) and how those launch (decide_wino,
+// decide_wino_wgrad).  Host arithmetic only (plain C++17, no HIP): conv_gemm.hip and conv_wino.hip ask one decide_* function per
+// launch and launch what the decision names; scda_debug_plan_conv / scda_debug_plan_gemm / scda_debug_plan_wino return the same
+// structs and scda_conv2d_route the route without a GPU (tests/test_launch_plans.py pins them against tests/golden/launch_plans.json
+// and wino_plans.json).  Every environment variable of these paths is read here, in read_plan_env / read_wino_env.
 #ifndef SCDA_LAUNCH_PLAN_H
 #define SCDA_LAUNCH_PLAN_H
 
@@ -392,6 +394,210 @@ static LaunchDecision decide_wgrad(const ConvShape &c, bool dy_aligned, bool ali
     // for 128-row tiles
     d.wbk = small ? 32 : 16;
     d.reduce = 1;
+    return d;
+}
+
+// ----------------------------- Winograd F(2x2, 3x3): environment, each variable read in ONE place --------------------------
+// The first eight are the reference paths of the tests (tests/test_conv_wino_gpu.py and the model tests switch them between launches),
+// the last two evidence aids.
+struct WinoEnv {
+    bool enabled;            // SCDA_WINOGRAD=0: every layer on the implicit-GEMM kernels
+    bool stacked;            // SCDA_WINO_STACKED=0: ... the stacks of 7 x 7 maps
+    bool pool_fuse;          // SCDA_CONV_POOL_FUSE=0: the 2x2 max-pool behind a convolution stays a launch of its own
+    bool gm_set; int gm;     // SCDA_WINO_GM=2|4: that split of the XCDs over m-tile groups x pixel-block runs where legal, 0 none
+    bool splits_set; int splits;               // SCDA_WINO_SPLITS: split-K count of the forward / data gradient
+    bool persist;            // SCDA_WINO_PERSIST=0: one workgroup per tile also where there are more tiles than CUs
+    bool wgrad_splits_set; int wgrad_splits;   // SCDA_WINO_WGRAD_SPLITS: K-split count of the weight gradient
+    bool wgrad_no_groups;    // SCDA_WINO_WGRAD_NO_GROUPS: 2 or 4 splits dealt over the XCDs as they come
+    int dbg;                 // SCDA_WINO_DBG: handed to conv_wino_kernel (WinoEpi::dbg: 1 no epilogue, 2 no K loop)
+    const char *log;         // SCDA_WINO_LOG=<file>: one line per launch (conv_wino.hip wino_log opens and writes it)
+};
+
+// (read per call, as read_plan_env)
+static WinoEnv read_wino_env() {
+    const auto off = [](const char *name) { const char *v = getenv(name); return v && strcmp(v, "0") == 0; };
+    const auto num = [](const char *name, bool *set) { const char *v = getenv(name); *set = v != nullptr; return v ? atoi(v) : 0; };
+    WinoEnv e{};
+    e.enabled = !off("SCDA_WINOGRAD");
+    e.stacked = !off("SCDA_WINO_STACKED");
+    e.pool_fuse = !off("SCDA_CONV_POOL_FUSE");
+    e.gm = num("SCDA_WINO_GM", &e.gm_set);
+    e.splits = num("SCDA_WINO_SPLITS", &e.splits_set);
+    const char *pe = getenv("SCDA_WINO_PERSIST");
+    e.persist = !(pe && pe[0] == '0');
+    e.wgrad_splits = num("SCDA_WINO_WGRAD_SPLITS", &e.wgrad_splits_set);
+    e.wgrad_no_groups = getenv("SCDA_WINO_WGRAD_NO_GROUPS") != nullptr;
+    bool dbg_set;
+    e.dbg = num("SCDA_WINO_DBG", &dbg_set);
+    e.log = getenv("SCDA_WINO_LOG");
+    return e;
+}
+
+// ----------------------------- Winograd: which convolutions take it --------------------------
+constexpr int WINO_SLAB = 8;          // channels per K-slab of conv_wino_kernel (wino_pack.h)
+constexpr int WINO_MIN_C = 32;        // fewer channels on either side: the implicit-GEMM kernels (the weight-gradient kernel's own floor)
+constexpr int WINO_FILL_TILES = 200;  // 64-row tiles from which a launch fills the chip: below, 32-row tiles and split-K; from it, the fused pool
+
+static bool below_2g(long long elems) { return elems * 4 < (1LL << 31); }   // (buffer descriptors with 32-bit byte offsets)
+
+// pixel blocks of 8 x 32 output pixels, partial on the right / bottom edge (a stack of 7 x 7 maps: one block column, a block row
+// per four maps)
+struct WinoBlocks { int nbx, nby, npb; };
+static WinoBlocks wino_blocks(int batch, int H, int W, int stack) {
+    const int nbx = stack ? 1 : (W + 31) / 32, nby = stack ? (stack + 3) / 4 : (H + 7) / 8;
+    return WinoBlocks{nbx, nby, batch * nby * nbx};
+}
+static long long wino_tiles64(int M, const WinoBlocks &b) { return (long long)((M + 63) / 64) * b.npb; }
+
+// what conv_wino_kernel runs: y [batch, M, H, W] from x [batch, C, H, W]; stack > 0: [1, C, stack * 7, 7] as that many 7 x 7 maps
+static bool wino_kernel_ok(int batch, int C, int H, int W, int M, int stack) {
+    return batch > 0 && M > 0 && stack >= 0 && C >= WINO_SLAB && (C % WINO_SLAB) == 0 &&
+           (stack ? batch == 1 && H == stack * 7 && W == 7 : (H % 2) == 0 && (W % 2) == 0) && below_2g((long long)C * H * W) &&
+           below_2g((long long)M * H * W);
+}
+// ... and conv_wino_wgrad_kernel (64-channel tiles on both sides; stacked maps need whole ones)
+static bool wino_wgrad_kernel_ok(int batch, int Cin, int H, int W, int Cout, int stack) {
+    const int min_c = stack ? 64 : WINO_MIN_C;
+    return batch > 0 && stack >= 0 && Cin >= min_c && Cout >= min_c && (stack ? batch == 1 && H == stack * 7 && W == 7 : (H % 2) == 0 && (W % 2) == 0) &&
+           below_2g(64LL * H * W);
+}
+
+enum Direction { DIR_FWD = 0, DIR_DGRAD = 1, DIR_WGRAD = 2 };
+enum RouteFamily { ROUTE_GEMM = 0, ROUTE_WINO = 1, ROUTE_WINO_STACKED = 2 };
+struct ConvRoute {
+    int family;
+    int maps;       // the image is a stack of this many 7 x 7 maps (row period 7: the ResNet-50 C4 detector's channel-major RoI head), else 0
+    bool pool;      // forward: conv + activation + 2x2 max-pool may run as ONE Winograd launch (the fused epilogue needs finished values:
+                    // a launch that fills the chip without split-K)
+};
+
+// c as the entry points receive it (Cin / Cout of the FORWARD convolution, IH x IW its input): stride-1 pad-1 3x3 layers the kernels
+// can run, from WINO_MIN_C channels a side
+static ConvRoute route_conv(int dir, const ConvShape &c, const WinoEnv &env) {
+    ConvRoute r{ROUTE_GEMM, 0, false};
+    if (c.row_period == 7 && c.IW == 7 && c.batch == 1 && c.IH % 7 == 0 && env.stacked) r.maps = c.IH / 7;
+    if (!(env.enabled && c.KH == 3 && c.KW == 3 && c.S == 1 && c.P == 1) || (c.row_period && !r.maps)) return r;
+    const int C = dir == DIR_DGRAD ? c.Cout : c.Cin, M = dir == DIR_DGRAD ? c.Cin : c.Cout;   // the data gradient reduces over Cout
+    if (dir == DIR_WGRAD ? !wino_wgrad_kernel_ok(c.batch, c.Cin, c.IH, c.IW, c.Cout, r.maps)
+                         : !(std::min(C, M) >= WINO_MIN_C && wino_kernel_ok(c.batch, C, c.IH, c.IW, M, r.maps)))
+        return r;
+    r.family = r.maps ? ROUTE_WINO_STACKED : ROUTE_WINO;
+    r.pool = dir == DIR_FWD && !r.maps && env.pool_fuse && wino_tiles64(M, wino_blocks(c.batch, c.IH, c.IW, 0)) >= WINO_FILL_TILES;
+    return r;
+}
+
+// ----------------------------- Winograd forward / data gradient --------------------------
+enum WinoEpilogue { WINO_EPI_PLAIN = 0, WINO_EPI_MASK = 1, WINO_EPI_POOL = 2, WINO_EPI_SPLIT = 3 };   // conv_wino_kernel's EPI
+
+struct WinoDecision {
+    int mb;               // tile rows / 32
+    int pixel_major;      // XCD order: contiguous pixel-block runs per XCD (else m-tile-major)
+    int gm;               // the 8 XCDs split gm x (8 / gm) over m-tile groups x pixel-block runs (1: no split)
+    int splits, slabs_per_split;
+    int per_xcd;          // pixel_major: (split, pixel block) items per XCD
+    int n_wg;             // workgroup slots of the launch: the grid of the one-tile-per-workgroup form
+    int persist;          // one workgroup per CU walks the tiles (grid = n_cu)
+    int epi;
+};
+
+// y [batch, M, H, W]; pool: the fused 2x2 max-pool, masked: the producer's activation mask (data gradient)
+static WinoDecision decide_wino(int batch, int C, int H, int W, int M, int stack, bool pool, bool masked, size_t ws_bytes, int n_cu,
+                                const WinoEnv &env) {
+    WinoDecision d{};
+    // tile rows: 64 (every fragment feeds two MFMAs), or 32 for layers with <= 32 output rows (the decoders' 64 -> 32 stage: half of
+    // a 64-row tile would multiply padding).  Measured on every VGG / decoder layer (scripts/bench_wino.py): the two are within 3 % of
+    // each other everywhere else -- two co-resident 32-row workgroups start and finish together, so one's start-up and epilogue do
+    // NOT hide under the other's K loop.
+    // ... and for launches that would not fill the chip with 64-row tiles (the decoders' batch-4 residual convolutions: 128 tiles;
+    // conv5_x / the RPN: 64): twice the workgroups first, split-K (slabs + a reduce launch) only for what is still missing
+    const WinoBlocks blocks = wino_blocks(batch, H, W, stack);
+    const int npb = blocks.npb;
+    d.mb = (M <= 32 || wino_tiles64(M, blocks) < WINO_FILL_TILES) ? 1 : 2;
+    const int n_mbg = (M + 63) / 64 * 2, n_mt = (M + 32 * d.mb - 1) / (32 * d.mb), n_slab = C / WINO_SLAB;
+    // XCD order: pixel-block-major when all m-tiles' filters can stream through one XCD's 4 MB L2 beside the patches (<= 4.5 MB: every
+    // layer below 512 output channels; conv3_2's 4.2 MB: 290 -> 109 MB read per launch), m-tile-major otherwise.  ALSO with a single
+    // m-tile (conv1_2, the decoders' up-sampling stages): dealt round-robin, row neighbours run on different XCDs and each fetches the
+    // two extra 128-byte lines its 136-byte patch rows straddle -- conv1_2 read 422 MB for a 134 MB input, 183 MB as contiguous runs
+    // (and the decoders' stages run 4 - 9 % faster).
+    // (... and only for launches of >= 16 pixel blocks per XCD: the runs leave up to 7 idle workgroups per m-tile, and a small
+    // launch -- the decoders' 64 blocks -- lost 13 % to the imbalance)
+    const double u_bytes = 16.0 * n_mbg * 32 * C * 4, in_bytes = 4.0 * batch * C * H * W;
+    d.pixel_major = npb >= 128 && u_bytes <= 4.5e6;
+    // filters beyond one L2: split the XCDs gm x (8 / gm) over m-tile groups x pixel-block runs where that moves fewer bytes than
+    // m-tile-major (filters x (8 / gm) + input x gm against filters + input x min(n_mt, 8)) and every XCD still streams <= 4.5 MB
+    // of filters
+    d.gm = 1;
+    if (!d.pixel_major) {
+        const int gm_legacy = n_mt >= 8 ? 8 : n_mt;
+        // (fewer than 8 m-tiles: a block's row neighbours land on different XCDs and each fetches the straddled lines itself)
+        double best = u_bytes * (8.0 / gm_legacy) + in_bytes * gm_legacy * (n_mt >= 8 ? 1.0 : 2.0);
+        for (int c = 2; c <= 4; c *= 2) {
+            const long long items = (long long)npb;     // (the split count is not known yet: launches that split are small, see below)
+            if (n_mt % c != 0 || items % (8 / c) != 0 || items / (8 / c) < 8 || u_bytes / c > 4.5e6) continue;
+            const double cost = u_bytes * (8.0 / c) + in_bytes * c;
+            if (env.gm_set ? env.gm == c : cost < best) { best = cost; d.gm = c; }
+        }
+        if (env.gm_set && env.gm == 0) d.gm = 1;
+        if (d.gm > 1) d.pixel_major = 1;
+    }
+    // split-K: a launch below one workgroup per CU splits the channel loop (>= 4 slabs per split), slabs in the natural pixel order
+    // (two 32-row workgroups per CU: conv5_x 65 -> 61 us; 32-row tiles at one per CU: the decoders' 256-tile launches run 10 % faster
+    // unsplit, and without a reduce launch)
+    const long long tiles = (long long)n_mt * npb;
+    const size_t out_bytes = (size_t)M * batch * H * W * sizeof(float);
+    int splits = 1;
+    if (env.splits_set) splits = env.splits;
+    else if (tiles < WINO_FILL_TILES) splits = (int)std::min<long long>((256 * (3 - d.mb) + tiles / 2) / tiles, n_slab / 4 > 0 ? n_slab / 4 : 1);
+    if (splits < 1) splits = 1;
+    while (splits > 1 && (size_t)splits * out_bytes > ws_bytes) --splits;
+    if (pool) splits = 1;      // (the fused pool needs finished values in the epilogue; its callers are the 256+-tile VGG layers)
+    if (out_bytes >= ((size_t)1 << 31)) splits = 1;      // (a slab is addressed with 32-bit byte offsets)
+    d.slabs_per_split = (n_slab + splits - 1) / splits;
+    d.splits = (n_slab + d.slabs_per_split - 1) / d.slabs_per_split;
+    long long wgs = tiles * d.splits;
+    if (d.pixel_major) {      // 8 / gm runs of per_xcd (split, pixel block) items x n_mt m-tiles; the last run may hold idle workgroups
+        const int gp = 8 / d.gm;
+        d.per_xcd = (int)(((long long)npb * d.splits + gp - 1) / gp);
+        wgs = 8LL * d.per_xcd * (n_mt / d.gm);
+    }
+    d.n_wg = (int)wgs;
+    // more 64-row tiles than CUs: one persistent workgroup per CU walks them (see the kernel)
+    // (a split launch is never persistent: the automatic heuristic only splits launches below one workgroup per CU, but
+    //  SCDA_WINO_SPLITS can force one where there are more -- the split-slab epilogue exists in the one-tile form only)
+    d.persist = d.mb == 2 && d.splits == 1 && wgs > n_cu && d.slabs_per_split >= 2 && n_slab >= 2 && env.persist && out_bytes < ((size_t)1 << 31);
+    d.epi = d.splits > 1 ? WINO_EPI_SPLIT : pool ? WINO_EPI_POOL : masked ? WINO_EPI_MASK : WINO_EPI_PLAIN;
+    return d;
+}
+
+// ----------------------------- Winograd weight gradient --------------------------
+struct WinoWgradDecision {
+    int n_slab;           // K-slabs of the launch: 2 x 16 pixels each (stacked maps: one tile row of a pair of maps)
+    int splits, slabs_per_split;
+    int splits_per_xcd;   // splits % 8 == 0: whole runs of splits per XCD (else 0)
+    int order;            // 0 workgroups dealt over the XCDs as they come, 1 whole splits per XCD, 2 one split + one m-tile group per XCD
+    int grid;
+};
+
+// dw [Cout, Cin, 3, 3]; with_db: 1024 rows of bias-gradient partials share the workspace
+static WinoWgradDecision decide_wino_wgrad(int batch, int Cin, int H, int W, int Cout, int stack, bool with_db, size_t ws_bytes,
+                                           const WinoEnv &env) {
+    WinoWgradDecision d{};
+    const int n_mt = (Cout + 63) / 64, n_ct = (Cin + 63) / 64;
+    d.n_slab = stack ? (stack + 1) / 2 * 4 : batch * (H / 2) * ((W + 15) / 16);
+    const long long tiles = (long long)n_mt * n_ct;
+    const size_t slab_bytes = (size_t)Cout * Cin * 9 * sizeof(float), db_bytes = with_db ? (size_t)1024 * Cout * sizeof(float) : 0;
+    // one workgroup per CU and round: splits so that the launch has ~256 workgroups (>= 8 slabs each, <= 1024 splits)
+    int splits = env.wgrad_splits_set ? env.wgrad_splits : (int)((256 + tiles - 1) / tiles);
+    splits = std::max(1, std::min(std::min(splits, 1024), std::max(1, d.n_slab / 8)));
+    if (splits >= 8) splits = (splits + 7) / 8 * 8;      // whole runs per XCD (the last XCD's run would otherwise hold idle workgroups)
+    splits = std::min(splits, std::max(1, d.n_slab / 4));
+    while (splits > 1 && (size_t)splits * slab_bytes + db_bytes > ws_bytes) --splits;
+    d.slabs_per_split = (d.n_slab + splits - 1) / splits;
+    d.splits = (d.n_slab + d.slabs_per_split - 1) / d.slabs_per_split;
+    d.splits_per_xcd = (d.splits % 8) == 0 ? d.splits / 8 : 0;
+    const bool groups = !env.wgrad_no_groups && (d.splits == 2 || d.splits == 4) && n_mt % (8 / d.splits) == 0;
+    d.order = d.splits_per_xcd > 0 ? 1 : groups ? 2 : 0;
+    d.grid = (int)(tiles * d.splits);
     return d;
 }
 

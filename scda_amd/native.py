@@ -593,42 +593,31 @@ def conv2d_pack_weight(w, for_dgrad=False, cache=True):
 
 
 def wino_enabled():
-    """the stride-1 3x3 layers the Winograd kernel supports run on it, forward and data gradient (SCDA_WINOGRAD=0: every layer on
-    the direct implicit-GEMM kernels)"""
-    return os.environ.get("SCDA_WINOGRAD", "1") != "0"
+    """the stride-1 3x3 layers the Winograd kernels support run on them (SCDA_WINOGRAD=0: every layer on the direct implicit-GEMM kernels)"""
+    return bool(lib().scda_conv2d_wino_enabled())
 
 
-def wino_min_channels():
-    return int(os.environ.get("SCDA_WINOGRAD_MIN_C", "32"))
+def _route(direction, B, Cin, IH, IW, Cout, KH, KW, stride, pad, row_period):
+    """csrc/launch_plan.h route_conv: (family 0 implicit GEMM / 1 Winograd / 2 Winograd on stacked 7 x 7 maps, conv + pool fusable, maps)"""
+    pool, maps = ctypes.c_int(0), ctypes.c_int(0)
+    fam = lib().scda_conv2d_route(i32(direction), i32(B), i32(Cin), i32(IH), i32(IW), i32(Cout), i32(KH), i32(KW), i32(stride), i32(pad),
+                                  i32(row_period), ctypes.byref(pool), ctypes.byref(maps))
+    return fam, bool(pool.value), maps.value
 
 
 def wino_stacked(B, IH, IW, row_period):
     """the image is a stack of 7 x 7 maps (the ResNet-50 C4 detector's channel-major RoI head): -> number of maps, else 0"""
-    if row_period == 7 and IW == 7 and B == 1 and IH % 7 == 0 and os.environ.get("SCDA_WINO_STACKED", "1") != "0":
-        return IH // 7
-    return 0
+    return _route(0, B, 0, IH, IW, 0, 3, 3, 1, 1, row_period)[2]
 
 
 def wino_ok(B, Cin, IH, IW, Cout, KH, KW, stride, pad, row_period=0):
-    """this convolution (forward: reduced channels Cin, output rows Cout; both at least wino_min_channels()) takes the Winograd path"""
-    if not (wino_enabled() and KH == 3 and KW == 3 and stride == 1 and pad == 1):
-        return False
-    if min(Cin, Cout) < wino_min_channels():
-        return False
-    if row_period:
-        maps = wino_stacked(B, IH, IW, row_period)
-        return bool(maps and lib().scda_conv2d_wino_stacked_supported(i32(maps), i32(Cin), i32(Cout)))
-    return bool(lib().scda_conv2d_wino_supported(i32(B), i32(Cin), i32(IH), i32(IW), i32(Cout)))
+    """this convolution (forward: reduced channels Cin, output rows Cout) takes the Winograd path"""
+    return _route(0, B, Cin, IH, IW, Cout, KH, KW, stride, pad, row_period)[0] != 0
 
 
 def wino_wgrad_ok(B, Cin, IH, IW, Cout, KH, KW, stride, pad, row_period=0):
-    """this weight gradient takes the Winograd kernel (SCDA_WINOGRAD_WGRAD=0 keeps it on the direct one)"""
-    if not (wino_enabled() and os.environ.get("SCDA_WINOGRAD_WGRAD", "1") != "0" and KH == 3 and KW == 3 and stride == 1 and pad == 1):
-        return False
-    if row_period:
-        maps = wino_stacked(B, IH, IW, row_period)
-        return bool(maps and lib().scda_conv2d_wino_wgrad_stacked_supported(i32(maps), i32(Cin), i32(Cout)))
-    return bool(lib().scda_conv2d_wino_wgrad_supported(i32(B), i32(Cin), i32(IH), i32(IW), i32(Cout)))
+    """this weight gradient takes the Winograd kernel"""
+    return _route(2, B, Cin, IH, IW, Cout, KH, KW, stride, pad, row_period)[0] != 0
 
 
 def conv2d_wino_wgrad(dy, x, w_shape, out=None, db_out=None, want_bias=False, row_period=0):
@@ -703,9 +692,7 @@ def conv2d_wino(x, u, bias, M, act=ACT_NONE, slope=0.01, mask_src=None, mask_slo
 def conv_pool_fusable(B, Cin, IH, IW, Cout, KH, KW, stride, pad, row_period=0):
     """conv3x3 + activation + 2x2 max-pool can run as one Winograd launch: an eligible layer on an even map with enough tiles to fill the
     chip without split-K (the fused epilogue needs finished values).  SCDA_CONV_POOL_FUSE=0 keeps the pool a launch of its own."""
-    if row_period or os.environ.get("SCDA_CONV_POOL_FUSE", "1") == "0" or not wino_ok(B, Cin, IH, IW, Cout, KH, KW, stride, pad, row_period):
-        return False
-    return ((Cout + 63) // 64) * B * ((IH + 7) // 8) * ((IW + 31) // 32) >= 200
+    return _route(0, B, Cin, IH, IW, Cout, KH, KW, stride, pad, row_period)[1]
 
 
 def conv2d_wino_pool(x, u, bias, M, act=ACT_NONE, slope=0.01):
@@ -741,7 +728,7 @@ def conv2d_pack_all(flat):
         for i, w in enumerate(ws):
             Cout, Cin, KH, KW = w.shape
             src = (w.data_ptr() - base) // 4
-            use_wino = wino is not None and wino[i] and (KH, KW) == (3, 3) and Cin % 8 == 0 and Cout % 8 == 0
+            use_wino = wino is not None and wino[i] and all(L.scda_conv2d_packed_elems(i32(Cout), i32(Cin), i32(KH), i32(KW), i32(d)) for d in (2, 3))
             for d in ((2, 3) if use_wino else (0, 1)):
                 n = int(L.scda_conv2d_packed_elems(i32(Cout), i32(Cin), i32(KH), i32(KW), i32(d)))
                 rows.append([src, off, Cout, Cin, KH * KW, d, tiles])
@@ -804,7 +791,7 @@ def conv2d_dgrad(dy, w, x_shape, stride, pad, act_src=None, act_slope=0.0, row_p
         _req(act_src, "act_src")
         if tuple(act_src.shape) != tuple(x_shape):
             raise ValueError("act_src must have the shape of the conv input")
-    if wino_ok(B, Cout, IH, IW, Cin, KH, KW, stride, pad, row_period):
+    if _route(1, B, Cin, IH, IW, Cout, KH, KW, stride, pad, row_period)[0]:
         return conv2d_wino(dy, conv2d_wino_pack(w, True), None, Cin, ACT_NONE, 0.0, act_src, act_slope, for_dgrad=True, row_period=row_period)
     dx = torch.empty(B, Cin, IH, IW, dtype=torch.float32, device=dy.device)
     if act_src is None and Cin <= 4 and Cout * KH * KW * 16 <= 65536 and (KH, KW) in ((3, 3), (1, 1)):
@@ -1418,6 +1405,25 @@ def plan_gemm(M, N, K, lda, ldb, trans_a=False, trans_b=False, aligned=True, ws_
     lib().scda_debug_plan_gemm(i32(M), i32(N), i32(K), i32(lda), i32(ldb), i32(N if ldc is None else ldc), i32(int(trans_a)), i32(int(trans_b)),
                                i32(int(aligned)), _sz(ws_bytes), out)
     return dict(zip(PLAN_FIELDS, out))
+
+
+WINO_PLAN_FIELDS = ("mb", "pixel_major", "gm", "splits", "slabs_per_split", "per_xcd", "n_wg", "persist", "epi")
+WINO_WGRAD_PLAN_FIELDS = ("n_slab", "splits", "slabs_per_split", "splits_per_xcd", "order", "grid")
+
+
+def plan_wino(kind, batch, cin, ih, iw, cout, row_period=0, ws_bytes=None):
+    """the launch decision of a stride-1 pad-1 3x3 layer on the Winograd kernels, for a 256-CU device (no GPU needed): kind "fwd" |
+    "fwd_pool" | "dgrad" | "dgrad_mask" -> WINO_PLAN_FIELDS, "wgrad" | "wgrad_bias" -> WINO_WGRAD_PLAN_FIELDS.  ws_bytes defaults to
+    what the operators pass"""
+    L = lib()
+    if ws_bytes is None:
+        L.scda_conv2d_workspace_bytes.restype = ctypes.c_size_t
+        ws_bytes = 0 if kind == "fwd_pool" else L.scda_conv2d_workspace_bytes(i32(batch), i32(cin), i32(ih), i32(iw), i32(cout), i32(3), i32(3), i32(1), i32(1))
+    C, M = (cout, cin) if kind.startswith("dgrad") else (cin, cout)      # the data gradient reduces over Cout
+    fwd, wgrad = (ctypes.c_int * 9)(), (ctypes.c_int * 6)()
+    L.scda_debug_plan_wino(i32(batch), i32(C), i32(ih), i32(iw), i32(M), i32(wino_stacked(batch, ih, iw, row_period)), i32(int(kind == "fwd_pool")),
+                           i32(int(kind == "dgrad_mask")), i32(int(kind == "wgrad_bias")), _sz(ws_bytes), fwd, wgrad)
+    return dict(zip(WINO_WGRAD_PLAN_FIELDS, wgrad)) if kind.startswith("wgrad") else dict(zip(WINO_PLAN_FIELDS, fwd))
 
 
 def wino_last_persistent():

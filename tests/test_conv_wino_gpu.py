@@ -203,10 +203,14 @@ def test_conv_pool_fusion_is_bit_identical_to_separate_launches(cuda, monkeypatc
     assert float(d) < 2e-3, float(d)
 
 
-@pytest.mark.parametrize("case,gm", [((1, 64, 64, 128, 512), 2), ((1, 64, 64, 128, 512), 4), ((1, 128, 64, 128, 256), 2),
-                                     ((1, 128, 64, 128, 256), 4), ((2, 64, 64, 64, 128), 2), ((2, 64, 64, 64, 128), 4)])
+# (module-level lists: tests/test_launch_plans.py pins the launch decision of every case here on the CPU)
+GM_CASES = [((1, 64, 64, 128, 512), 2), ((1, 64, 64, 128, 512), 4), ((1, 128, 64, 128, 256), 2),
+            ((1, 128, 64, 128, 256), 4), ((2, 64, 64, 64, 128), 2), ((2, 64, 64, 64, 128), 4)]
+
+
+@pytest.mark.parametrize("case,gm", GM_CASES)
 def test_wino_xcd_split_orders_give_the_same_result(cuda, case, gm, monkeypatch):
-    """the launch order (which XCD runs which (m-tile, pixel block): csrc/conv_wino.hip wino_launch) is a pure renumbering of the
+    """the launch order (which XCD runs which (m-tile, pixel block): csrc/launch_plan.h decide_wino) is a pure renumbering of the
     workgroups: every forced split of the XCDs over m-tile groups x pixel-block runs gives the bits of the plain order"""
     from scda_amd import native
     B, Cin, H, W, Cout = case
@@ -225,8 +229,11 @@ def test_wino_xcd_split_orders_give_the_same_result(cuda, case, gm, monkeypatch)
     close(y1, F.relu(F.conv2d(x.cpu(), w.cpu(), b.cpu(), stride=1, padding=1)))
 
 
-@pytest.mark.parametrize("case,splits", [((1, 64, 32, 64, 512), 2), ((1, 64, 32, 64, 512), 4), ((1, 128, 16, 64, 256), 2),
-                                         ((1, 512, 32, 64, 512), 4), ((2, 64, 16, 64, 128), 4)])
+WGRAD_SPLIT_CASES = [((1, 64, 32, 64, 512), 2), ((1, 64, 32, 64, 512), 4), ((1, 128, 16, 64, 256), 2),
+                     ((1, 512, 32, 64, 512), 4), ((2, 64, 16, 64, 128), 4)]
+
+
+@pytest.mark.parametrize("case,splits", WGRAD_SPLIT_CASES)
 def test_wino_wgrad_split_groups_give_the_same_result(cuda, case, splits, monkeypatch):
     """2 or 4 K-splits: one split and one m-tile group per XCD (conv_wino_wgrad_kernel's index decode) -- the same partial slabs,
     the same fixed-order reduce: bit-identical to the launch dealt over the XCDs as it comes"""
@@ -247,9 +254,10 @@ def test_wino_wgrad_split_groups_give_the_same_result(cuda, case, splits, monkey
     assert torch.equal(dw0, dw1) and torch.equal(db0, db1)
     close(dw1, w.grad); close(db1, bias.grad)
 
+PERSIST_CASES = [(1, 256, 128, 256, 256), (3, 72, 70, 200, 72), (1, 64, 256, 512, 64)]
 
 
-@pytest.mark.parametrize("case", [(1, 256, 128, 256, 256), (3, 72, 70, 200, 72), (1, 64, 256, 512, 64)])
+@pytest.mark.parametrize("case", PERSIST_CASES)
 def test_wino_persistent_form_is_bit_identical_to_one_tile_per_workgroup(cuda, case, monkeypatch):
     """launches of more 64-row tiles than CUs run as one persistent workgroup per CU that walks the tiles (next tile's patches requested
     before the epilogue, stores left to drain under the next K loop): forward (bias + activation), data gradient with the fused
@@ -275,7 +283,10 @@ def test_wino_persistent_form_is_bit_identical_to_one_tile_per_workgroup(cuda, c
         assert torch.equal(a, c)
 
 
-@pytest.mark.parametrize("case,splits", [((1, 256, 128, 256, 256), 2), ((1, 128, 64, 128, 128), 2), ((3, 72, 70, 200, 72), 3)])
+FORCED_SPLIT_CASES = [((1, 256, 128, 256, 256), 2), ((1, 128, 64, 128, 128), 2), ((3, 72, 70, 200, 72), 3)]
+
+
+@pytest.mark.parametrize("case,splits", FORCED_SPLIT_CASES)
 def test_wino_forced_split_on_a_launch_of_more_tiles_than_cus(cuda, case, splits, monkeypatch):
     """SCDA_WINO_SPLITS on a layer of more 64-row tiles than CUs (the persistent form's territory; the automatic heuristic never splits
     there): the launch must take the one-tile split form + reduce and give the unsplit launch's result to rounding -- a persistent
@@ -298,7 +309,11 @@ def test_wino_forced_split_on_a_launch_of_more_tiles_than_cus(cuda, case, splits
     close(y1, F.relu(F.conv2d(x.cpu(), w.cpu(), b.cpu(), stride=1, padding=1)))
 
 
-@pytest.mark.parametrize("case", [(512, 64, 64), (37, 72, 40), (6, 512, 512), (130, 128, 256)])
+STACKED_CASES = [(512, 64, 64), (37, 72, 40), (6, 512, 512), (130, 128, 256)]        # maps, Cin, Cout
+STACKED_WGRAD_CASES = [(512, 64, 64), (37, 72, 80), (7, 128, 256)]
+
+
+@pytest.mark.parametrize("case", STACKED_CASES)
 @pytest.mark.parametrize("masked", [False, True])
 def test_wino_on_stacked_7x7_maps(cuda, case, masked, monkeypatch):
     """x [1, C, R * 7, 7] as a stack of R independent 7 x 7 maps (row period 7: the ResNet-50 C4 detector's channel-major RoI head,
@@ -329,7 +344,7 @@ def test_wino_on_stacked_7x7_maps(cuda, case, masked, monkeypatch):
     close(y, y0, 5e-5)
 
 
-@pytest.mark.parametrize("case", [(512, 64, 64), (37, 72, 80), (7, 128, 256)])
+@pytest.mark.parametrize("case", STACKED_WGRAD_CASES)
 def test_wino_wgrad_on_stacked_7x7_maps(cuda, case, monkeypatch):
     """the weight (+ bias) gradient on stacks of 7 x 7 maps: a K-slab = one tile row of a pair of maps (odd map counts: the last
     pair's second map is masked), against torch's batched convolution on [R, C, 7, 7] and the direct kernel on the same stack"""
