@@ -329,6 +329,72 @@ size_t scda_mask_iou_workspace_bytes(int M, int N, int H, int Wd);
 int scda_mask_iou_hip(const uint32_t *dt_bits, int M, const uint32_t *gt_bits, int N, int H, int Wd, int h, int w,
                       const unsigned char *iscrowd_or_null, void *ws, double *iou, uint32_t *inter, void *stream);
 
+/* ---- COCO AP on the device (scda_amd/csrc/coco_eval.hip; opt-in: scda_amd.coco_eval.CocoEvaluator) ---------------------------------
+ * The detection evaluator of the reference's datasets/pycocotools/cocoeval.py (COCOeval.evaluate / accumulate / summarize, iouType
+ * 'bbox' and 'segm', useCats = 1) and bbIou of datasets/pycocotools/common/maskApi.c, bit for bit: integer work plus single IEEE double
+ * operations in the reference's order.  The only atomics are integer adds; two runs give the same bytes.  tests/coco_eval_np.py restates
+ * the rules in numpy; tests/golden/coco_eval_ref.npz holds what the reference's own code gives.  Thresholds, area ranges and maxDets
+ * are DEVICE arrays filled by the host (np.linspace values as Params.setDetParams computes them); the limits are T <= 16 thresholds,
+ * A <= 8 area ranges, M <= 4 maxDets, R <= 128 recall thresholds, K <= 255 categories (indices 1..K), D, G <= 1024 detection slots /
+ * ground truths per image.  Not covered: keypoints / OKS, useCats = 0, the JSON round trip, anything of coco.py.  No call waits for
+ * the host or allocates.
+ *
+ * scda_coco_det_rows_hip: detections [B, top_n, 7] = (b, x1, y1, x2, y2, score, class) + detection_counts i32 [B] (scda_box_predict_hip's
+ *   outputs) -> dt_xywh f64 [B, top_n, 4] = ((double) x1, (double) y1, (double) x2 - (double) x1, (double) y2 - (double) y1), dt_area f64
+ *   = w * h, or (double) mask_area_or_null[slot] (uint32 [B, top_n], scda_mask_rle_hip's area) for 'segm'; score f32; cat i32 = the class
+ *   when the slot is below its image's count and 1 <= class <= K, else 0 (the slot takes no part).
+ * scda_coco_box_iou_hip: bbIou (maskApi.c:110-121) for B images: dt f64 [B, D, 4] and gt f64 [B, G, 4] xywh, iscrowd u8 [B, G], counts
+ *   i32 [B] read on the device -> iou f64 [B, G * D], o[g * D + d] per image (D = the slot capacity: the layout scda_mask_iou_hip
+ *   writes for M = D detections), written for d < dt_counts[b], g < gt_counts[b].  Per pair, all in double, in this order:
+ *   w = fmin(d.x + d.w, g.x + g.w) - fmax(d.x, g.x), h likewise; o = 0 when w <= 0 or h <= 0; i = w * h;
+ *   u = iscrowd[g] ? d.w * d.h : d.w * d.h + g.w * g.h - i; o = i / u.
+ * scda_coco_match_hip: evaluateImg (cocoeval.py:236-314) for B images in one launch, one workgroup per (image, category k = 1..K), one
+ *   lane per (area range a, threshold t).  iou as above (either source).  Per (image, category) with at least one detection or GT:
+ *   seen[k - 1] = 1;
+ *   detections: the slots of cat == k in descending score order, ties in slot order (the stable mergesort on -score); rank = the
+ *     position in that order, written for every such slot; only rank < max_det (= maxDets[-1]) take part;
+ *   GTs (rows < gt_counts[b] with gt_cat == k): _ignore = iscrowd || area < aRng[a][0] || area > aRng[a][1] -- both bounds inclusive, an
+ *     area equal to a bound is inside --; visited non-ignored first, otherwise in row order (the stable argsort of _ignore);
+ *     npig[k - 1, a] += the number of non-ignored ones (integer atomic add);
+ *   per (a, t), detections in rank order: iou = min(t, 1 - 1e-10), m = none; for each GT in that order: skip it when it is matched
+ *     already and is no crowd; STOP when m is a non-ignored GT and this one is ignored; skip it when ious < iou; else iou = ious, m = it
+ *     (so an IoU equal to the threshold matches, and of two GTs with equal IoU the later one wins).  m found: the detection is matched,
+ *     its ignore flag is m's _ignore, m is marked matched.  Not found: it is ignored when its area < aRng[a][0] or > aRng[a][1].
+ *   Outputs per slot (the rows of its image): rank i32 [B, D]; bits u32 [B, D, A] = matched (bit t) | ignored (bit 16 + t), zero for
+ *   rank >= max_det; with dbg_match_or_null i32 [B, D, A, T]: the matched GT's row in its image or -1, written for the slots of cat > 0.
+ *   The (image, category)'s IoU block is staged in LDS when it has at most 2048 entries and read from memory otherwise.
+ *   npig i32 [K, A] and seen i32 [K] ACCUMULATE over calls: zero them before the first image.
+ * scda_coco_accumulate_hip: accumulate (cocoeval.py:316-419) over the rows of n_images images (image_ids i32 [n_images], distinct; cat,
+ *   rank, score [n_images, D], bits [n_images, D, A] as written above, in ANY image order).  The reference's concatenation and stable
+ *   mergesort on -score is the total order (category, score descending, image id ascending, rank ascending); it is produced by a stable
+ *   LSD radix sort, 8 bits per pass: the images by id (4 passes), then the rows in (image, slot) order by score (4 passes) and category
+ *   (1 pass) -- within an (image, category) equal scores are in slot order, which is their rank order.  The maxDets subsets are the
+ *   rows of rank < maxDets[m] of that one order.  Per (k, a, m, t) over the category's rows: tp = matched && !ignored, fp = !matched &&
+ *   !ignored as inclusive integer scans converted to double; rc = tp / npig; pr = tp / (fp + tp + 2.220446049250313e-16); pr replaced
+ *   by its right-to-left running maximum; per recall threshold the first index with rc >= thr (searchsorted left) gives precision
+ *   [t, r, k, a, m] = pr there and scores [...] = the score there, 0 for every threshold no index satisfies; recall [t, k, a, m] =
+ *   rc[last], 0 without detections.  Entries are -1 where seen[k] == 0 or npig[k, a] == 0.  precision / scores f64 [T, R, K, A, M],
+ *   recall f64 [T, K, A, M].  ws: scda_coco_accumulate_workspace_bytes(n_images, D, K, A) bytes, 16-byte aligned.
+ * scda_coco_summarize_hip: _summarizeDets.  spec i32 [n_stats, 4] (device) = (ap, t, a, m): the mean over the entries > -1 of
+ *   precision[t, :, :, a, m] (ap != 0) or recall[t, :, a, m]; t = -1 every threshold, t = -2 none (the reference's np.where found no
+ *   such threshold); -1 when no entry qualifies -> stats f64 [n_stats].  The sum is taken in a fixed order (deterministic); it differs
+ *   from numpy's pairwise mean by at most 2 N 2^-53 for N averaged entries in [0, 1]. */
+int scda_coco_det_rows_hip(const float *detections, const int *detection_counts, int B, int top_n, const uint32_t *mask_area_or_null,
+                           int K, double *dt_xywh, double *dt_area, float *score, int *cat, void *stream);
+int scda_coco_box_iou_hip(const double *dt, const int *dt_counts, const double *gt, const int *gt_counts, const unsigned char *iscrowd,
+                          int B, int D, int G, double *iou, void *stream);
+int scda_coco_match_hip(const double *iou, int B, int D, int G, const int *dt_counts, const int *dt_cat, const float *score,
+                        const double *dt_area, const int *gt_counts, const int *gt_cat, const double *gt_area,
+                        const unsigned char *gt_iscrowd, int K, const double *iou_thrs, int T, const double *area_rng, int A, int max_det,
+                        int *rank, uint32_t *bits, int *npig, int *seen, int *dbg_match_or_null, void *stream);
+size_t scda_coco_accumulate_workspace_bytes(int n_images, int D, int K, int A);
+int scda_coco_accumulate_hip(const int *image_ids, int n_images, int D, const int *cat, const int *rank, const float *score,
+                             const uint32_t *bits, const int *npig, const int *seen, int K, int T, int A, const double *rec_thrs, int R,
+                             const int *max_dets, int M, int max_det_last, void *ws, double *precision, double *recall, double *scores,
+                             void *stream);
+int scda_coco_summarize_hip(const double *precision, const double *recall, int T, int R, int K, int A, int M, const int *spec,
+                            int n_stats, double *stats, void *stream);
+
 /* ------------------------------------------------- convolution / GEMM ---- */
 /* The reference reaches these through torch.nn (cuDNN / cuBLAS): nn.Conv2d in
  * models/faster_rcnn/vgg_adver_expansion_cluster.py:101-114 (VGG body),

@@ -1,0 +1,648 @@
+// coco_eval.hip -- COCO AP on the device (gfx950): the detection evaluator of datasets/pycocotools/cocoeval.py (COCOeval.evaluate,
+// accumulate, summarize for iouType 'bbox' / 'segm', useCats = 1) and bbIou of datasets/pycocotools/common/maskApi.c.  The rules are
+// stated in include/scda_ops.h and restated in numpy by tests/coco_eval_np.py.  Everything is integer work plus single IEEE double
+// operations in the reference's order (built with -ffp-contract=off), so the arrays are the reference's bit for bit; the only atomics
+// are integer adds (the non-ignored GT counts) and integer LDS histogram counters, so two runs give the same bytes.
+//
+//   det_rows_kernel     per detection slot: xywh and area in double from the float32 corners, score, category (0 = padding)
+//   box_iou_kernel      per (image, gt, dt) pair: bbIou
+//   match_kernel        per (image, category): ranks, the GT orders, evaluateImg's greedy matching, one lane per (area range, threshold)
+//   sort_*_kernel       stable LSD radix sort, 8 bits per pass: per-tile histograms, one scan, a stable scatter (wave match by ballots)
+//   gather_kernel       the rows in sorted order (score, rank, match bits), category segments
+//   pr_kernel           per (category, area range, maxDets): tp / fp scans, precision envelope, the recall thresholds
+//   stats_kernel        the 12 numbers of _summarizeDets
+#include "common.h"
+
+namespace {
+using namespace scda;
+
+constexpr int kMaxT = 16, kMaxA = 8, kMaxM = 4, kMaxRec = 128, kMaxPer = 1024;
+constexpr int kMatchThreads = 128;              // >= kMaxT * kMaxA lanes, one per (area range, threshold)
+constexpr int kIouLds = 2048;                   // doubles of one (image, category)'s IoU block staged in LDS
+constexpr int kGtmWords = kMaxPer / 32;
+
+// grid-stride over B * top_n slots
+__global__ __launch_bounds__(256) void det_rows_kernel(const float *__restrict__ det, const int *__restrict__ counts, int B, int top_n,
+                                                       const uint32_t *__restrict__ mask_area, int K, double *__restrict__ xywh,
+                                                       double *__restrict__ area, float *__restrict__ score, int *__restrict__ cat) {
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < B * top_n; i += gridDim.x * blockDim.x) {
+        const int b = i / top_n, d = i - b * top_n;
+        const float *r = det + (size_t)i * 7;
+        const double x = (double)r[1], y = (double)r[2];
+        const double w = (double)r[3] - x, h = (double)r[4] - y;
+        const bool live = d < counts[b];
+        const float c = r[6];
+        xywh[(size_t)i * 4 + 0] = x; xywh[(size_t)i * 4 + 1] = y; xywh[(size_t)i * 4 + 2] = w; xywh[(size_t)i * 4 + 3] = h;
+        area[i] = mask_area ? (double)mask_area[i] : w * h;
+        score[i] = live ? r[5] : 0.0f;
+        cat[i] = (live && c >= 1.0f && c <= (float)K) ? (int)c : 0;
+    }
+}
+
+// grid (cdiv(D * G, 256), B): o[b][g * D + d], d < dt_counts[b], g < gt_counts[b] (the rest is not written)
+__global__ __launch_bounds__(256) void box_iou_kernel(const double *__restrict__ dt, const int *__restrict__ dt_counts,
+                                                      const double *__restrict__ gt, const int *__restrict__ gt_counts,
+                                                      const unsigned char *__restrict__ iscrowd, int D, int G, double *__restrict__ iou) {
+    const int b = blockIdx.y, i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= D * G) return;
+    const int g = i / D, d = i - g * D;
+    if (d >= dt_counts[b] || g >= gt_counts[b]) return;
+    const double *p = dt + ((size_t)b * D + d) * 4, *q = gt + ((size_t)b * G + g) * 4;
+    const double da = p[2] * p[3], ga = q[2] * q[3];
+    const double w = fmin(p[2] + p[0], q[2] + q[0]) - fmax(p[0], q[0]);
+    const double h = fmin(p[3] + p[1], q[3] + q[1]) - fmax(p[1], q[1]);
+    double o = 0.0;
+    if (!(w <= 0.0) && !(h <= 0.0)) {
+        const double in = w * h;
+        const double u = iscrowd[(size_t)b * G + g] ? da : da + ga - in;
+        o = in / u;
+    }
+    iou[(size_t)b * D * G + i] = o;
+}
+
+// stable compaction by one wave: the indices i < n with pred(i), in order, appended to list at *cnt (wave-uniform)
+template <class Pred>
+__device__ inline int wave_compact(int n, int lane, uint16_t *list, int cnt, Pred pred) {
+    for (int base = 0; base < n; base += 64) {
+        const int i = base + lane;
+        const bool f = i < n && pred(i);
+        const unsigned long long m = __ballot(f);
+        if (f) list[cnt + __popcll(m & ((1ull << lane) - 1ull))] = (uint16_t)i;
+        cnt += __popcll(m);
+    }
+    return cnt;
+}
+
+struct MatchArgs {
+    const double *iou;                          // [B, G * D]
+    const int *dt_counts, *dt_cat;              // [B], [B, D]
+    const float *score;                         // [B, D]
+    const double *dt_area;                      // [B, D]
+    const int *gt_counts, *gt_cat;              // [B], [B, G]
+    const double *gt_area;                      // [B, G]
+    const unsigned char *gt_iscrowd;            // [B, G]
+    const double *iou_thrs, *area_rng;          // [T], [A, 2]
+    int D, G, K, T, A, max_det;
+    int *rank;                                  // [B, D]
+    uint32_t *bits;                             // [B, D, A]: matched (bit t) | ignored (bit 16 + t)
+    int *npig, *seen;                           // [K, A], [K]
+    int *dbg;                                   // [B, D, A, T] or null
+};
+
+// grid (K, B), 128 threads: evaluateImg of image b, category k + 1, for every area range and threshold
+__global__ __launch_bounds__(kMatchThreads) void match_kernel(MatchArgs p) {
+    __shared__ double s_iou[kIouLds];
+    __shared__ uint32_t s_gtm[kGtmWords][kMatchThreads];
+    __shared__ uint16_t s_go[kMaxA][kMaxPer];   // per area range: the category's GTs, non-ignored first; bit 15 = crowd
+    __shared__ float s_score[kMaxPer];
+    __shared__ uint16_t s_dl[kMaxPer], s_gl[kMaxPer], s_sorted[kMaxPer];
+    __shared__ uint32_t s_tile[kMatchThreads][2];
+    __shared__ int s_cnt[2], s_nni[kMaxA];
+    const int k = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int nd = min(p.dt_counts[b], p.D), ng = min(p.gt_counts[b], p.G);
+    const int *dcat = p.dt_cat + (size_t)b * p.D, *gcat = p.gt_cat + (size_t)b * p.G;
+    const unsigned char *crowd = p.gt_iscrowd + (size_t)b * p.G;
+    // ---- this category's detections and ground truths, in the order given
+    if (wv == 0) {
+        const int c = wave_compact(nd, lane, s_dl, 0, [&](int i) { return dcat[i] == k + 1; });
+        if (lane == 0) s_cnt[0] = c;
+    } else {
+        const int c = wave_compact(ng, lane, s_gl, 0, [&](int i) { return gcat[i] == k + 1; });
+        if (lane == 0) s_cnt[1] = c;
+    }
+    __syncthreads();
+    const int Dc = s_cnt[0], Gc = s_cnt[1];
+    if (Dc == 0 && Gc == 0) return;
+    if (tid == 0) p.seen[k] = 1;
+    for (int i = tid; i < Dc; i += kMatchThreads) s_score[i] = p.score[(size_t)b * p.D + s_dl[i]];
+    __syncthreads();
+    // ---- rank = position under the stable sort on -score; the first max_det take part
+    for (int i = tid; i < Dc; i += kMatchThreads) {
+        const float s = s_score[i];
+        int r = 0;
+        for (int j = 0; j < Dc; ++j) r += (s_score[j] > s || (s_score[j] == s && j < i)) ? 1 : 0;
+        s_sorted[r] = s_dl[i];
+        p.rank[(size_t)b * p.D + s_dl[i]] = r;
+    }
+    // ---- per area range: _ignore = iscrowd || area < lo || area > hi; non-ignored first, otherwise as given
+    for (int a = wv; a < p.A; a += kMatchThreads / 64) {
+        const double lo = p.area_rng[2 * a], hi = p.area_rng[2 * a + 1];
+        const double *ga = p.gt_area + (size_t)b * p.G;
+        auto ign = [&](int i) { const int g = s_gl[i]; return crowd[g] != 0 || ga[g] < lo || ga[g] > hi; };
+        const int n0 = wave_compact(Gc, lane, s_go[a], 0, [&](int i) { return !ign(i); });
+        wave_compact(Gc, lane, s_go[a], n0, [&](int i) { return ign(i); });
+        if (lane == 0) {
+            s_nni[a] = n0;
+            if (n0) atomicAdd(p.npig + k * p.A + a, n0);
+        }
+    }
+    __syncthreads();
+    const int Dm = min(Dc, p.max_det);
+    // s_go holds positions in s_gl; add the crowd flag
+    for (int i = tid; i < p.A * Gc; i += kMatchThreads) {
+        const int a = i / Gc, j = i - a * Gc;
+        const uint32_t pos = s_go[a][j];
+        s_go[a][j] = (uint16_t)(pos | (crowd[s_gl[pos]] ? 0x8000u : 0u));
+    }
+    // the IoU block [Gc, Dm] of the category, rows in s_gl's order, columns in rank order, where it fits
+    const bool staged = Gc * Dm <= kIouLds;
+    const double *iou = p.iou + (size_t)b * p.D * p.G;
+    if (staged)
+        for (int i = tid; i < Gc * Dm; i += kMatchThreads) {
+            const int j = i / Dm, d = i - j * Dm;
+            s_iou[i] = iou[(size_t)s_gl[j] * p.D + s_sorted[d]];
+        }
+    for (int w = 0; w < (Gc + 31) / 32; ++w) s_gtm[w][tid] = 0u;
+    __syncthreads();
+    const bool active = tid < p.A * p.T;
+    const int a = active ? tid / p.T : 0, t = active ? tid - a * p.T : 0;
+    const double thr = active ? fmin(p.iou_thrs[t], 1 - 1e-10) : 0.0;
+    const double lo = p.area_rng[2 * a], hi = p.area_rng[2 * a + 1];
+    const int nni = s_nni[a];
+    uint32_t mbits = 0, ibits = 0;
+    for (int d = 0; d < Dm; ++d) {
+        const int di = s_sorted[d];
+        if (active) {
+            double best = thr;
+            int m = -1;
+            for (int gi = 0; gi < Gc; ++gi) {
+                const uint32_t e = s_go[a][gi];
+                if (((s_gtm[gi >> 5][tid] >> (gi & 31)) & 1u) && !(e & 0x8000u)) continue;
+                if (m > -1 && m < nni && gi >= nni) break;
+                const int j = e & 0x7fff;
+                const double v = staged ? s_iou[j * Dm + d] : iou[(size_t)s_gl[j] * p.D + di];
+                if (v < best) continue;
+                best = v;
+                m = gi;
+            }
+            bool ig;
+            int row = -1;
+            if (m >= 0) {
+                s_gtm[m >> 5][tid] |= 1u << (m & 31);
+                mbits |= 1u << (d & 31);
+                ig = m >= nni;
+                row = s_gl[s_go[a][m] & 0x7fff];
+            } else {
+                const double ar = p.dt_area[(size_t)b * p.D + di];
+                ig = ar < lo || ar > hi;
+            }
+            if (ig) ibits |= 1u << (d & 31);
+            if (p.dbg) p.dbg[(((size_t)b * p.D + di) * p.A + a) * p.T + t] = row;
+        }
+        if ((d & 31) == 31 || d == Dm - 1) {
+            // 32 detections done: the lanes' bit columns become per-detection threshold masks
+            s_tile[tid][0] = mbits; s_tile[tid][1] = ibits;
+            mbits = ibits = 0;
+            __syncthreads();
+            const int d0 = d & ~31, cnt = d - d0 + 1;
+            for (int i = tid; i < cnt * p.A; i += kMatchThreads) {
+                const int j = i / p.A, aa = i - j * p.A;
+                uint32_t mm = 0, ii = 0;
+                for (int tt = 0; tt < p.T; ++tt) {
+                    mm |= ((s_tile[aa * p.T + tt][0] >> j) & 1u) << tt;
+                    ii |= ((s_tile[aa * p.T + tt][1] >> j) & 1u) << tt;
+                }
+                p.bits[((size_t)b * p.D + s_sorted[d0 + j]) * p.A + aa] = mm | (ii << 16);
+            }
+            __syncthreads();
+        }
+    }
+    // detections past max_det take no part: no bits, no match
+    for (int i = Dm * p.A + tid; i < Dc * p.A; i += kMatchThreads) {
+        const int j = i / p.A, aa = i - j * p.A;
+        p.bits[((size_t)b * p.D + s_sorted[j]) * p.A + aa] = 0u;
+        if (p.dbg)
+            for (int tt = 0; tt < p.T; ++tt) p.dbg[(((size_t)b * p.D + s_sorted[j]) * p.A + aa) * p.T + tt] = -1;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ the stable radix sort
+constexpr int kSortRounds = 16, kSortTile = 64 * kSortRounds;
+
+struct SortKey {
+    int kind;                                   // 0: image id, 1: score (descending), 2: category (0 = the row takes no part)
+    int shift;
+    const int *ids;
+    const float *score;
+    const int *cat, *rank;
+    int max_det;
+};
+
+__device__ inline uint32_t sort_digit(const SortKey &k, uint32_t e) {
+    uint32_t v;
+    if (k.kind == 0) {
+        v = (uint32_t)k.ids[e] ^ 0x80000000u;
+    } else if (k.kind == 1) {
+        const float s = k.score[e];
+        const uint32_t u = s == 0.0f ? 0u : __float_as_uint(s);
+        v = ~((u & 0x80000000u) ? ~u : (u | 0x80000000u));
+    } else {
+        v = (k.cat[e] > 0 && k.rank[e] < k.max_det) ? (uint32_t)k.cat[e] : 0u;
+    }
+    return (v >> k.shift) & 255u;
+}
+
+__global__ __launch_bounds__(256) void iota_kernel(uint32_t *out, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = (uint32_t)i;
+}
+
+// rows in (image id, slot) order: the sequence the reference concatenates
+__global__ __launch_bounds__(256) void rows_kernel(const uint32_t *__restrict__ img_order, int D, uint32_t *out, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = img_order[i / D] * (uint32_t)D + (uint32_t)(i % D);
+}
+
+// grid (tiles), 64 threads: hist [tiles, 256]
+__global__ __launch_bounds__(64) void sort_hist_kernel(const uint32_t *__restrict__ src, int n, SortKey key, uint32_t *__restrict__ hist) {
+    __shared__ uint32_t h[256];
+    const int lane = threadIdx.x;
+    for (int q = lane; q < 256; q += 64) h[q] = 0;
+    __syncthreads();
+    for (int r = 0; r < kSortRounds; ++r) {
+        const int i = blockIdx.x * kSortTile + r * 64 + lane;
+        if (i < n) atomicAdd(&h[sort_digit(key, src[i])], 1u);
+    }
+    __syncthreads();
+    for (int q = lane; q < 256; q += 64) hist[(size_t)blockIdx.x * 256 + q] = h[q];
+}
+
+// exclusive scan of one value per thread over 256 threads
+__device__ inline uint32_t block_excl_scan256(uint32_t v, uint32_t *wave_sums, uint32_t *total) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    uint32_t inc = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t o = __shfl_up(inc, d, 64);
+        if (lane >= d) inc += o;
+    }
+    __syncthreads();
+    if (lane == 63) wave_sums[wv] = inc;
+    __syncthreads();
+    uint32_t before = 0, all = 0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        if (q < wv) before += wave_sums[q];
+        all += wave_sums[q];
+    }
+    *total = all;
+    return before + inc - v;
+}
+
+// one block of 256 threads: hist [tiles, 256] -> each (tile, digit)'s first output index, digits major
+__global__ __launch_bounds__(256) void sort_scan_kernel(uint32_t *__restrict__ hist, int tiles) {
+    __shared__ uint32_t wave_sums[4];
+    const int d = threadIdx.x;
+    uint32_t tot = 0;
+    for (int b = 0; b < tiles; ++b) tot += hist[(size_t)b * 256 + d];
+    uint32_t all;
+    uint32_t run = block_excl_scan256(tot, wave_sums, &all);
+    for (int b = 0; b < tiles; ++b) {
+        const uint32_t v = hist[(size_t)b * 256 + d];
+        hist[(size_t)b * 256 + d] = run;
+        run += v;
+    }
+}
+
+// grid (tiles), 64 threads: 64 elements per round; a lane's place among the lanes of its digit comes from 8 ballots
+__global__ __launch_bounds__(64) void sort_scatter_kernel(const uint32_t *__restrict__ src, uint32_t *__restrict__ dst, int n, SortKey key,
+                                                          const uint32_t *__restrict__ offs) {
+    __shared__ uint32_t base[256];
+    const int lane = threadIdx.x;
+    for (int q = lane; q < 256; q += 64) base[q] = offs[(size_t)blockIdx.x * 256 + q];
+    __syncthreads();
+    for (int r = 0; r < kSortRounds; ++r) {
+        const int i = blockIdx.x * kSortTile + r * 64 + lane;
+        const bool valid = i < n;
+        const uint32_t e = valid ? src[i] : 0u;
+        const uint32_t dg = valid ? sort_digit(key, e) : 0u;
+        unsigned long long peers = __ballot(valid);
+#pragma unroll
+        for (int bit = 0; bit < 8; ++bit) {
+            const bool s = (dg >> bit) & 1u;
+            const unsigned long long m = __ballot(valid && s);
+            peers &= s ? m : ~m;
+        }
+        const int before = __popcll(peers & ((1ull << lane) - 1ull)), all = __popcll(peers);
+        uint32_t pos = 0;
+        if (valid) pos = base[dg] + before;
+        __syncthreads();
+        if (valid && before == all - 1) base[dg] += all;
+        __syncthreads();
+        if (valid && pos < (uint32_t)n) dst[pos] = e;
+    }
+}
+
+// the rows in sorted order.  s_bits [A, n]
+__global__ __launch_bounds__(256) void gather_kernel(const uint32_t *__restrict__ perm, int n, const float *__restrict__ score,
+                                                     const int *__restrict__ cat, const int *__restrict__ rank,
+                                                     const uint32_t *__restrict__ bits, int A, int max_det, float *__restrict__ s_score,
+                                                     int *__restrict__ s_rank, int *__restrict__ s_cat, uint32_t *__restrict__ s_bits) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t e = perm[i];
+    const bool part = cat[e] > 0 && rank[e] < max_det;
+    s_score[i] = score[e];
+    s_rank[i] = rank[e];
+    s_cat[i] = part ? cat[e] : 0;
+    for (int a = 0; a < A; ++a) s_bits[(size_t)a * n + i] = part ? bits[(size_t)e * A + a] : 0u;
+}
+
+// seg [2, K + 1]: first row and row count of every category's segment (zeroed before)
+__global__ __launch_bounds__(256) void segment_kernel(const int *__restrict__ s_cat, int n, int K, int *__restrict__ seg) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int c = s_cat[i];
+    if (i == 0 || s_cat[i - 1] != c) seg[c] = i;
+    if (i == n - 1 || s_cat[i + 1] != c) seg[K + 1 + c] = i + 1;         // the END here; the count is taken by the reader
+}
+
+__global__ __launch_bounds__(256) void fill_kernel(double *p, size_t n, double v) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[i] = v;
+}
+
+struct PrArgs {
+    const float *s_score;
+    const int *s_rank;
+    const uint32_t *s_bits;
+    const int *seg, *npig, *seen, *max_dets;
+    const double *rec;
+    int n, K, T, A, M, R;
+    double *precision, *recall, *scores;
+};
+
+// grid (K * A * M), 256 threads.  The rows are visited from the LAST to the first, so the scans in thread order are suffix scans
+__global__ __launch_bounds__(256) void pr_kernel(PrArgs p) {
+    __shared__ int cs[kMaxRec];
+    __shared__ unsigned long long w_cnt[4];
+    __shared__ uint32_t w_in[4];
+    __shared__ double w_max[4];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int m = blockIdx.x % p.M, a = (blockIdx.x / p.M) % p.A, k = blockIdx.x / (p.M * p.A);
+    const int np = p.npig[k * p.A + a];
+    if (!p.seen[k] || np == 0) return;          // the arrays hold -1 already
+    const int start = p.seg[k + 1], end = p.seg[p.K + 1 + k + 1];
+    const int n = end > start ? end - start : 0;
+    const int md = p.max_dets[m];
+    // cs[r] = the smallest count c with c / npig >= recThrs[r] (np + 1: none); rc >= thr first holds at the c-th true positive
+    for (int r = tid; r < p.R; r += 256) {
+        int lo = 0, hi = np + 1;
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if ((double)mid / (double)np >= p.rec[r]) hi = mid; else lo = mid + 1;
+        }
+        cs[r] = lo;
+    }
+    const float *score = p.s_score + start;
+    const int *rank = p.s_rank + start;
+    const uint32_t *bits = p.s_bits + (size_t)a * p.n + start;
+    for (int t = 0; t < p.T; ++t) {
+        const size_t o_rec = (((size_t)t * p.K + k) * p.A + a) * p.M + m;
+        for (int r = tid; r < p.R; r += 256) {
+            const size_t o = ((((size_t)t * p.R + r) * p.K + k) * p.A + a) * p.M + m;
+            p.precision[o] = 0.0;
+            p.scores[o] = 0.0;
+        }
+        // ---- totals
+        unsigned long long tot = 0;             // tp in the low, fp in the high 32 bits
+        uint32_t nin = 0;
+        for (int i = tid; i < n; i += 256) {
+            const uint32_t w = bits[i];
+            const bool in = rank[i] < md, mt = (w >> t) & 1u, ig = (w >> (16 + t)) & 1u;
+            nin += in ? 1u : 0u;
+            if (in && !ig) tot += mt ? 1ull : (1ull << 32);
+        }
+#pragma unroll
+        for (int s = 32; s > 0; s >>= 1) { tot += __shfl_xor(tot, s, 64); nin += __shfl_xor(nin, s, 64); }
+        __syncthreads();                        // cs is written; the previous round's use of w_* is over
+        if (lane == 0) { w_cnt[wv] = tot; w_in[wv] = nin; }
+        __syncthreads();
+        tot = w_cnt[0] + w_cnt[1] + w_cnt[2] + w_cnt[3];
+        nin = w_in[0] + w_in[1] + w_in[2] + w_in[3];
+        const uint32_t tp_tot = (uint32_t)tot, fp_tot = (uint32_t)(tot >> 32);
+        if (tid == 0) p.recall[o_rec] = nin ? (double)tp_tot / (double)np : 0.0;
+        // ---- from the last row backwards
+        unsigned long long c_cnt = 0;
+        uint32_t c_in = 0;
+        double c_max = -1.0;
+        for (int base = 0; base < n; base += 256) {
+            const int j = base + tid, i = n - 1 - j;
+            bool in = false, tp = false, fp = false;
+            if (j < n) {
+                const uint32_t w = bits[i];
+                const bool mt = (w >> t) & 1u, ig = (w >> (16 + t)) & 1u;
+                in = rank[i] < md;
+                tp = in && !ig && mt;
+                fp = in && !ig && !mt;
+            }
+            unsigned long long sc = tp ? 1ull : (fp ? (1ull << 32) : 0ull);
+            uint32_t si = in ? 1u : 0u;
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) {
+                const unsigned long long oc = __shfl_up(sc, d, 64);
+                const uint32_t oi = __shfl_up(si, d, 64);
+                if (lane >= d) { sc += oc; si += oi; }
+            }
+            __syncthreads();
+            if (lane == 63) { w_cnt[wv] = sc; w_in[wv] = si; }
+            __syncthreads();
+            unsigned long long all_c = 0; uint32_t all_i = 0;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                if (q < wv) { sc += w_cnt[q]; si += w_in[q]; }
+                all_c += w_cnt[q]; all_i += w_in[q];
+            }
+            sc += c_cnt; si += c_in;            // inclusive suffix counts of the row
+            // the row's inclusive prefix counts = totals - the suffix behind it
+            const uint32_t tpc = tp_tot - ((uint32_t)sc - (tp ? 1u : 0u)), fpc = fp_tot - ((uint32_t)(sc >> 32) - (fp ? 1u : 0u));
+            const uint32_t inc = nin - (si - (in ? 1u : 0u));
+            const double tpd = (double)tpc, fpd = (double)fpc;
+            double pm = in ? tpd / (fpd + tpd + 2.220446049250313e-16) : -1.0;
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) {
+                const double o = __shfl_up(pm, d, 64);
+                if (lane >= d) pm = fmax(pm, o);
+            }
+            __syncthreads();
+            if (lane == 63) w_max[wv] = pm;
+            __syncthreads();
+            double all_m = c_max;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                if (q < wv) pm = fmax(pm, w_max[q]);
+                all_m = fmax(all_m, w_max[q]);
+            }
+            pm = fmax(pm, c_max);
+            if (in) {
+                // searchsorted(rc, thr, 'left'): the c-th true positive for the thresholds whose count is c, the first row for count 0
+                for (int pass = 0; pass < 2; ++pass) {
+                    if (pass == 0 ? !tp : inc != 1u) continue;
+                    const int c = pass == 0 ? (int)tpc : 0;
+                    int lo = 0, hi = p.R;
+                    while (lo < hi) { const int mid = (lo + hi) >> 1; if (cs[mid] >= c) hi = mid; else lo = mid + 1; }
+                    for (int r = lo; r < p.R && cs[r] == c; ++r) {
+                        const size_t o = ((((size_t)t * p.R + r) * p.K + k) * p.A + a) * p.M + m;
+                        p.precision[o] = pm;
+                        p.scores[o] = (double)score[i];
+                    }
+                }
+            }
+            c_cnt += all_c; c_in += all_i; c_max = all_m;
+        }
+        __syncthreads();
+    }
+}
+
+// grid (n_stats), 256 threads.  spec [n, 4] = (ap, t or -1: all or -2: none, a, m): the mean of the entries > -1, or -1
+__global__ __launch_bounds__(256) void stats_kernel(const double *__restrict__ precision, const double *__restrict__ recall, int T, int R,
+                                                    int K, int A, int M, const int *__restrict__ spec, double *__restrict__ stats) {
+    __shared__ double w_sum[4];
+    __shared__ uint32_t w_n[4];
+    const int *s = spec + blockIdx.x * 4;
+    const int ap = s[0], ts = s[1], a = s[2], m = s[3], tid = threadIdx.x;
+    const int nt = ts == -1 ? T : (ts >= 0 ? 1 : 0), t0 = ts >= 0 ? ts : 0, nr = ap ? R : 1;
+    const long long total = (long long)nt * nr * K;
+    double sum = 0.0;
+    uint32_t cnt = 0;
+    for (long long i = tid; i < total; i += 256) {
+        const int k = (int)(i % K), r = (int)((i / K) % nr), t = t0 + (int)(i / ((long long)K * nr));
+        const double v = ap ? precision[((((size_t)t * R + r) * K + k) * A + a) * M + m] : recall[(((size_t)t * K + k) * A + a) * M + m];
+        if (v > -1.0) { sum += v; ++cnt; }
+    }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) { sum += __shfl_xor(sum, d, 64); cnt += __shfl_xor(cnt, d, 64); }
+    if ((tid & 63) == 0) { w_sum[tid >> 6] = sum; w_n[tid >> 6] = cnt; }
+    __syncthreads();
+    if (tid == 0) {
+        sum = ((w_sum[0] + w_sum[1]) + (w_sum[2] + w_sum[3]));
+        cnt = w_n[0] + w_n[1] + w_n[2] + w_n[3];
+        stats[blockIdx.x] = cnt ? sum / (double)cnt : -1.0;
+    }
+}
+
+inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+struct AccLayout { size_t perm_a, perm_b, img_a, img_b, hist, seg, s_score, s_rank, s_cat, s_bits, total; int tiles; };
+
+AccLayout acc_layout(int n_images, int D, int K, int A) {
+    AccLayout l;
+    const size_t n = (size_t)n_images * D;
+    l.tiles = (int)((n + kSortTile - 1) / kSortTile);
+    size_t o = 0;
+    auto take = [&](size_t bytes) { const size_t at = o; o += align256(bytes); return at; };
+    l.perm_a = take(n * 4); l.perm_b = take(n * 4);
+    l.img_a = take((size_t)n_images * 4); l.img_b = take((size_t)n_images * 4);
+    l.hist = take((size_t)l.tiles * 256 * 4);
+    l.seg = take((size_t)2 * (K + 1) * 4);
+    l.s_score = take(n * 4); l.s_rank = take(n * 4); l.s_cat = take(n * 4);
+    l.s_bits = take(n * 4 * A);
+    l.total = o;
+    return l;
+}
+
+// one stable pass: src -> dst
+void sort_pass(const uint32_t *src, uint32_t *dst, int n, const SortKey &key, uint32_t *hist, hipStream_t st) {
+    const int tiles = (n + kSortTile - 1) / kSortTile;
+    hipLaunchKernelGGL(sort_hist_kernel, dim3(tiles), dim3(64), 0, st, src, n, key, hist);
+    hipLaunchKernelGGL(sort_scan_kernel, dim3(1), dim3(256), 0, st, hist, tiles);
+    hipLaunchKernelGGL(sort_scatter_kernel, dim3(tiles), dim3(64), 0, st, src, dst, n, key, (const uint32_t *)hist);
+}
+
+}  // namespace
+
+#define CE_CHECK(cond, name) if (!(cond)) { set_error(name ": bad arguments"); return SCDA_EINVAL; }
+
+SCDA_API int scda_coco_det_rows_hip(const float *detections, const int *detection_counts, int B, int top_n,
+                                    const uint32_t *mask_area_or_null, int K, double *dt_xywh, double *dt_area, float *score, int *cat,
+                                    void *stream) {
+    CE_CHECK(detections && detection_counts && dt_xywh && dt_area && score && cat && B > 0 && top_n > 0 && K > 0 &&
+             (long long)B * top_n < 0x7fffffffLL, "scda_coco_det_rows_hip")
+    hipLaunchKernelGGL(det_rows_kernel, dim3(ew_grid((long long)B * top_n)), dim3(256), 0, as_stream(stream), detections,
+                       detection_counts, B, top_n, mask_area_or_null, K, dt_xywh, dt_area, score, cat);
+    return launch_status("det_rows_kernel");
+}
+
+SCDA_API int scda_coco_box_iou_hip(const double *dt, const int *dt_counts, const double *gt, const int *gt_counts,
+                                   const unsigned char *iscrowd, int B, int D, int G, double *iou, void *stream) {
+    CE_CHECK(dt && dt_counts && gt && gt_counts && iscrowd && iou && B > 0 && B <= 65535 && D > 0 && G > 0 && D <= kMaxPer &&
+             G <= kMaxPer, "scda_coco_box_iou_hip")
+    hipLaunchKernelGGL(box_iou_kernel, dim3(cdiv((long long)D * G, 256), B), dim3(256), 0, as_stream(stream), dt, dt_counts, gt,
+                       gt_counts, iscrowd, D, G, iou);
+    return launch_status("box_iou_kernel");
+}
+
+SCDA_API int scda_coco_match_hip(const double *iou, int B, int D, int G, const int *dt_counts, const int *dt_cat, const float *score,
+                                 const double *dt_area, const int *gt_counts, const int *gt_cat, const double *gt_area,
+                                 const unsigned char *gt_iscrowd, int K, const double *iou_thrs, int T, const double *area_rng, int A,
+                                 int max_det, int *rank, uint32_t *bits, int *npig, int *seen, int *dbg_match_or_null, void *stream) {
+    CE_CHECK(iou && dt_counts && dt_cat && score && dt_area && gt_counts && gt_cat && gt_area && gt_iscrowd && iou_thrs && area_rng &&
+             rank && bits && npig && seen, "scda_coco_match_hip")
+    CE_CHECK(B > 0 && B <= 65535 && D > 0 && D <= kMaxPer && G > 0 && G <= kMaxPer && K > 0 && K <= 65535 && T > 0 && T <= kMaxT &&
+             A > 0 && A <= kMaxA && max_det > 0, "scda_coco_match_hip (limits: D, G <= 1024, T <= 16, A <= 8)")
+    const MatchArgs args = {iou, dt_counts, dt_cat, score, dt_area, gt_counts, gt_cat, gt_area, gt_iscrowd, iou_thrs, area_rng,
+                            D, G, K, T, A, max_det, rank, bits, npig, seen, dbg_match_or_null};
+    hipLaunchKernelGGL(match_kernel, dim3(K, B), dim3(kMatchThreads), 0, as_stream(stream), args);
+    return launch_status("match_kernel");
+}
+
+SCDA_API size_t scda_coco_accumulate_workspace_bytes(int n_images, int D, int K, int A) {
+    if (n_images <= 0 || D <= 0 || K <= 0 || A <= 0 || A > kMaxA || (long long)n_images * D >= 0x7fffffffLL) return 0;
+    return acc_layout(n_images, D, K, A).total;
+}
+
+SCDA_API int scda_coco_accumulate_hip(const int *image_ids, int n_images, int D, const int *cat, const int *rank, const float *score,
+                                      const uint32_t *bits, const int *npig, const int *seen, int K, int T, int A,
+                                      const double *rec_thrs, int R, const int *max_dets, int M, int max_det_last, void *ws,
+                                      double *precision, double *recall, double *scores, void *stream) {
+    CE_CHECK(image_ids && cat && rank && score && bits && npig && seen && rec_thrs && max_dets && ws && precision && recall && scores &&
+             (uintptr_t)ws % 16 == 0, "scda_coco_accumulate_hip")
+    CE_CHECK(n_images > 0 && D > 0 && D <= kMaxPer && (long long)n_images * D < 0x7fffffffLL && K > 0 && K <= 255 && T > 0 &&
+             T <= kMaxT && A > 0 && A <= kMaxA && R > 0 && R <= kMaxRec && M > 0 && M <= kMaxM && max_det_last > 0,
+             "scda_coco_accumulate_hip (limits: K <= 255, T <= 16, A <= 8, M <= 4, R <= 128)")
+    const AccLayout l = acc_layout(n_images, D, K, A);
+    char *w8 = (char *)ws;
+    uint32_t *perm_a = (uint32_t *)(w8 + l.perm_a), *perm_b = (uint32_t *)(w8 + l.perm_b);
+    uint32_t *img_a = (uint32_t *)(w8 + l.img_a), *img_b = (uint32_t *)(w8 + l.img_b), *hist = (uint32_t *)(w8 + l.hist);
+    int *seg = (int *)(w8 + l.seg), *s_rank = (int *)(w8 + l.s_rank), *s_cat = (int *)(w8 + l.s_cat);
+    float *s_score = (float *)(w8 + l.s_score);
+    uint32_t *s_bits = (uint32_t *)(w8 + l.s_bits);
+    hipStream_t st = as_stream(stream);
+    const int n = n_images * D;
+    // the images by id, then the rows in (image, slot) order: within an (image, category) equal scores keep the order given, which is
+    // their rank order, so stable passes over the score (descending) and the category finish the reference's order
+    SortKey key = {0, 0, image_ids, score, cat, rank, max_det_last};
+    hipLaunchKernelGGL(iota_kernel, dim3(cdiv(n_images, 256)), dim3(256), 0, st, img_a, n_images);
+    for (int pass = 0; pass < 4; ++pass) {
+        key.shift = 8 * pass;
+        sort_pass(img_a, img_b, n_images, key, hist, st);
+        uint32_t *t = img_a; img_a = img_b; img_b = t;
+    }
+    hipLaunchKernelGGL(rows_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, (const uint32_t *)img_a, D, perm_a, n);
+    key.kind = 1;
+    for (int pass = 0; pass < 4; ++pass) {
+        key.shift = 8 * pass;
+        sort_pass(perm_a, perm_b, n, key, hist, st);
+        uint32_t *t = perm_a; perm_a = perm_b; perm_b = t;
+    }
+    key.kind = 2; key.shift = 0;
+    sort_pass(perm_a, perm_b, n, key, hist, st);
+    hipLaunchKernelGGL(gather_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, (const uint32_t *)perm_b, n, score, cat, rank, bits, A,
+                       max_det_last, s_score, s_rank, s_cat, s_bits);
+    if (hipMemsetAsync(seg, 0, (size_t)2 * (K + 1) * 4, st) != hipSuccess) return launch_status("scda_coco_accumulate_hip (memset)");
+    hipLaunchKernelGGL(segment_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, (const int *)s_cat, n, K, seg);
+    const size_t np_ = (size_t)T * R * K * A * M, nr_ = (size_t)T * K * A * M;
+    hipLaunchKernelGGL(fill_kernel, dim3(ew_grid((long long)np_)), dim3(256), 0, st, precision, np_, -1.0);
+    hipLaunchKernelGGL(fill_kernel, dim3(ew_grid((long long)np_)), dim3(256), 0, st, scores, np_, -1.0);
+    hipLaunchKernelGGL(fill_kernel, dim3(ew_grid((long long)nr_)), dim3(256), 0, st, recall, nr_, -1.0);
+    const PrArgs args = {s_score, s_rank, s_bits, seg, npig, seen, max_dets, rec_thrs, n, K, T, A, M, R, precision, recall, scores};
+    hipLaunchKernelGGL(pr_kernel, dim3(K * A * M), dim3(256), 0, st, args);
+    return launch_status("coco accumulate kernels");
+}
+
+SCDA_API int scda_coco_summarize_hip(const double *precision, const double *recall, int T, int R, int K, int A, int M, const int *spec,
+                                     int n_stats, double *stats, void *stream) {
+    CE_CHECK(precision && recall && spec && stats && T > 0 && R > 0 && K > 0 && A > 0 && M > 0 && n_stats > 0 && n_stats <= 64,
+             "scda_coco_summarize_hip")
+    hipLaunchKernelGGL(stats_kernel, dim3(n_stats), dim3(256), 0, as_stream(stream), precision, recall, T, R, K, A, M, spec, stats);
+    return launch_status("stats_kernel");
+}

@@ -135,3 +135,25 @@ def write_segm_results(writer, image_info, image_ids, out, category_of=None, inp
             writer.write(json.dumps(res) + '\n')
         writer.flush()
     return fallbacks
+
+
+def coco_stats(loader, predictor, evaluator, device=None):
+    """Drives a scda_amd.infer.Predictor over a loader into a scda_amd.coco_eval.CocoEvaluator and returns COCOeval's 12 stats (numpy
+    float64).  Loader items are dicts: 'image' [B, 3, H, W], 'image_info' [B, >= 2], 'image_ids' int32 [B], and the ground truth as
+    CocoEvaluator.add takes it -- 'gt_boxes' float64 [B, Gcap, 4] (x, y, w, h), 'gt_areas', 'gt_iscrowd', 'gt_categories', 'gt_counts',
+    for 'segm' also 'gt_mask_bits' (infer.pack_masks) and optionally 'sizes' -- IN THE COORDINATES OF THE DETECTIONS (the network input:
+    scale the ground truth by resize_scale, nothing is divided here).  Tensors that are on the device already are used as they are; the
+    only wait for the host is the last one.  validate() is not involved."""
+    segm = evaluator.iou_type == 'segm'
+    if segm and not (predictor.masks and predictor.rle):
+        raise ValueError("coco_stats: a 'segm' evaluator needs Predictor(masks=True, rle=True)")
+    device = evaluator.device if device is None else device
+    with torch.no_grad():
+        for item in loader:
+            out = predictor(item['image'].to(device, non_blocking=True), item['image_info'])
+            kw = {}
+            if segm:
+                kw = {'mask_bits': out[4], 'det_areas': out[5]['area'], 'gt_mask_bits': item['gt_mask_bits'], 'sizes': item.get('sizes')}
+            evaluator.add(item['image_ids'], out[2], out[3], item['gt_boxes'], item['gt_areas'], item['gt_iscrowd'], item['gt_categories'],
+                          item['gt_counts'], **kw)
+    return evaluator.summarize()

@@ -33,7 +33,7 @@ def lib():
         _lib.scda_last_error.restype = ctypes.c_char_p
         _lib.scda_nms_workspace_bytes.restype = ctypes.c_size_t
         for f in ("scda_rpn_topk_workspace_bytes", "scda_rpn_proposals_workspace_bytes", "scda_box_predict_workspace_bytes",
-                  "scda_mask_rle_workspace_bytes", "scda_mask_iou_workspace_bytes"):
+                  "scda_mask_rle_workspace_bytes", "scda_mask_iou_workspace_bytes", "scda_coco_accumulate_workspace_bytes"):
             getattr(_lib, f).restype = ctypes.c_size_t
     return _lib
 
@@ -509,10 +509,15 @@ def mask_rle(bits, size=None, image_info=None, rois=None, cap_runs=None, ws=None
     return out
 
 
-def mask_iou(dt_bits, gt_bits, size, iscrowd=None):
+def mask_iou_workspace_bytes(M, N, H, Wd):
+    return int(lib().scda_mask_iou_workspace_bytes(i32(M), i32(N), i32(H), i32(Wd)))
+
+
+def mask_iou(dt_bits, gt_bits, size, iscrowd=None, ws=None, out=None):
     """maskApi.c's rleIou of packed masks on the device: dt_bits int32 [M, H, Wd], gt_bits int32 [N, H, Wd], size = (h, w) of the image
     inside the planes, iscrowd uint8 [N] on the device or None -> (iou float64 [N, M], inter int32 [N, M] holding uint32 counts); the
-    box gate of the reference included (include/scda_ops.h)"""
+    box gate of the reference included (include/scda_ops.h).  ws (uint8, mask_iou_workspace_bytes) / out = (iou, inter): buffers of the
+    caller, so that nothing is allocated."""
     _words(dt_bits, "dt_bits"); _words(gt_bits, "gt_bits")
     M, H, Wd = dt_bits.shape
     N = gt_bits.shape[0]
@@ -528,12 +533,127 @@ def mask_iou(dt_bits, gt_bits, size, iscrowd=None):
     need = int(lib().scda_mask_iou_workspace_bytes(i32(M), i32(N), i32(H), i32(Wd)))
     if need == 0:
         raise ValueError("mask_iou: planes of at most 65535 masks x 65535 rows and fewer than 2^31 pixels")
-    ws = torch.empty(need, dtype=torch.uint8, device=dt_bits.device)
-    iou = torch.empty(N, M, dtype=torch.float64, device=dt_bits.device)
-    inter = torch.empty(N, M, dtype=torch.int32, device=dt_bits.device)
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.uint8, device=dt_bits.device)
+    _req(ws, "ws", torch.uint8)
+    if ws.numel() < need:
+        raise ValueError("mask_iou: workspace too small")
+    if out is None:
+        out = (torch.empty(N, M, dtype=torch.float64, device=dt_bits.device),
+               torch.empty(N, M, dtype=torch.int32, device=dt_bits.device))
+    iou, inter = _req(out[0], "iou", torch.float64), _req(out[1], "inter", torch.int32)
+    if iou.numel() != N * M or inter.numel() != N * M:
+        raise ValueError("mask_iou: out must hold [N, M]")
     _check(lib().scda_mask_iou_hip(_p(dt_bits), i32(M), _p(gt_bits), i32(N), i32(H), i32(Wd), i32(h), i32(w), _p(iscrowd), _p(ws),
                                    _p(iou), _p(inter), _stream()), "scda_mask_iou_hip")
     return iou, inter
+
+
+# ------------------------------------------------- COCO AP (COCOeval) -------
+def coco_det_rows(detections, detection_counts, K, xywh, area, score, cat, mask_area=None):
+    """detections float32 [B, top_n, 7] + detection_counts int32 [B] -> the caller's xywh float64 [B, top_n, 4], area float64, score
+    float32, cat int32 [B, top_n] (include/scda_ops.h: scda_coco_det_rows_hip).  mask_area int32 [B, top_n]: the RLE area, for 'segm'."""
+    _req(detections, "detections"); _req(detection_counts, "detection_counts", torch.int32)
+    if detections.dim() != 3 or detections.shape[2] != 7 or detection_counts.numel() != detections.shape[0]:
+        raise ValueError("coco_det_rows: detections [B, top_n, 7] and detection_counts [B]")
+    B, top_n = detections.shape[:2]
+    for t, name, dt, n in ((xywh, "xywh", torch.float64, 4), (area, "area", torch.float64, 1), (score, "score", torch.float32, 1),
+                           (cat, "cat", torch.int32, 1)):
+        _req(t, name, dt)
+        if t.numel() != B * top_n * n:
+            raise ValueError(f"coco_det_rows: {name} must hold [B, top_n{', 4' if n == 4 else ''}]")
+    if mask_area is not None:
+        _req(mask_area, "mask_area", torch.int32)
+        if mask_area.numel() != B * top_n:
+            raise ValueError("coco_det_rows: mask_area must be [B, top_n]")
+    _check(lib().scda_coco_det_rows_hip(_p(detections), _p(detection_counts), i32(B), i32(top_n), _p(mask_area), i32(int(K)), _p(xywh),
+                                        _p(area), _p(score), _p(cat), _stream()), "scda_coco_det_rows_hip")
+
+
+def coco_box_iou(dt, dt_counts, gt, gt_counts, iscrowd, out=None):
+    """bbIou for B images: dt float64 [B, D, 4], gt float64 [B, G, 4] (x, y, w, h), iscrowd uint8 [B, G], counts int32 [B] -> iou float64
+    [B, G, D] (o[g * D + d] per image), written where d < dt_counts[b] and g < gt_counts[b]; a fresh `out` is zero elsewhere"""
+    _req(dt, "dt", torch.float64); _req(gt, "gt", torch.float64); _req(iscrowd, "iscrowd", torch.uint8)
+    _req(dt_counts, "dt_counts", torch.int32); _req(gt_counts, "gt_counts", torch.int32)
+    if dt.dim() != 3 or gt.dim() != 3 or dt.shape[2] != 4 or gt.shape[2] != 4 or gt.shape[0] != dt.shape[0]:
+        raise ValueError("coco_box_iou: dt [B, D, 4] and gt [B, G, 4]")
+    B, D, G = dt.shape[0], dt.shape[1], gt.shape[1]
+    if iscrowd.numel() != B * G or dt_counts.numel() != B or gt_counts.numel() != B:
+        raise ValueError("coco_box_iou: iscrowd [B, G], counts [B]")
+    if not (1 <= D <= 1024 and 1 <= G <= 1024):
+        raise ValueError("coco_box_iou: 1 <= D, G <= 1024")
+    if out is None:
+        out = torch.zeros(B, G, D, dtype=torch.float64, device=dt.device)
+    _req(out, "out", torch.float64)
+    if out.numel() < B * G * D:
+        raise ValueError("coco_box_iou: out must hold [B, G, D]")
+    _check(lib().scda_coco_box_iou_hip(_p(dt), _p(dt_counts), _p(gt), _p(gt_counts), _p(iscrowd), i32(B), i32(D), i32(G), _p(out),
+                                       _stream()), "scda_coco_box_iou_hip")
+    return out
+
+
+def coco_match(iou, dt_counts, dt_cat, score, dt_area, gt_counts, gt_cat, gt_area, gt_iscrowd, K, iou_thrs, area_rng, max_det, rank, bits,
+               npig, seen, dbg_match=None):
+    """evaluateImg for B images (include/scda_ops.h: scda_coco_match_hip).  iou float64 [B, G, D]; dt_cat int32 / score float32 / dt_area
+    float64 [B, D]; gt_cat int32 / gt_area float64 / gt_iscrowd uint8 [B, G]; iou_thrs float64 [T], area_rng float64 [A, 2] on the device
+    -> rank int32 [B, D], bits int32 [B, D, A], and npig int32 [K, A], seen int32 [K] accumulated.  dbg_match int32 [B, D, A, T] or None."""
+    B, D = dt_cat.shape
+    G = gt_cat.shape[1]
+    T, A = iou_thrs.numel(), area_rng.shape[0]
+    for t, name, dt, n in ((iou, "iou", torch.float64, B * G * D), (dt_counts, "dt_counts", torch.int32, B), (dt_cat, "dt_cat", torch.int32, B * D),
+                           (score, "score", torch.float32, B * D), (dt_area, "dt_area", torch.float64, B * D),
+                           (gt_counts, "gt_counts", torch.int32, B), (gt_cat, "gt_cat", torch.int32, B * G),
+                           (gt_area, "gt_area", torch.float64, B * G), (gt_iscrowd, "gt_iscrowd", torch.uint8, B * G),
+                           (iou_thrs, "iou_thrs", torch.float64, T), (area_rng, "area_rng", torch.float64, 2 * A),
+                           (rank, "rank", torch.int32, B * D), (bits, "bits", torch.int32, B * D * A), (npig, "npig", torch.int32, K * A),
+                           (seen, "seen", torch.int32, K)) + (((dbg_match, "dbg_match", torch.int32, B * D * A * T),) if dbg_match is not None else ()):
+        _req(t, name, dt)
+        if t.numel() < n:
+            raise ValueError(f"coco_match: {name} holds {t.numel()} elements, {n} needed")
+    _check(lib().scda_coco_match_hip(_p(iou), i32(B), i32(D), i32(G), _p(dt_counts), _p(dt_cat), _p(score), _p(dt_area), _p(gt_counts),
+                                     _p(gt_cat), _p(gt_area), _p(gt_iscrowd), i32(int(K)), _p(iou_thrs), i32(T), _p(area_rng), i32(A),
+                                     i32(int(max_det)), _p(rank), _p(bits), _p(npig), _p(seen), _p(dbg_match), _stream()),
+           "scda_coco_match_hip")
+
+
+def coco_accumulate_workspace_bytes(n_images, D, K, A):
+    return int(lib().scda_coco_accumulate_workspace_bytes(i32(n_images), i32(D), i32(K), i32(A)))
+
+
+def coco_accumulate(image_ids, n_images, cat, rank, score, bits, npig, seen, rec_thrs, max_dets, max_det_last, T, ws, precision, recall,
+                    scores):
+    """accumulate over the first n_images images' rows (include/scda_ops.h: scda_coco_accumulate_hip); every tensor is the caller's"""
+    D = cat.shape[1]
+    K, A = npig.shape
+    R, M = rec_thrs.numel(), max_dets.numel()
+    for t, name, dt, n in ((image_ids, "image_ids", torch.int32, n_images), (cat, "cat", torch.int32, n_images * D),
+                           (rank, "rank", torch.int32, n_images * D), (score, "score", torch.float32, n_images * D),
+                           (bits, "bits", torch.int32, n_images * D * A), (npig, "npig", torch.int32, K * A), (seen, "seen", torch.int32, K),
+                           (rec_thrs, "rec_thrs", torch.float64, R), (max_dets, "max_dets", torch.int32, M),
+                           (precision, "precision", torch.float64, T * R * K * A * M), (recall, "recall", torch.float64, T * K * A * M),
+                           (scores, "scores", torch.float64, T * R * K * A * M), (ws, "ws", torch.uint8, 1)):
+        _req(t, name, dt)
+        if t.numel() < n:
+            raise ValueError(f"coco_accumulate: {name} holds {t.numel()} elements, {n} needed")
+    need = coco_accumulate_workspace_bytes(n_images, D, K, A)
+    if need == 0 or ws.numel() < need:
+        raise ValueError("coco_accumulate: workspace too small or sizes out of range")
+    _check(lib().scda_coco_accumulate_hip(_p(image_ids), i32(n_images), i32(D), _p(cat), _p(rank), _p(score), _p(bits), _p(npig), _p(seen),
+                                          i32(K), i32(T), i32(A), _p(rec_thrs), i32(R), _p(max_dets), i32(M), i32(int(max_det_last)),
+                                          _p(ws), _p(precision), _p(recall), _p(scores), _stream()), "scda_coco_accumulate_hip")
+
+
+def coco_summarize(precision, recall, shape, spec, stats):
+    """_summarizeDets on the device: shape = (T, R, K, A, M), spec int32 [n, 4] = (ap, t, a, m) -> stats float64 [n]"""
+    _req(precision, "precision", torch.float64); _req(recall, "recall", torch.float64)
+    _req(spec, "spec", torch.int32); _req(stats, "stats", torch.float64)
+    T, R, K, A, M = (int(v) for v in shape)
+    n = spec.shape[0]
+    if precision.numel() != T * R * K * A * M or recall.numel() != T * K * A * M or spec.numel() != 4 * n or stats.numel() < n:
+        raise ValueError("coco_summarize: precision [T, R, K, A, M], recall [T, K, A, M], spec [n, 4], stats [n]")
+    _check(lib().scda_coco_summarize_hip(_p(precision), _p(recall), i32(T), i32(R), i32(K), i32(A), i32(M), _p(spec), i32(n), _p(stats),
+                                         _stream()), "scda_coco_summarize_hip")
+    return stats
 
 
 # ------------------------------------------------- convolution / GEMM -------
