@@ -1,5 +1,9 @@
 """ctypes binding of libscda_ops.so (C ABI declared in include/scda_ops.h).
 
+lib() reads that header when it loads the library and sets `argtypes` / `restype` of every declared function from its declaration:
+the signatures are stated once, in the header, and a call site passes plain Python values (ctypes converts them to the declared C
+types and raises on a missing argument or a value of the wrong kind).
+
 Every wrapper takes torch CUDA tensors, checks device/dtype/contiguity, passes
 raw device pointers + sizes + the current HIP stream, and raises on a non-zero
 status.  There is no CPU fallback: operators raise if the library or a HIP
@@ -7,12 +11,14 @@ device is missing.
 """
 import ctypes
 import os
+import re
 import weakref
 
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SCDA_OPS_LIB") or os.path.join(_HERE, "libscda_ops.so")   # (the env override: A/B builds of the library)
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "scda_ops.h")            # always this checkout's
 
 _lib = None
 
@@ -21,20 +27,54 @@ class ScdaNativeError(RuntimeError):
     pass
 
 
+# the header's whole type vocabulary; every pointer or array parameter is a c_void_p (an int address, None, a ctypes array or byref())
+C_SCALARS = {"int": ctypes.c_int, "unsigned": ctypes.c_uint, "float": ctypes.c_float, "double": ctypes.c_double,
+             "long long": ctypes.c_longlong, "size_t": ctypes.c_size_t, "uint64_t": ctypes.c_uint64}
+C_RETURNS = dict(C_SCALARS, **{"void": None, "const char *": ctypes.c_char_p})
+
+
+def parse_header(text):
+    """{function name: (restype, [argtypes])} of the declarations in the text of a plain-C header"""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r'^\s*#.*$|extern\s*"C"\s*\{|\}', " ", text, flags=re.M)
+    sigs = {}
+    for decl in (" ".join(d.split()) for d in text.split(";")):
+        if not decl:
+            continue
+        m = re.fullmatch(r"(.+?)\b(\w+) ?\(([^()]*)\)", decl)
+        if not m or m.group(1).strip() not in C_RETURNS:
+            raise ScdaNativeError(f"cannot bind the declaration `{decl}`: not `<{' | '.join(C_RETURNS)}> name(parameters)`")
+        argtypes = []
+        for param in ([] if m.group(3).strip() == "void" else m.group(3).split(",")):
+            ctype = " ".join(w for w in param.split()[:-1] if w != "const")      # the last word is the parameter's name
+            if "*" in param or param.rstrip().endswith("]"):
+                argtypes.append(ctypes.c_void_p)
+            elif ctype in C_SCALARS:
+                argtypes.append(C_SCALARS[ctype])
+            else:
+                raise ScdaNativeError(f"cannot bind the declaration `{decl}`: parameter `{param.strip()}` has no type in {sorted(C_SCALARS)}")
+        sigs[m.group(2)] = (C_RETURNS[m.group(1).strip()], argtypes)
+    return sigs
+
+
 def lib():
-    """Load libscda_ops.so once; fail loudly if it has not been built."""
+    """Load libscda_ops.so once and type every function include/scda_ops.h declares; fail loudly if either is missing."""
     global _lib
     if _lib is None:
         if not os.path.exists(LIB_PATH):
             raise ScdaNativeError(
                 f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "or `make -C scda_amd/csrc` (no CPU fallback exists)")
-        _lib = ctypes.CDLL(LIB_PATH)
-        _lib.scda_last_error.restype = ctypes.c_char_p
-        _lib.scda_nms_workspace_bytes.restype = ctypes.c_size_t
-        for f in ("scda_rpn_topk_workspace_bytes", "scda_rpn_proposals_workspace_bytes", "scda_box_predict_workspace_bytes",
-                  "scda_mask_rle_workspace_bytes", "scda_mask_iou_workspace_bytes", "scda_coco_accumulate_workspace_bytes"):
-            getattr(_lib, f).restype = ctypes.c_size_t
+        if not os.path.exists(HEADER_PATH):
+            raise ScdaNativeError(f"{HEADER_PATH} not found: the binding takes every signature of {LIB_PATH} from it")
+        cdll = ctypes.CDLL(LIB_PATH)
+        with open(HEADER_PATH) as f:
+            sigs = parse_header(f.read())
+        for name, (restype, argtypes) in sigs.items():
+            fn = getattr(cdll, name, None)      # a symbol the library lacks raises AttributeError where it is used (tests/test_abi.py lists them)
+            if fn is not None:
+                fn.restype, fn.argtypes = restype, argtypes
+        _lib = cdll
     return _lib
 
 
@@ -48,14 +88,14 @@ _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 
 
 def _stream():
-    """current HIP stream of the current device as void* (one C call; this runs once per kernel launch)"""
+    """current HIP stream of the current device as an address (one C call; this runs once per kernel launch)"""
     if _raw_stream is not None:
-        return ctypes.c_void_p(_raw_stream(torch.cuda.current_device()))
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        return _raw_stream(torch.cuda.current_device())
+    return torch.cuda.current_stream().cuda_stream
 
 
 def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
+    return t.data_ptr() if t is not None else None
 
 
 def _req(t, name, dtype=torch.float32):
@@ -70,10 +110,6 @@ def _req(t, name, dtype=torch.float32):
     return t
 
 
-f32 = ctypes.c_float
-i32 = ctypes.c_int
-
-
 # ----------------------------------------------------------------- NMS ------
 def nms(boxes, thresh, max_keep=0):
     """boxes [n,5] fp32 CUDA, sorted by score desc -> (keep int64[n] CUDA, num_out int64[1] CUDA)."""
@@ -81,9 +117,8 @@ def nms(boxes, thresh, max_keep=0):
     n = boxes.shape[0]
     keep = torch.empty(max(n, 1), dtype=torch.int64, device=boxes.device)
     num = torch.zeros(1, dtype=torch.int64, device=boxes.device)
-    ws = torch.empty(max(lib().scda_nms_workspace_bytes(i32(n)), 8), dtype=torch.uint8, device=boxes.device)
-    _check(lib().scda_nms_hip(_p(boxes), i32(n), f32(thresh), _p(ws), _p(keep), _p(num), i32(max_keep), _stream()),
-           "scda_nms_hip")
+    ws = torch.empty(max(lib().scda_nms_workspace_bytes(n), 8), dtype=torch.uint8, device=boxes.device)
+    _check(lib().scda_nms_hip(_p(boxes), n, thresh, _p(ws), _p(keep), _p(num), max_keep, _stream()), "scda_nms_hip")
     return keep, num
 
 
@@ -96,8 +131,7 @@ def nms_segments(boxes, seg, max_n, thresh):
     num = torch.zeros(max(S, 1), dtype=torch.int64, device=boxes.device)
     words = S * max_n * ((max_n + 63) // 64)                  # upper bound of the lists' mask words
     ws = torch.empty(max(words, 1), dtype=torch.int64, device=boxes.device)
-    _check(lib().scda_nms_segments_hip(_p(boxes), _p(seg), i32(S), i32(max_n), f32(thresh), _p(ws), _p(keep), _p(num), _stream()),
-           "scda_nms_segments_hip")
+    _check(lib().scda_nms_segments_hip(_p(boxes), _p(seg), S, max_n, thresh, _p(ws), _p(keep), _p(num), _stream()), "scda_nms_segments_hip")
     return keep, num
 
 
@@ -106,7 +140,7 @@ def nms_mask(boxes, thresh):
     n = boxes.shape[0]
     cb = (n + 63) // 64
     mask = torch.zeros(n, cb, dtype=torch.int64, device=boxes.device)
-    _check(lib().scda_nms_mask_hip(_p(boxes), i32(n), f32(thresh), _p(mask), _stream()), "scda_nms_mask_hip")
+    _check(lib().scda_nms_mask_hip(_p(boxes), n, thresh, _p(mask), _stream()), "scda_nms_mask_hip")
     return mask
 
 
@@ -121,8 +155,8 @@ def roi_pool_fwd(features, rois, ph, pw, scale, want_argmax=True):
     R = rois.shape[0]
     out = torch.empty(R, C, ph, pw, dtype=torch.float32, device=features.device)
     arg = torch.empty(R, C, ph, pw, dtype=torch.int32, device=features.device) if want_argmax else None
-    _check(lib().scda_roi_pool_fwd_hip(_p(features), _p(rois), i32(R), i32(B), i32(C), i32(H), i32(W), i32(ph), i32(pw),
-                                       f32(scale), _p(out), _p(arg), _stream()), "scda_roi_pool_fwd_hip")
+    _check(lib().scda_roi_pool_fwd_hip(_p(features), _p(rois), R, B, C, H, W, ph, pw, scale, _p(out), _p(arg), _stream()),
+           "scda_roi_pool_fwd_hip")
     return out, arg
 
 
@@ -131,8 +165,8 @@ def roi_pool_bwd(top_grad, argmax, rois, feat_shape, ph, pw, scale):
     B, C, H, W = feat_shape
     R = rois.shape[0]
     gi = torch.empty(B, C, H, W, dtype=torch.float32, device=top_grad.device)
-    _check(lib().scda_roi_pool_bwd_hip(_p(top_grad), _p(argmax), _p(rois), i32(R), i32(B), i32(C), i32(H), i32(W),
-                                       i32(ph), i32(pw), f32(scale), _p(gi), _stream()), "scda_roi_pool_bwd_hip")
+    _check(lib().scda_roi_pool_bwd_hip(_p(top_grad), _p(argmax), _p(rois), R, B, C, H, W, ph, pw, scale, _p(gi), _stream()),
+           "scda_roi_pool_bwd_hip")
     return gi
 
 
@@ -146,8 +180,7 @@ def roi_align_fwd(features, rois, ah, aw, scale, channel_major=False):
     R = rois.shape[0]
     out = torch.empty((C, R, ah, aw) if channel_major else (R, C, ah, aw), dtype=torch.float32, device=features.device)
     fn = lib().scda_roi_align_cmajor_fwd_hip if channel_major else lib().scda_roi_align_fwd_hip
-    _check(fn(_p(features), _p(rois), i32(R), i32(B), i32(C), i32(H), i32(W), i32(ah), i32(aw), f32(scale), _p(out), _stream()),
-           "scda_roi_align_fwd_hip")
+    _check(fn(_p(features), _p(rois), R, B, C, H, W, ah, aw, scale, _p(out), _stream()), "scda_roi_align_fwd_hip")
     return out
 
 
@@ -156,8 +189,7 @@ def roi_align_bwd(top_grad, rois, feat_shape, ah, aw, scale, channel_major=False
     B, C, H, W = feat_shape
     gi = torch.zeros(B, C, H, W, dtype=torch.float32, device=top_grad.device)
     fn = lib().scda_roi_align_cmajor_bwd_hip if channel_major else lib().scda_roi_align_bwd_hip
-    _check(fn(_p(top_grad), _p(rois), i32(rois.shape[0]), i32(B), i32(C), i32(H), i32(W), i32(ah), i32(aw), f32(scale), _p(gi),
-              _stream()), "scda_roi_align_bwd_hip")
+    _check(fn(_p(top_grad), _p(rois), rois.shape[0], B, C, H, W, ah, aw, scale, _p(gi), _stream()), "scda_roi_align_bwd_hip")
     return gi
 
 
@@ -165,18 +197,16 @@ def roi_align_bwd(top_grad, rois, feat_shape, ah, aw, scale, channel_major=False
 def focal_sigmoid_fwd(logits, targets, weight_pos, gamma, alpha, num_classes):
     _req(logits, "logits"); _req(targets, "targets", torch.int32)
     losses = torch.empty_like(logits)
-    _check(lib().scda_focal_sigmoid_fwd_hip(i32(logits.numel()), _p(logits), _p(targets), f32(weight_pos), f32(gamma),
-                                            f32(alpha), i32(num_classes), _p(losses), _stream()),
-           "scda_focal_sigmoid_fwd_hip")
+    _check(lib().scda_focal_sigmoid_fwd_hip(logits.numel(), _p(logits), _p(targets), weight_pos, gamma, alpha, num_classes, _p(losses),
+                                            _stream()), "scda_focal_sigmoid_fwd_hip")
     return losses
 
 
 def focal_sigmoid_bwd(logits, targets, weight_pos, gamma, alpha, num_classes):
     _req(logits, "logits"); _req(targets, "targets", torch.int32)
     dx = torch.empty_like(logits)
-    _check(lib().scda_focal_sigmoid_bwd_hip(i32(logits.numel()), _p(logits), _p(targets), _p(dx), f32(weight_pos),
-                                            f32(gamma), f32(alpha), i32(num_classes), _stream()),
-           "scda_focal_sigmoid_bwd_hip")
+    _check(lib().scda_focal_sigmoid_bwd_hip(logits.numel(), _p(logits), _p(targets), _p(dx), weight_pos, gamma, alpha, num_classes,
+                                            _stream()), "scda_focal_sigmoid_bwd_hip")
     return dx
 
 
@@ -185,9 +215,8 @@ def focal_softmax_fwd(logits, targets, weight_pos, gamma, alpha, num_classes):
     rows = logits.numel() // num_classes
     losses = torch.empty(rows, dtype=torch.float32, device=logits.device)
     priors = torch.empty_like(logits)
-    _check(lib().scda_focal_softmax_fwd_hip(i32(logits.numel()), _p(logits), _p(targets), f32(weight_pos), f32(gamma),
-                                            f32(alpha), i32(num_classes), _p(losses), _p(priors), _stream()),
-           "scda_focal_softmax_fwd_hip")
+    _check(lib().scda_focal_softmax_fwd_hip(logits.numel(), _p(logits), _p(targets), weight_pos, gamma, alpha, num_classes, _p(losses),
+                                            _p(priors), _stream()), "scda_focal_softmax_fwd_hip")
     return losses, priors
 
 
@@ -196,9 +225,8 @@ def focal_softmax_bwd(logits, targets, priors, weight_pos, gamma, alpha, num_cla
     rows = logits.numel() // num_classes
     dx = torch.empty_like(logits)
     buff = torch.empty(rows, dtype=torch.float32, device=logits.device)
-    _check(lib().scda_focal_softmax_bwd_hip(i32(logits.numel()), _p(logits), _p(targets), _p(dx), f32(weight_pos),
-                                            f32(gamma), f32(alpha), i32(num_classes), _p(priors), _p(buff), _stream()),
-           "scda_focal_softmax_bwd_hip")
+    _check(lib().scda_focal_softmax_bwd_hip(logits.numel(), _p(logits), _p(targets), _p(dx), weight_pos, gamma, alpha, num_classes,
+                                            _p(priors), _p(buff), _stream()), "scda_focal_softmax_bwd_hip")
     return dx
 
 
@@ -208,8 +236,7 @@ def iou_overlaps(b1, b2):
     if b1.shape[1] != b2.shape[1]:
         raise ValueError("box widths differ")
     out = torch.empty(b1.shape[0], b2.shape[0], dtype=torch.float32, device=b1.device)
-    _check(lib().scda_iou_overlaps_hip(_p(b1), _p(b2), i32(b1.shape[1]), i32(b1.shape[0]), i32(b2.shape[0]), _p(out),
-                                       _stream()), "scda_iou_overlaps_hip")
+    _check(lib().scda_iou_overlaps_hip(_p(b1), _p(b2), b1.shape[1], b1.shape[0], b2.shape[0], _p(out), _stream()), "scda_iou_overlaps_hip")
     return out
 
 
@@ -218,8 +245,7 @@ def bbox_overlaps(boxes, query):
     if boxes.shape[1] != 4 or query.shape[1] != 4:
         raise ValueError("bbox_overlaps takes [N,4] and [K,4]")
     out = torch.empty(boxes.shape[0], query.shape[0], dtype=torch.float32, device=boxes.device)
-    _check(lib().scda_bbox_overlaps_hip(_p(boxes), i32(boxes.shape[0]), _p(query), i32(query.shape[0]), _p(out),
-                                        _stream()), "scda_bbox_overlaps_hip")
+    _check(lib().scda_bbox_overlaps_hip(_p(boxes), boxes.shape[0], _p(query), query.shape[0], _p(out), _stream()), "scda_bbox_overlaps_hip")
     return out
 
 
@@ -228,10 +254,9 @@ def anchor_label(anchors32, gts, neg_thresh, pos_thresh, min_gt_best, bufs):
     """bufs: dict of caller-owned device buffers (best_iou, best_gt, gt_best, labels, pos_list, neg_list, counts)"""
     _req(anchors32, "anchors"); _req(gts, "gts")
     KA, G = anchors32.shape[0], gts.shape[0]
-    _check(lib().scda_anchor_label_hip(_p(anchors32), i32(KA), _p(gts), i32(G), i32(gts.shape[1]), f32(neg_thresh), f32(pos_thresh),
-                                       f32(min_gt_best), _p(bufs["best_iou"]), _p(bufs["best_gt"]), _p(bufs["gt_best"]),
-                                       _p(bufs["labels"]), _p(bufs["pos_list"]), _p(bufs["neg_list"]), _p(bufs["counts"]), _stream()),
-           "scda_anchor_label_hip")
+    _check(lib().scda_anchor_label_hip(_p(anchors32), KA, _p(gts), G, gts.shape[1], neg_thresh, pos_thresh, min_gt_best,
+                                       _p(bufs["best_iou"]), _p(bufs["best_gt"]), _p(bufs["gt_best"]), _p(bufs["labels"]),
+                                       _p(bufs["pos_list"]), _p(bufs["neg_list"]), _p(bufs["counts"]), _stream()), "scda_anchor_label_hip")
 
 
 def anchor_finalize(bufs, drop_pos, drop_neg, anchors64, gts, A, fh, fw):
@@ -241,10 +266,9 @@ def anchor_finalize(bufs, drop_pos, drop_neg, anchors64, gts, A, fh, fw):
     loc_t = torch.empty(1, 4 * A, fh, fw, dtype=torch.float32, device=dev)
     loc_m = torch.empty(1, 4 * A, fh, fw, dtype=torch.float32, device=dev)
     _check(lib().scda_anchor_finalize_hip(_p(bufs["labels"]), _p(bufs["best_gt"]), _p(bufs["pos_list"]), _p(drop_pos),
-                                          i32(0 if drop_pos is None else drop_pos.numel()), _p(bufs["neg_list"]), _p(drop_neg),
-                                          i32(0 if drop_neg is None else drop_neg.numel()), _p(anchors64), _p(gts), i32(gts.shape[1]),
-                                          i32(A), i32(fh), i32(fw), _p(cls_t), _p(loc_t), _p(loc_m), _stream()),
-           "scda_anchor_finalize_hip")
+                                          0 if drop_pos is None else drop_pos.numel(), _p(bufs["neg_list"]), _p(drop_neg),
+                                          0 if drop_neg is None else drop_neg.numel(), _p(anchors64), _p(gts), gts.shape[1], A, fh, fw,
+                                          _p(cls_t), _p(loc_t), _p(loc_m), _stream()), "scda_anchor_finalize_hip")
     return cls_t, loc_t, loc_m
 
 
@@ -252,10 +276,10 @@ def proposal_match(props, gts, img_h, img_w, pos_thresh, neg_hi, neg_lo, bufs):
     """props [n,>=5] fp32 rows (b,x1,y1,x2,y2,..), gts [G,>=5]; bufs: caller-owned device buffers rois [n+G,4], best_iou, best_gt,
     labels, pos_list, neg_list [n+G], counts [2] (scda_proposal_match_hip)"""
     _req(props, "props"); _req(gts, "gts")
-    _check(lib().scda_proposal_match_hip(_p(props), i32(props.shape[0]), i32(props.shape[1]), _p(gts), i32(gts.shape[0]), i32(gts.shape[1]),
-                                         f32(img_h), f32(img_w), f32(pos_thresh), f32(neg_hi), f32(neg_lo), _p(bufs["rois"]),
-                                         _p(bufs["best_iou"]), _p(bufs["best_gt"]), _p(bufs["labels"]), _p(bufs["pos_list"]),
-                                         _p(bufs["neg_list"]), _p(bufs["counts"]), _stream()), "scda_proposal_match_hip")
+    _check(lib().scda_proposal_match_hip(_p(props), props.shape[0], props.shape[1], _p(gts), gts.shape[0], gts.shape[1], img_h, img_w,
+                                         pos_thresh, neg_hi, neg_lo, _p(bufs["rois"]), _p(bufs["best_iou"]), _p(bufs["best_gt"]),
+                                         _p(bufs["labels"]), _p(bufs["pos_list"]), _p(bufs["neg_list"]), _p(bufs["counts"]), _stream()),
+           "scda_proposal_match_hip")
 
 
 def proposal_finalize(cand_rois, sel, gt_of, enc, gts, num_classes, image_index):
@@ -266,9 +290,8 @@ def proposal_finalize(cand_rois, sel, gt_of, enc, gts, num_classes, image_index)
     labels = torch.empty(R, dtype=torch.int64, device=dev)
     t = torch.empty(R, 4 * num_classes, dtype=torch.float32, device=dev)
     w = torch.empty(R, 4 * num_classes, dtype=torch.float32, device=dev)
-    _check(lib().scda_proposal_finalize_hip(_p(cand_rois), _p(sel), _p(gt_of), _p(enc), _p(gts), i32(gts.shape[1]), i32(R),
-                                            i32(num_classes), f32(image_index), _p(rois), _p(labels), _p(t), _p(w), _stream()),
-           "scda_proposal_finalize_hip")
+    _check(lib().scda_proposal_finalize_hip(_p(cand_rois), _p(sel), _p(gt_of), _p(enc), _p(gts), gts.shape[1], R, num_classes, image_index,
+                                            _p(rois), _p(labels), _p(t), _p(w), _stream()), "scda_proposal_finalize_hip")
     return rois, labels, t, w
 
 
@@ -286,15 +309,12 @@ def proposals_from_ranking(order, exp_wh, anchors64, loc, prob, A, fh, fw, img_h
     props = torch.empty(n, 5, dtype=torch.float32, device=dev)
     ok = torch.empty(n, dtype=torch.uint8, device=dev)
     L = lib()
-    _check(L.scda_proposal_decode_hip(_p(order), _p(exp_wh), i32(n), _p(anchors64), _p(loc), _p(prob), i32(A), i32(fh), i32(fw),
-                                      ctypes.c_double(img_h), ctypes.c_double(img_w), ctypes.c_double(min_size), _p(props), _p(ok),
-                                      _stream()), "scda_proposal_decode_hip")
+    _check(L.scda_proposal_decode_hip(_p(order), _p(exp_wh), n, _p(anchors64), _p(loc), _p(prob), A, fh, fw, img_h, img_w, min_size,
+                                      _p(props), _p(ok), _stream()), "scda_proposal_decode_hip")
     keep = torch.empty(n, dtype=torch.int64, device=dev)
-    ws = torch.empty(max(L.scda_nms_workspace_bytes(i32(n)), 8), dtype=torch.uint8, device=dev)
-    _check(L.scda_nms_valid_hip(_p(props), _p(ok), i32(n), f32(nms_thresh), _p(ws), _p(keep), _p(num), i32(max_keep), _stream()),
-           "scda_nms_valid_hip")
-    _check(L.scda_proposal_gather_hip(_p(props), _p(keep), _p(num), f32(image_index), i32(rows), _p(out6), _stream()),
-           "scda_proposal_gather_hip")
+    ws = torch.empty(max(L.scda_nms_workspace_bytes(n), 8), dtype=torch.uint8, device=dev)
+    _check(L.scda_nms_valid_hip(_p(props), _p(ok), n, nms_thresh, _p(ws), _p(keep), _p(num), max_keep, _stream()), "scda_nms_valid_hip")
+    _check(L.scda_proposal_gather_hip(_p(props), _p(keep), _p(num), image_index, rows, _p(out6), _stream()), "scda_proposal_gather_hip")
     return out6, num
 
 
@@ -312,13 +332,13 @@ def rpn_topk(prob, top_n, order=None, ws=None):
         order = torch.empty(B, n, dtype=torch.int32, device=prob.device)
     _req(order, "order", torch.int32)
     if ws is None:
-        ws = torch.empty(max(L.scda_rpn_topk_workspace_bytes(i32(B), i32(KA), i32(top_n)), 8), dtype=torch.uint8, device=prob.device)
-    _check(L.scda_rpn_topk_hip(_p(prob), i32(B), i32(A), i32(fh), i32(fw), i32(top_n), _p(order), _p(ws), _stream()), "scda_rpn_topk_hip")
+        ws = torch.empty(max(L.scda_rpn_topk_workspace_bytes(B, KA, top_n), 8), dtype=torch.uint8, device=prob.device)
+    _check(L.scda_rpn_topk_hip(_p(prob), B, A, fh, fw, top_n, _p(order), _p(ws), _stream()), "scda_rpn_topk_hip")
     return order
 
 
 def rpn_proposals_workspace_bytes(B, A, fh, fw, top_n):
-    return int(lib().scda_rpn_proposals_workspace_bytes(i32(B), i32(A), i32(fh), i32(fw), i32(top_n)))
+    return int(lib().scda_rpn_proposals_workspace_bytes(B, A, fh, fw, top_n))
 
 
 def rpn_proposals_batched(prob, loc, anchors64, image_info, pre_nms_top_n, min_size, nms_thresh, post_nms_top_n, ws, rois5, props6,
@@ -334,14 +354,14 @@ def rpn_proposals_batched(prob, loc, anchors64, image_info, pre_nms_top_n, min_s
         raise ValueError("rpn_proposals_batched: inconsistent shapes")
     if ws.numel() < rpn_proposals_workspace_bytes(B, A, fh, fw, pre_nms_top_n):
         raise ValueError("rpn_proposals_batched: workspace too small")
-    _check(lib().scda_rpn_proposals_hip(_p(prob), _p(loc), _p(anchors64), i32(B), i32(A), i32(fh), i32(fw), _p(image_info),
-                                        i32(image_info.shape[1]), i32(pre_nms_top_n), ctypes.c_double(min_size), f32(nms_thresh),
-                                        i32(P), _p(ws), _p(rois5), _p(props6), _p(counts), _stream()), "scda_rpn_proposals_hip")
+    _check(lib().scda_rpn_proposals_hip(_p(prob), _p(loc), _p(anchors64), B, A, fh, fw, _p(image_info), image_info.shape[1], pre_nms_top_n,
+                                        min_size, nms_thresh, P, _p(ws), _p(rois5), _p(props6), _p(counts), _stream()),
+           "scda_rpn_proposals_hip")
     return rois5, props6, counts
 
 
 def box_predict_workspace_bytes(B, P, C):
-    return int(lib().scda_box_predict_workspace_bytes(i32(B), i32(P), i32(C)))
+    return int(lib().scda_box_predict_workspace_bytes(B, P, C))
 
 
 def box_predict(rois, roi_counts, prob, loc, image_info, stds, means, score_thresh, nms_thresh, top_n, ws, det, det_counts):
@@ -357,9 +377,8 @@ def box_predict(rois, roi_counts, prob, loc, image_info, stds, means, score_thre
     if ws.numel() < box_predict_workspace_bytes(B, P, C):
         raise ValueError("box_predict: workspace too small")
     s4, m4 = (ctypes.c_double * 4)(*[float(v) for v in stds]), (ctypes.c_double * 4)(*[float(v) for v in means])
-    _check(lib().scda_box_predict_hip(_p(rois), _p(roi_counts), i32(B), i32(P), _p(prob), _p(loc), i32(C), _p(image_info),
-                                      i32(image_info.shape[1]), s4, m4, f32(score_thresh), f32(nms_thresh), i32(top_n), _p(ws),
-                                      _p(det), _p(det_counts), _stream()), "scda_box_predict_hip")
+    _check(lib().scda_box_predict_hip(_p(rois), _p(roi_counts), B, P, _p(prob), _p(loc), C, _p(image_info), image_info.shape[1], s4, m4,
+                                      score_thresh, nms_thresh, top_n, _p(ws), _p(det), _p(det_counts), _stream()), "scda_box_predict_hip")
     return det, det_counts
 
 
@@ -378,7 +397,7 @@ def det_rois(det, det_counts, rois5=None, cls=None):
     _req(rois5, "rois5"); _req(cls, "cls", torch.int32)
     if rois5.shape != (B * top_n, 5) or cls.numel() != B * top_n:
         raise ValueError("det_rois: inconsistent shapes")
-    _check(lib().scda_det_rois_hip(_p(det), _p(det_counts), i32(B), i32(top_n), _p(rois5), _p(cls), _stream()), "scda_det_rois_hip")
+    _check(lib().scda_det_rois_hip(_p(det), _p(det_counts), B, top_n, _p(rois5), _p(cls), _stream()), "scda_det_rois_hip")
     return rois5, cls
 
 
@@ -398,9 +417,9 @@ def mask_select(logits, cls, sigmoid=False, out=None):
     _req(out, "out")
     if out.shape != (R, h, w):
         raise ValueError("mask_select: out must be [R, h, w]")
-    sr, sc, sh, sw = (ctypes.c_longlong(v) for v in logits.stride())
-    _check(lib().scda_mask_select_hip(_p(logits), sr, sc, sh, sw, _p(cls), i32(R), i32(C), i32(h), i32(w), i32(1 if sigmoid else 0),
-                                      _p(out), _stream()), "scda_mask_select_hip")
+    sr, sc, sh, sw = logits.stride()
+    _check(lib().scda_mask_select_hip(_p(logits), sr, sc, sh, sw, _p(cls), R, C, h, w, 1 if sigmoid else 0, _p(out), _stream()),
+           "scda_mask_select_hip")
     return out
 
 
@@ -428,19 +447,19 @@ def mask_paste(rois, planes, H, W, cls=None, packed=False, threshold=0.5, out=No
     _req(out, "out", dtype)
     if tuple(out.shape) != shape:
         raise ValueError("mask_paste: out must be %s" % (shape,))
-    _check(lib().scda_mask_paste_hip(_p(rois), i32(rois.shape[1]), _p(cls), _p(planes), i32(R), i32(h), i32(w), i32(H), i32(W),
-                                     i32(1 if packed else 0), f32(threshold), _p(out), _stream()), "scda_mask_paste_hip")
+    _check(lib().scda_mask_paste_hip(_p(rois), rois.shape[1], _p(cls), _p(planes), R, h, w, H, W, 1 if packed else 0, threshold, _p(out),
+                                     _stream()), "scda_mask_paste_hip")
     return out
 
 
 # ------------------------------------------------- COCO run-length results ---
 def mask_rle_max_chars(h, w):
     """characters one count of an h x w plane can take in the 6-bit string: ceil((bitlength(h * w) + 1) / 5)"""
-    return int(lib().scda_mask_rle_max_chars(i32(int(h)), i32(int(w))))
+    return int(lib().scda_mask_rle_max_chars(int(h), int(w)))
 
 
 def mask_rle_workspace_bytes(R, H, Wd, cap_runs):
-    return int(lib().scda_mask_rle_workspace_bytes(i32(R), i32(H), i32(Wd), i32(cap_runs)))
+    return int(lib().scda_mask_rle_workspace_bytes(R, H, Wd, cap_runs))
 
 
 def _words(t, name):
@@ -502,15 +521,14 @@ def mask_rle(bits, size=None, image_info=None, rois=None, cap_runs=None, ws=None
         _req(out[k], k, dt)
         if out[k].numel() != R * (shape[1] if len(shape) > 1 else 1):
             raise ValueError("mask_rle: out[%r] must hold %s" % (k, shape))
-    _check(lib().scda_mask_rle_hip(_p(bits), i32(R), i32(H), i32(Wd), _p(image_info), i32(stride), i32(per), i32(h_all), i32(w_all),
-                                   _p(rois), i32(rstride), i32(cap_runs), i32(cap_bytes), _p(ws), _p(out['n_runs']), _p(out['counts']),
-                                   _p(out['n_bytes']), _p(out['chars']), _p(out['area']), _p(out['bbox']), _stream()),
-           "scda_mask_rle_hip")
+    _check(lib().scda_mask_rle_hip(_p(bits), R, H, Wd, _p(image_info), stride, per, h_all, w_all, _p(rois), rstride, cap_runs, cap_bytes,
+                                   _p(ws), _p(out['n_runs']), _p(out['counts']), _p(out['n_bytes']), _p(out['chars']), _p(out['area']),
+                                   _p(out['bbox']), _stream()), "scda_mask_rle_hip")
     return out
 
 
 def mask_iou_workspace_bytes(M, N, H, Wd):
-    return int(lib().scda_mask_iou_workspace_bytes(i32(M), i32(N), i32(H), i32(Wd)))
+    return int(lib().scda_mask_iou_workspace_bytes(M, N, H, Wd))
 
 
 def mask_iou(dt_bits, gt_bits, size, iscrowd=None, ws=None, out=None):
@@ -530,7 +548,7 @@ def mask_iou(dt_bits, gt_bits, size, iscrowd=None, ws=None, out=None):
         _req(iscrowd, "iscrowd", torch.uint8)
         if iscrowd.numel() != N:
             raise ValueError("mask_iou: iscrowd must be [N]")
-    need = int(lib().scda_mask_iou_workspace_bytes(i32(M), i32(N), i32(H), i32(Wd)))
+    need = int(lib().scda_mask_iou_workspace_bytes(M, N, H, Wd))
     if need == 0:
         raise ValueError("mask_iou: planes of at most 65535 masks x 65535 rows and fewer than 2^31 pixels")
     if ws is None:
@@ -544,8 +562,8 @@ def mask_iou(dt_bits, gt_bits, size, iscrowd=None, ws=None, out=None):
     iou, inter = _req(out[0], "iou", torch.float64), _req(out[1], "inter", torch.int32)
     if iou.numel() != N * M or inter.numel() != N * M:
         raise ValueError("mask_iou: out must hold [N, M]")
-    _check(lib().scda_mask_iou_hip(_p(dt_bits), i32(M), _p(gt_bits), i32(N), i32(H), i32(Wd), i32(h), i32(w), _p(iscrowd), _p(ws),
-                                   _p(iou), _p(inter), _stream()), "scda_mask_iou_hip")
+    _check(lib().scda_mask_iou_hip(_p(dt_bits), M, _p(gt_bits), N, H, Wd, h, w, _p(iscrowd), _p(ws), _p(iou), _p(inter), _stream()),
+           "scda_mask_iou_hip")
     return iou, inter
 
 
@@ -566,8 +584,8 @@ def coco_det_rows(detections, detection_counts, K, xywh, area, score, cat, mask_
         _req(mask_area, "mask_area", torch.int32)
         if mask_area.numel() != B * top_n:
             raise ValueError("coco_det_rows: mask_area must be [B, top_n]")
-    _check(lib().scda_coco_det_rows_hip(_p(detections), _p(detection_counts), i32(B), i32(top_n), _p(mask_area), i32(int(K)), _p(xywh),
-                                        _p(area), _p(score), _p(cat), _stream()), "scda_coco_det_rows_hip")
+    _check(lib().scda_coco_det_rows_hip(_p(detections), _p(detection_counts), B, top_n, _p(mask_area), int(K), _p(xywh), _p(area),
+                                        _p(score), _p(cat), _stream()), "scda_coco_det_rows_hip")
 
 
 def coco_box_iou(dt, dt_counts, gt, gt_counts, iscrowd, out=None):
@@ -587,8 +605,8 @@ def coco_box_iou(dt, dt_counts, gt, gt_counts, iscrowd, out=None):
     _req(out, "out", torch.float64)
     if out.numel() < B * G * D:
         raise ValueError("coco_box_iou: out must hold [B, G, D]")
-    _check(lib().scda_coco_box_iou_hip(_p(dt), _p(dt_counts), _p(gt), _p(gt_counts), _p(iscrowd), i32(B), i32(D), i32(G), _p(out),
-                                       _stream()), "scda_coco_box_iou_hip")
+    _check(lib().scda_coco_box_iou_hip(_p(dt), _p(dt_counts), _p(gt), _p(gt_counts), _p(iscrowd), B, D, G, _p(out), _stream()),
+           "scda_coco_box_iou_hip")
     return out
 
 
@@ -610,14 +628,13 @@ def coco_match(iou, dt_counts, dt_cat, score, dt_area, gt_counts, gt_cat, gt_are
         _req(t, name, dt)
         if t.numel() < n:
             raise ValueError(f"coco_match: {name} holds {t.numel()} elements, {n} needed")
-    _check(lib().scda_coco_match_hip(_p(iou), i32(B), i32(D), i32(G), _p(dt_counts), _p(dt_cat), _p(score), _p(dt_area), _p(gt_counts),
-                                     _p(gt_cat), _p(gt_area), _p(gt_iscrowd), i32(int(K)), _p(iou_thrs), i32(T), _p(area_rng), i32(A),
-                                     i32(int(max_det)), _p(rank), _p(bits), _p(npig), _p(seen), _p(dbg_match), _stream()),
-           "scda_coco_match_hip")
+    _check(lib().scda_coco_match_hip(_p(iou), B, D, G, _p(dt_counts), _p(dt_cat), _p(score), _p(dt_area), _p(gt_counts), _p(gt_cat),
+                                     _p(gt_area), _p(gt_iscrowd), int(K), _p(iou_thrs), T, _p(area_rng), A, int(max_det), _p(rank),
+                                     _p(bits), _p(npig), _p(seen), _p(dbg_match), _stream()), "scda_coco_match_hip")
 
 
 def coco_accumulate_workspace_bytes(n_images, D, K, A):
-    return int(lib().scda_coco_accumulate_workspace_bytes(i32(n_images), i32(D), i32(K), i32(A)))
+    return int(lib().scda_coco_accumulate_workspace_bytes(n_images, D, K, A))
 
 
 def coco_accumulate(image_ids, n_images, cat, rank, score, bits, npig, seen, rec_thrs, max_dets, max_det_last, T, ws, precision, recall,
@@ -638,9 +655,9 @@ def coco_accumulate(image_ids, n_images, cat, rank, score, bits, npig, seen, rec
     need = coco_accumulate_workspace_bytes(n_images, D, K, A)
     if need == 0 or ws.numel() < need:
         raise ValueError("coco_accumulate: workspace too small or sizes out of range")
-    _check(lib().scda_coco_accumulate_hip(_p(image_ids), i32(n_images), i32(D), _p(cat), _p(rank), _p(score), _p(bits), _p(npig), _p(seen),
-                                          i32(K), i32(T), i32(A), _p(rec_thrs), i32(R), _p(max_dets), i32(M), i32(int(max_det_last)),
-                                          _p(ws), _p(precision), _p(recall), _p(scores), _stream()), "scda_coco_accumulate_hip")
+    _check(lib().scda_coco_accumulate_hip(_p(image_ids), n_images, D, _p(cat), _p(rank), _p(score), _p(bits), _p(npig), _p(seen), K, T, A,
+                                          _p(rec_thrs), R, _p(max_dets), M, int(max_det_last), _p(ws), _p(precision), _p(recall),
+                                          _p(scores), _stream()), "scda_coco_accumulate_hip")
 
 
 def coco_summarize(precision, recall, shape, spec, stats):
@@ -651,8 +668,8 @@ def coco_summarize(precision, recall, shape, spec, stats):
     n = spec.shape[0]
     if precision.numel() != T * R * K * A * M or recall.numel() != T * K * A * M or spec.numel() != 4 * n or stats.numel() < n:
         raise ValueError("coco_summarize: precision [T, R, K, A, M], recall [T, K, A, M], spec [n, 4], stats [n]")
-    _check(lib().scda_coco_summarize_hip(_p(precision), _p(recall), i32(T), i32(R), i32(K), i32(A), i32(M), _p(spec), i32(n), _p(stats),
-                                         _stream()), "scda_coco_summarize_hip")
+    _check(lib().scda_coco_summarize_hip(_p(precision), _p(recall), T, R, K, A, M, _p(spec), n, _p(stats), _stream()),
+           "scda_coco_summarize_hip")
     return stats
 
 
@@ -663,7 +680,7 @@ _WS = {}
 def workspace(nbytes, device):
     """Grow-only scratch buffer (split-K slabs), one per (device, stream): kernels on different HIP streams may run
     concurrently and must not share slabs.  Never freed during a run."""
-    key = (device.index, _stream().value)
+    key = (device.index, _stream())
     buf = _WS.get(key)
     if buf is None or buf.numel() < nbytes:
         buf = torch.empty(int(nbytes), dtype=torch.uint8, device=device)
@@ -672,13 +689,11 @@ def workspace(nbytes, device):
 
 
 ACT_NONE, ACT_RELU, ACT_LEAKY = 0, 1, 2
-_sz = ctypes.c_size_t
 
 
 def _conv_ws(batch, cin, ih, iw, cout, kh, kw, s, p, device):
     L = lib()
-    L.scda_conv2d_workspace_bytes.restype = ctypes.c_size_t
-    n = L.scda_conv2d_workspace_bytes(i32(batch), i32(cin), i32(ih), i32(iw), i32(cout), i32(kh), i32(kw), i32(s), i32(p))
+    n = L.scda_conv2d_workspace_bytes(batch, cin, ih, iw, cout, kh, kw, s, p)
     return workspace(n, device), n
 
 
@@ -702,11 +717,9 @@ def conv2d_pack_weight(w, for_dgrad=False, cache=True):
         # valid only for the very same tensor object (a freed temporary's address may be reused by another weight)
         if hit is not None and hit[0] == tag and hit[2]() is w:
             return hit[1]
-    lib().scda_conv2d_packed_elems.restype = ctypes.c_size_t
-    n = lib().scda_conv2d_packed_elems(i32(Cout), i32(Cin), i32(KH), i32(KW), i32(int(for_dgrad)))
+    n = lib().scda_conv2d_packed_elems(Cout, Cin, KH, KW, int(for_dgrad))
     out = torch.empty(n, dtype=torch.float32, device=w.device)
-    _check(lib().scda_conv2d_pack_weight_hip(_p(w), _p(out), i32(Cout), i32(Cin), i32(KH), i32(KW), i32(int(for_dgrad)),
-                                             _stream()), "scda_conv2d_pack_weight_hip")
+    _check(lib().scda_conv2d_pack_weight_hip(_p(w), _p(out), Cout, Cin, KH, KW, int(for_dgrad), _stream()), "scda_conv2d_pack_weight_hip")
     if cache:
         _PACK_CACHE[key] = (tag, out, weakref.ref(w))
     return out
@@ -720,8 +733,7 @@ def wino_enabled():
 def _route(direction, B, Cin, IH, IW, Cout, KH, KW, stride, pad, row_period):
     """csrc/launch_plan.h route_conv: (family 0 implicit GEMM / 1 Winograd / 2 Winograd on stacked 7 x 7 maps, conv + pool fusable, maps)"""
     pool, maps = ctypes.c_int(0), ctypes.c_int(0)
-    fam = lib().scda_conv2d_route(i32(direction), i32(B), i32(Cin), i32(IH), i32(IW), i32(Cout), i32(KH), i32(KW), i32(stride), i32(pad),
-                                  i32(row_period), ctypes.byref(pool), ctypes.byref(maps))
+    fam = lib().scda_conv2d_route(direction, B, Cin, IH, IW, Cout, KH, KW, stride, pad, row_period, ctypes.byref(pool), ctypes.byref(maps))
     return fam, bool(pool.value), maps.value
 
 
@@ -761,11 +773,11 @@ def conv2d_wino_wgrad(dy, x, w_shape, out=None, db_out=None, want_bias=False, ro
         maps = wino_stacked(B, IH, IW, row_period)
         if not maps:
             raise ValueError("conv2d_wino_wgrad: row_period %d on %s is not a stack of 7 x 7 maps" % (row_period, tuple(x.shape)))
-        _check(lib().scda_conv2d_wino_wgrad_stacked_hip(_p(dy), _p(x), _p(out), _p(db), i32(maps), i32(Cin), i32(Cout), i32(acc), i32(dbacc),
-                                                        _p(ws), _sz(n), _stream()), "scda_conv2d_wino_wgrad_stacked_hip")
+        _check(lib().scda_conv2d_wino_wgrad_stacked_hip(_p(dy), _p(x), _p(out), _p(db), maps, Cin, Cout, acc, dbacc, _p(ws), n, _stream()),
+               "scda_conv2d_wino_wgrad_stacked_hip")
         return out, db
-    _check(lib().scda_conv2d_wino_wgrad_hip(_p(dy), _p(x), _p(out), _p(db), i32(B), i32(Cin), i32(IH), i32(IW), i32(Cout), i32(acc),
-                                            i32(dbacc), _p(ws), _sz(n), _stream()), "scda_conv2d_wino_wgrad_hip")
+    _check(lib().scda_conv2d_wino_wgrad_hip(_p(dy), _p(x), _p(out), _p(db), B, Cin, IH, IW, Cout, acc, dbacc, _p(ws), n, _stream()),
+           "scda_conv2d_wino_wgrad_hip")
     return out, db
 
 
@@ -782,10 +794,9 @@ def conv2d_wino_pack(w, for_dgrad=False, cache=True):
         if hit is not None and hit[0] == tag and hit[2]() is w:
             return hit[1]
     L = lib()
-    L.scda_conv2d_wino_packed_elems.restype = ctypes.c_size_t
-    n = L.scda_conv2d_wino_packed_elems(i32(Cout), i32(Cin), i32(int(for_dgrad)))
+    n = L.scda_conv2d_wino_packed_elems(Cout, Cin, int(for_dgrad))
     out = torch.empty(n, dtype=torch.float32, device=w.device)
-    _check(L.scda_conv2d_wino_pack_hip(_p(w.contiguous()), _p(out), i32(Cout), i32(Cin), i32(int(for_dgrad)), _stream()), "scda_conv2d_wino_pack_hip")
+    _check(L.scda_conv2d_wino_pack_hip(_p(w.contiguous()), _p(out), Cout, Cin, int(for_dgrad), _stream()), "scda_conv2d_wino_pack_hip")
     if cache:
         _PACK_CACHE[key] = (tag, out, weakref.ref(w))
     return out
@@ -801,11 +812,11 @@ def conv2d_wino(x, u, bias, M, act=ACT_NONE, slope=0.01, mask_src=None, mask_slo
         maps = wino_stacked(B, H, W, row_period)
         if not maps:
             raise ValueError("conv2d_wino: row_period %d on %s is not a stack of 7 x 7 maps" % (row_period, tuple(x.shape)))
-        _check(lib().scda_conv2d_wino_stacked_hip(_p(x), _p(u), _p(bias), _p(y), i32(maps), i32(C), i32(M), i32(act), f32(slope), _p(mask_src),
-                                                  f32(mask_slope), i32(int(for_dgrad)), _p(ws), _sz(n), _stream()), "scda_conv2d_wino_stacked_hip")
+        _check(lib().scda_conv2d_wino_stacked_hip(_p(x), _p(u), _p(bias), _p(y), maps, C, M, act, slope, _p(mask_src), mask_slope,
+                                                  int(for_dgrad), _p(ws), n, _stream()), "scda_conv2d_wino_stacked_hip")
         return y
-    _check(lib().scda_conv2d_wino_hip(_p(x), _p(u), _p(bias), _p(y), i32(B), i32(C), i32(H), i32(W), i32(M), i32(act), f32(slope),
-                                      _p(mask_src), f32(mask_slope), i32(int(for_dgrad)), _p(ws), _sz(n), _stream()), "scda_conv2d_wino_hip")
+    _check(lib().scda_conv2d_wino_hip(_p(x), _p(u), _p(bias), _p(y), B, C, H, W, M, act, slope, _p(mask_src), mask_slope, int(for_dgrad),
+                                      _p(ws), n, _stream()), "scda_conv2d_wino_hip")
     return y
 
 
@@ -820,8 +831,8 @@ def conv2d_wino_pool(x, u, bias, M, act=ACT_NONE, slope=0.01):
     B, C, H, W = x.shape
     y = torch.empty(B, M, H // 2, W // 2, dtype=torch.float32, device=x.device)
     idx = torch.empty(B, M, H // 2, W // 2, dtype=torch.uint8, device=x.device)
-    _check(lib().scda_conv2d_wino_pool_hip(_p(x), _p(u), _p(bias), _p(y), _p(idx), i32(B), i32(C), i32(H), i32(W), i32(M), i32(act),
-                                           f32(slope), _stream()), "scda_conv2d_wino_pool_hip")
+    _check(lib().scda_conv2d_wino_pool_hip(_p(x), _p(u), _p(bias), _p(y), _p(idx), B, C, H, W, M, act, slope, _stream()),
+           "scda_conv2d_wino_pool_hip")
     return y, idx
 
 
@@ -841,20 +852,18 @@ def conv2d_pack_all(flat):
     plan = plans.get(wino)
     L = lib()
     if plan is None:
-        L.scda_conv2d_packed_elems.restype = ctypes.c_size_t
-        L.scda_conv2d_pack_tiles.restype = ctypes.c_longlong
         rows, entries, off, tiles = [], [], 0, 0
         base = flat.data.data_ptr()
         for i, w in enumerate(ws):
             Cout, Cin, KH, KW = w.shape
             src = (w.data_ptr() - base) // 4
-            use_wino = wino is not None and wino[i] and all(L.scda_conv2d_packed_elems(i32(Cout), i32(Cin), i32(KH), i32(KW), i32(d)) for d in (2, 3))
+            use_wino = wino is not None and wino[i] and all(L.scda_conv2d_packed_elems(Cout, Cin, KH, KW, d) for d in (2, 3))
             for d in ((2, 3) if use_wino else (0, 1)):
-                n = int(L.scda_conv2d_packed_elems(i32(Cout), i32(Cin), i32(KH), i32(KW), i32(d)))
+                n = int(L.scda_conv2d_packed_elems(Cout, Cin, KH, KW, d))
                 rows.append([src, off, Cout, Cin, KH * KW, d, tiles])
                 entries.append((w, d if d >= 2 else bool(d), off, n))
                 off += n
-                tiles += int(L.scda_conv2d_pack_tiles(i32(Cout), i32(Cin), i32(KH), i32(KW), i32(d)))
+                tiles += int(L.scda_conv2d_pack_tiles(Cout, Cin, KH, KW, d))
         desc = upload(torch.tensor(rows, dtype=torch.int64), flat.data.device)
         while len(plans) >= 4:       # least recently used first (dicts keep insertion order; a hit re-inserts below)
             plans.pop(next(iter(plans)))
@@ -869,8 +878,8 @@ def conv2d_pack_all(flat):
     out = flat.__dict__.get("_scda_pack_out")
     if out is None or out.numel() < total:
         out = flat.__dict__["_scda_pack_out"] = torch.empty(total, dtype=torch.float32, device=flat.data.device)
-    _check(L.scda_conv2d_pack_weights_batched_hip(_p(flat.data), _p(out), _p(desc), i32(len(entries)),
-                                                  ctypes.c_longlong(tiles), _stream()), "scda_conv2d_pack_weights_batched_hip")
+    _check(L.scda_conv2d_pack_weights_batched_hip(_p(flat.data), _p(out), _p(desc), len(entries), tiles, _stream()),
+           "scda_conv2d_pack_weights_batched_hip")
     for w, d, off, n in entries:
         if w.data_ptr() < flat.data.data_ptr():   # parameter was re-homed: fall back to the lazy path for it
             continue
@@ -895,9 +904,8 @@ def conv2d_fwd(x, w, bias, stride, pad, act=ACT_NONE, slope=0.01, row_period=0):
     wp = conv2d_pack_weight(w, False)
     y = torch.empty(B, Cout, OH, OW, dtype=torch.float32, device=x.device)
     ws, n = _conv_ws(B, Cin, IH, IW, Cout, KH, KW, stride, pad, x.device)
-    _check(lib().scda_conv2d_fwd_hip(_p(x), _p(wp), _p(bias), _p(y), i32(B), i32(Cin), i32(IH), i32(IW), i32(Cout), i32(KH),
-                                     i32(KW), i32(stride), i32(pad), i32(row_period), i32(act), f32(slope), _p(ws), _sz(n), _stream()),
-           "scda_conv2d_fwd_hip")
+    _check(lib().scda_conv2d_fwd_hip(_p(x), _p(wp), _p(bias), _p(y), B, Cin, IH, IW, Cout, KH, KW, stride, pad, row_period, act, slope,
+                                     _p(ws), n, _stream()), "scda_conv2d_fwd_hip")
     return y
 
 
@@ -916,15 +924,13 @@ def conv2d_dgrad(dy, w, x_shape, stride, pad, act_src=None, act_slope=0.0, row_p
     dx = torch.empty(B, Cin, IH, IW, dtype=torch.float32, device=dy.device)
     if act_src is None and Cin <= 4 and Cout * KH * KW * 16 <= 65536 and (KH, KW) in ((3, 3), (1, 1)):
         # image-side layer: 3 rows of a 64-row MFMA tile would be 95 % padding -- direct kernel, unpacked weights
-        _check(lib().scda_conv2d_dgrad_small_cin_hip(_p(dy), _p(w.contiguous()), _p(dx), i32(B), i32(Cin), i32(IH), i32(IW), i32(Cout),
-                                                     i32(KH), i32(KW), i32(stride), i32(pad), _stream()),
-               "scda_conv2d_dgrad_small_cin_hip")
+        _check(lib().scda_conv2d_dgrad_small_cin_hip(_p(dy), _p(w.contiguous()), _p(dx), B, Cin, IH, IW, Cout, KH, KW, stride, pad,
+                                                     _stream()), "scda_conv2d_dgrad_small_cin_hip")
         return dx
     wt = conv2d_pack_weight(w, True)
     ws, n = _conv_ws(B, Cin, IH, IW, Cout, KH, KW, stride, pad, dy.device)
-    _check(lib().scda_conv2d_dgrad_act_hip(_p(dy), _p(wt), _p(dx), i32(B), i32(Cin), i32(IH), i32(IW), i32(Cout), i32(KH),
-                                           i32(KW), i32(stride), i32(pad), i32(row_period), _p(act_src), f32(act_slope), _p(ws), _sz(n), _stream()),
-           "scda_conv2d_dgrad_act_hip")
+    _check(lib().scda_conv2d_dgrad_act_hip(_p(dy), _p(wt), _p(dx), B, Cin, IH, IW, Cout, KH, KW, stride, pad, row_period, _p(act_src),
+                                           act_slope, _p(ws), n, _stream()), "scda_conv2d_dgrad_act_hip")
     return dx
 
 
@@ -941,9 +947,8 @@ def conv2d_wgrad(dy, x, w_shape, stride, pad, out=None, row_period=0):
     else:
         _req(out, "out"); acc = 1
     ws, n = _conv_ws(B, Cin, IH, IW, Cout, KH, KW, stride, pad, x.device)
-    _check(lib().scda_conv2d_wgrad_hip(_p(dy), _p(x), _p(out), i32(B), i32(Cin), i32(IH), i32(IW), i32(Cout), i32(KH),
-                                       i32(KW), i32(stride), i32(pad), i32(row_period), i32(acc), _p(ws), _sz(n), _stream()),
-           "scda_conv2d_wgrad_hip")
+    _check(lib().scda_conv2d_wgrad_hip(_p(dy), _p(x), _p(out), B, Cin, IH, IW, Cout, KH, KW, stride, pad, row_period, acc, _p(ws), n,
+                                       _stream()), "scda_conv2d_wgrad_hip")
     return out
 
 
@@ -957,7 +962,7 @@ def conv2d_wgrad_bias(dy, x, w_shape, stride, pad, out=None, db_out=None, row_pe
     if wino_wgrad_ok(B, Cin, IH, IW, Cout, KH, KW, stride, pad, row_period):
         return conv2d_wino_wgrad(dy, x, w_shape, out=out, db_out=db_out, want_bias=True, row_period=row_period)
     L = lib()
-    if not L.scda_conv2d_wgrad_bias_fusable(i32(B), i32(Cout), i32(dy.shape[2]), i32(dy.shape[3]), _p(dy)):
+    if not L.scda_conv2d_wgrad_bias_fusable(B, Cout, dy.shape[2], dy.shape[3], _p(dy)):
         return conv2d_wgrad(dy, x, w_shape, stride, pad, out=out, row_period=row_period), bias_grad_nchw(dy, out=db_out)
     acc = dbacc = 0
     if out is None:
@@ -969,9 +974,8 @@ def conv2d_wgrad_bias(dy, x, w_shape, stride, pad, out=None, db_out=None, row_pe
     else:
         _req(db_out, "db_out"); dbacc = 1
     ws, n = _conv_ws(B, Cin, IH, IW, Cout, KH, KW, stride, pad, x.device)
-    _check(L.scda_conv2d_wgrad_bias_hip(_p(dy), _p(x), _p(out), _p(db_out), i32(B), i32(Cin), i32(IH), i32(IW), i32(Cout),
-                                        i32(KH), i32(KW), i32(stride), i32(pad), i32(row_period), i32(acc), i32(dbacc), _p(ws), _sz(n),
-                                        _stream()), "scda_conv2d_wgrad_bias_hip")
+    _check(L.scda_conv2d_wgrad_bias_hip(_p(dy), _p(x), _p(out), _p(db_out), B, Cin, IH, IW, Cout, KH, KW, stride, pad, row_period, acc,
+                                        dbacc, _p(ws), n, _stream()), "scda_conv2d_wgrad_bias_hip")
     return out, db_out
 
 
@@ -986,12 +990,10 @@ def gemm(a, b, M, N, K, lda, ldb, trans_a=False, trans_b=False, bias=None, bias_
     else:
         _req(out, "out")
     L = lib()
-    L.scda_gemm_workspace_bytes.restype = ctypes.c_size_t
-    n = L.scda_gemm_workspace_bytes(i32(M), i32(N), i32(K))
+    n = L.scda_gemm_workspace_bytes(M, N, K)
     ws = workspace(n, a.device)
-    _check(L.scda_gemm_hip(_p(a), _p(b), _p(out), i32(M), i32(N), i32(K), i32(lda), i32(ldb), i32(N), i32(int(trans_a)),
-                           i32(int(trans_b)), _p(bias), i32(int(bias_on_n)), i32(act), f32(slope), i32(int(accumulate)),
-                           _p(ws), _sz(n), _stream()), "scda_gemm_hip")
+    _check(L.scda_gemm_hip(_p(a), _p(b), _p(out), M, N, K, lda, ldb, N, int(trans_a), int(trans_b), _p(bias), int(bias_on_n), act, slope,
+                           int(accumulate), _p(ws), n, _stream()), "scda_gemm_hip")
     return out
 
 
@@ -1017,16 +1019,12 @@ def linear_wgrad(dy, x, out=None, accumulate=True):
 
 
 # ------------------------------------------------------ layer kernels -------
-i64 = ctypes.c_longlong
-u64 = ctypes.c_uint64
-
-
 def maxpool2x2_fwd(x):
     _req(x, "x")
     B, C, H, W = x.shape
     y = torch.empty(B, C, H // 2, W // 2, dtype=torch.float32, device=x.device)
     idx = torch.empty(B, C, H // 2, W // 2, dtype=torch.uint8, device=x.device)
-    _check(lib().scda_maxpool2x2_fwd_hip(_p(x), _p(y), _p(idx), i32(B * C), i32(H), i32(W), _stream()), "scda_maxpool2x2_fwd_hip")
+    _check(lib().scda_maxpool2x2_fwd_hip(_p(x), _p(y), _p(idx), B * C, H, W, _stream()), "scda_maxpool2x2_fwd_hip")
     return y, idx
 
 
@@ -1036,10 +1034,10 @@ def maxpool2x2_bwd(dy, idx, x_shape, relu_y=None):
     B, C, H, W = x_shape
     dx = torch.empty(B, C, H, W, dtype=torch.float32, device=dy.device)
     if relu_y is None:
-        _check(lib().scda_maxpool2x2_bwd_hip(_p(dy), _p(idx), _p(dx), i32(B * C), i32(H), i32(W), _stream()), "scda_maxpool2x2_bwd_hip")
+        _check(lib().scda_maxpool2x2_bwd_hip(_p(dy), _p(idx), _p(dx), B * C, H, W, _stream()), "scda_maxpool2x2_bwd_hip")
     else:
         _req(relu_y, "relu_y")
-        _check(lib().scda_maxpool2x2_bwd_relu_hip(_p(dy), _p(idx), _p(relu_y), _p(dx), i32(B * C), i32(H), i32(W), _stream()),
+        _check(lib().scda_maxpool2x2_bwd_relu_hip(_p(dy), _p(idx), _p(relu_y), _p(dx), B * C, H, W, _stream()),
                "scda_maxpool2x2_bwd_relu_hip")
     return dx
 
@@ -1048,7 +1046,7 @@ def maxpool3x3s2_fwd(x):
     _req(x, "x")
     B, C, H, W = x.shape
     y = torch.empty(B, C, (H - 1) // 2 + 1, (W - 1) // 2 + 1, dtype=torch.float32, device=x.device)
-    _check(lib().scda_maxpool3x3s2_fwd_hip(_p(x), _p(y), i32(B * C), i32(H), i32(W), _stream()), "scda_maxpool3x3s2_fwd_hip")
+    _check(lib().scda_maxpool3x3s2_fwd_hip(_p(x), _p(y), B * C, H, W, _stream()), "scda_maxpool3x3s2_fwd_hip")
     return y
 
 
@@ -1057,7 +1055,7 @@ def add_relu(a, b):
     if a.shape != b.shape:
         raise ValueError("add_relu: shape mismatch")
     y = torch.empty_like(a)
-    _check(lib().scda_add_relu_hip(_p(a), _p(b), _p(y), i64(a.numel()), _stream()), "scda_add_relu_hip")
+    _check(lib().scda_add_relu_hip(_p(a), _p(b), _p(y), a.numel(), _stream()), "scda_add_relu_hip")
     return y
 
 
@@ -1067,14 +1065,14 @@ ACT_MODE = {"relu": 0, "leaky": 1, "tanh": 2, "sigmoid": 3}
 def act_fwd(x, mode, slope=0.01):
     _req(x, "x")
     y = torch.empty_like(x)
-    _check(lib().scda_act_fwd_hip(_p(x), _p(y), i64(x.numel()), i32(mode), f32(slope), _stream()), "scda_act_fwd_hip")
+    _check(lib().scda_act_fwd_hip(_p(x), _p(y), x.numel(), mode, slope, _stream()), "scda_act_fwd_hip")
     return y
 
 
 def act_bwd(dy, y, mode, slope=0.01):
     _req(dy, "dy"); _req(y, "y")
     dx = torch.empty_like(dy)
-    _check(lib().scda_act_bwd_hip(_p(dy), _p(y), _p(dx), i64(dy.numel()), i32(mode), f32(slope), _stream()), "scda_act_bwd_hip")
+    _check(lib().scda_act_bwd_hip(_p(dy), _p(y), _p(dx), dy.numel(), mode, slope, _stream()), "scda_act_bwd_hip")
     return dx
 
 
@@ -1083,21 +1081,20 @@ def axpby(a, b, alpha=1.0, beta=1.0):
     if b is not None:
         _req(b, "b")
     y = torch.empty_like(a)
-    _check(lib().scda_axpby_hip(_p(a), _p(b), _p(y), i64(a.numel()), f32(alpha), f32(beta), _stream()), "scda_axpby_hip")
+    _check(lib().scda_axpby_hip(_p(a), _p(b), _p(y), a.numel(), alpha, beta, _stream()), "scda_axpby_hip")
     return y
 
 
 def dropout_mask(shape, p, seed, device):
     mask = torch.empty(shape, dtype=torch.uint8, device=device)
-    _check(lib().scda_dropout_mask_hip(_p(mask), i64(mask.numel()), f32(p), u64(seed & 0xFFFFFFFFFFFFFFFF), _stream()),
-           "scda_dropout_mask_hip")
+    _check(lib().scda_dropout_mask_hip(_p(mask), mask.numel(), p, seed & 0xFFFFFFFFFFFFFFFF, _stream()), "scda_dropout_mask_hip")
     return mask
 
 
 def dropout_apply(x, mask, scale):
     _req(x, "x"); _req(mask, "mask", torch.uint8)
     y = torch.empty_like(x)
-    _check(lib().scda_dropout_apply_hip(_p(x), _p(mask), _p(y), i64(x.numel()), f32(scale), _stream()), "scda_dropout_apply_hip")
+    _check(lib().scda_dropout_apply_hip(_p(x), _p(mask), _p(y), x.numel(), scale, _stream()), "scda_dropout_apply_hip")
     return y
 
 
@@ -1107,8 +1104,8 @@ def dropout_seeded(x, p, seed, scale, relu_src=None):
     if relu_src is not None:
         _req(relu_src, "relu_src")
     y = torch.empty_like(x)
-    _check(lib().scda_dropout_seeded_hip(_p(x), _p(y), i64(x.numel()), f32(p), u64(seed & 0xFFFFFFFFFFFFFFFF), f32(scale),
-                                         _p(relu_src), _stream()), "scda_dropout_seeded_hip")
+    _check(lib().scda_dropout_seeded_hip(_p(x), _p(y), x.numel(), p, seed & 0xFFFFFFFFFFFFFFFF, scale, _p(relu_src), _stream()),
+           "scda_dropout_seeded_hip")
     return y
 
 
@@ -1125,16 +1122,16 @@ def sigmoid_bce_rows_fwd(x, t, w, scale, out=None, want_prob=True):
     if out is None:
         out = torch.empty(1, dtype=torch.float32, device=x.device)
     prob = torch.empty_like(x) if want_prob else None
-    _check(lib().scda_sigmoid_bce_rows_fwd_hip(_p(x), _p(t), i32(t_rows), _p(w), i32(C), i32(n), f32(scale), i32(int(acc)), _p(prob),
-                                               _p(out), _stream()), "scda_sigmoid_bce_rows_fwd_hip")
+    _check(lib().scda_sigmoid_bce_rows_fwd_hip(_p(x), _p(t), t_rows, _p(w), C, n, scale, int(acc), _p(prob), _p(out), _stream()),
+           "scda_sigmoid_bce_rows_fwd_hip")
     return out, prob
 
 
 def sigmoid_bce_rows_bwd(prob, t, w, scale, g):
     C, n = prob.shape
     dx = torch.empty_like(prob)
-    _check(lib().scda_sigmoid_bce_rows_bwd_hip(_p(prob), _p(t), i32(t.numel() // n), _p(w), i32(C), i32(n), f32(scale), _p(g), _p(dx),
-                                               _stream()), "scda_sigmoid_bce_rows_bwd_hip")
+    _check(lib().scda_sigmoid_bce_rows_bwd_hip(_p(prob), _p(t), t.numel() // n, _p(w), C, n, scale, _p(g), _p(dx), _stream()),
+           "scda_sigmoid_bce_rows_bwd_hip")
     return dx
 
 
@@ -1145,10 +1142,8 @@ def bias_grad_nchw(dy, out=None):
     HW = dy.numel() // (B * C)
     db = out if out is not None else torch.empty(C, dtype=torch.float32, device=dy.device)
     L = lib()
-    L.scda_bias_grad_workspace_bytes.restype = ctypes.c_size_t
-    ws = torch.empty(L.scda_bias_grad_workspace_bytes(i32(C)) // 4, dtype=torch.float32, device=dy.device)
-    _check(L.scda_bias_grad_nchw_hip(_p(dy), _p(db), i32(B), i32(C), i32(HW), i32(0 if out is None else 1), _p(ws), _stream()),
-           "scda_bias_grad_nchw_hip")
+    ws = torch.empty(L.scda_bias_grad_workspace_bytes(C) // 4, dtype=torch.float32, device=dy.device)
+    _check(L.scda_bias_grad_nchw_hip(_p(dy), _p(db), B, C, HW, 0 if out is None else 1, _p(ws), _stream()), "scda_bias_grad_nchw_hip")
     return db
 
 
@@ -1156,7 +1151,7 @@ def colsum(dy, out=None):
     _req(dy, "dy")
     M, N = dy.shape
     db = out if out is not None else torch.empty(N, dtype=torch.float32, device=dy.device)
-    _check(lib().scda_colsum_hip(_p(dy), _p(db), i32(M), i32(N), i32(0 if out is None else 1), _stream()), "scda_colsum_hip")
+    _check(lib().scda_colsum_hip(_p(dy), _p(db), M, N, 0 if out is None else 1, _stream()), "scda_colsum_hip")
     return db
 
 
@@ -1165,7 +1160,7 @@ def softmax_ce_fwd(logits, targets, ignore_index=-100):
     R, C = logits.shape
     probs = torch.empty_like(logits)
     out2 = torch.empty(2, dtype=torch.float32, device=logits.device)
-    _check(lib().scda_softmax_ce_fwd_hip(_p(logits), _p(targets), i32(R), i32(C), i32(ignore_index), _p(probs), _p(out2), _stream()),
+    _check(lib().scda_softmax_ce_fwd_hip(_p(logits), _p(targets), R, C, ignore_index, _p(probs), _p(out2), _stream()),
            "scda_softmax_ce_fwd_hip")
     return out2, probs
 
@@ -1174,7 +1169,7 @@ def softmax_ce_bwd(probs, targets, out2, g, ignore_index=-100):
     _req(probs, "probs"); _req(g, "g")
     R, C = probs.shape
     dx = torch.empty_like(probs)
-    _check(lib().scda_softmax_ce_bwd_hip(_p(probs), _p(targets), i32(R), i32(C), i32(ignore_index), _p(out2), _p(g), _p(dx), _stream()),
+    _check(lib().scda_softmax_ce_bwd_hip(_p(probs), _p(targets), R, C, ignore_index, _p(out2), _p(g), _p(dx), _stream()),
            "scda_softmax_ce_bwd_hip")
     return dx
 
@@ -1183,7 +1178,7 @@ def row_softmax(x):
     _req(x, "x")
     R, C = x.shape
     y = torch.empty_like(x)
-    _check(lib().scda_row_softmax_hip(_p(x), _p(y), i32(R), i32(C), _stream()), "scda_row_softmax_hip")
+    _check(lib().scda_row_softmax_hip(_p(x), _p(y), R, C, _stream()), "scda_row_softmax_hip")
     return y
 
 
@@ -1191,7 +1186,7 @@ def accuracy(logits, targets, ignore_index=-1):
     _req(logits, "logits"); _req(targets, "targets", torch.int64)
     R, C = logits.shape
     out = torch.empty(1, dtype=torch.float32, device=logits.device)
-    _check(lib().scda_accuracy_hip(_p(logits), _p(targets), i32(R), i32(C), i32(ignore_index), _p(out), _stream()), "scda_accuracy_hip")
+    _check(lib().scda_accuracy_hip(_p(logits), _p(targets), R, C, ignore_index, _p(out), _stream()), "scda_accuracy_hip")
     return out
 
 
@@ -1200,17 +1195,16 @@ def smooth_l1_fwd(pred, mask, target, sigma, scale):
     if mask is not None:
         _req(mask, "mask")
     L = lib()
-    L.scda_smooth_l1_workspace_bytes.restype = ctypes.c_size_t
     ws = torch.empty(L.scda_smooth_l1_workspace_bytes() // 4, dtype=torch.float32, device=pred.device)
     out = torch.empty(1, dtype=torch.float32, device=pred.device)
-    _check(L.scda_smooth_l1_fwd_hip(_p(pred), _p(mask), _p(target), i64(pred.numel()), f32(sigma), f32(scale), _p(ws), _p(out), _stream()),
+    _check(L.scda_smooth_l1_fwd_hip(_p(pred), _p(mask), _p(target), pred.numel(), sigma, scale, _p(ws), _p(out), _stream()),
            "scda_smooth_l1_fwd_hip")
     return out
 
 
 def smooth_l1_bwd(pred, mask, target, sigma, scale, g):
     dp = torch.empty_like(pred)
-    _check(lib().scda_smooth_l1_bwd_hip(_p(pred), _p(mask), _p(target), i64(pred.numel()), f32(sigma), f32(scale), _p(g), _p(dp), _stream()),
+    _check(lib().scda_smooth_l1_bwd_hip(_p(pred), _p(mask), _p(target), pred.numel(), sigma, scale, _p(g), _p(dp), _stream()),
            "scda_smooth_l1_bwd_hip")
     return dp
 
@@ -1221,8 +1215,7 @@ def instnorm_fwd(x, eps, act, slope):
     y = torch.empty_like(x)
     mean = torch.empty(B * C, dtype=torch.float32, device=x.device)
     rstd = torch.empty(B * C, dtype=torch.float32, device=x.device)
-    _check(lib().scda_instnorm_fwd_hip(_p(x), _p(y), _p(mean), _p(rstd), i32(B * C), i32(H * W), f32(eps), i32(act), f32(slope), _stream()),
-           "scda_instnorm_fwd_hip")
+    _check(lib().scda_instnorm_fwd_hip(_p(x), _p(y), _p(mean), _p(rstd), B * C, H * W, eps, act, slope, _stream()), "scda_instnorm_fwd_hip")
     return y, mean, rstd
 
 
@@ -1230,7 +1223,7 @@ def instnorm_bwd(dy, x, mean, rstd, act, slope):
     _req(dy, "dy"); _req(x, "x")
     B, C, H, W = x.shape
     dx = torch.empty_like(x)
-    _check(lib().scda_instnorm_bwd_hip(_p(dy), _p(x), _p(mean), _p(rstd), _p(dx), i32(B * C), i32(H * W), i32(act), f32(slope), _stream()),
+    _check(lib().scda_instnorm_bwd_hip(_p(dy), _p(x), _p(mean), _p(rstd), _p(dx), B * C, H * W, act, slope, _stream()),
            "scda_instnorm_bwd_hip")
     return dx
 
@@ -1246,11 +1239,11 @@ def instnorm_drop_add_fwd(x, residual, eps, p, seed):
     rstd = torch.empty(B * C, dtype=torch.float32, device=x.device)
     if torch.is_tensor(seed):     # a slot of a scda_amd.seeds.SeedArena: the kernel reads the seed from device memory
         _req(seed, "seed", torch.int64)
-        _check(lib().scda_instnorm_drop_add_fwd_dev_hip(_p(x), _p(residual), _p(y), _p(mean), _p(rstd), i32(B * C), i32(H * W), f32(eps),
-                                                        f32(p), _p(seed), f32(1.0 / (1.0 - p)), _stream()), "scda_instnorm_drop_add_fwd_dev_hip")
+        _check(lib().scda_instnorm_drop_add_fwd_dev_hip(_p(x), _p(residual), _p(y), _p(mean), _p(rstd), B * C, H * W, eps, p, _p(seed),
+                                                        1.0 / (1.0 - p), _stream()), "scda_instnorm_drop_add_fwd_dev_hip")
         return y, mean, rstd
-    _check(lib().scda_instnorm_drop_add_fwd_hip(_p(x), _p(residual), _p(y), _p(mean), _p(rstd), i32(B * C), i32(H * W), f32(eps), f32(p),
-                                                u64(seed & 0xFFFFFFFFFFFFFFFF), f32(1.0 / (1.0 - p)), _stream()), "scda_instnorm_drop_add_fwd_hip")
+    _check(lib().scda_instnorm_drop_add_fwd_hip(_p(x), _p(residual), _p(y), _p(mean), _p(rstd), B * C, H * W, eps, p,
+                                                seed & 0xFFFFFFFFFFFFFFFF, 1.0 / (1.0 - p), _stream()), "scda_instnorm_drop_add_fwd_hip")
     return y, mean, rstd
 
 
@@ -1259,18 +1252,17 @@ def instnorm_drop_bwd(dy, x, mean, rstd, p, seed):
     B, C, H, W = x.shape
     dx = torch.empty_like(x)
     if torch.is_tensor(seed):
-        _check(lib().scda_instnorm_drop_bwd_dev_hip(_p(dy), _p(x), _p(mean), _p(rstd), _p(dx), i32(B * C), i32(H * W), f32(p), _p(seed),
-                                                    f32(1.0 / (1.0 - p)), _stream()), "scda_instnorm_drop_bwd_dev_hip")
+        _check(lib().scda_instnorm_drop_bwd_dev_hip(_p(dy), _p(x), _p(mean), _p(rstd), _p(dx), B * C, H * W, p, _p(seed), 1.0 / (1.0 - p),
+                                                    _stream()), "scda_instnorm_drop_bwd_dev_hip")
         return dx
-    _check(lib().scda_instnorm_drop_bwd_hip(_p(dy), _p(x), _p(mean), _p(rstd), _p(dx), i32(B * C), i32(H * W), f32(p),
-                                            u64(seed & 0xFFFFFFFFFFFFFFFF), f32(1.0 / (1.0 - p)), _stream()), "scda_instnorm_drop_bwd_dev_hip")
+    _check(lib().scda_instnorm_drop_bwd_hip(_p(dy), _p(x), _p(mean), _p(rstd), _p(dx), B * C, H * W, p, seed & 0xFFFFFFFFFFFFFFFF,
+                                            1.0 / (1.0 - p), _stream()), "scda_instnorm_drop_bwd_dev_hip")
     return dx
 
 
 def _bn_ws(B, C, HW, device):
     L = lib()
-    L.scda_batchnorm_workspace_bytes.restype = ctypes.c_size_t
-    n = L.scda_batchnorm_workspace_bytes(i32(B), i32(C), i32(HW))
+    n = L.scda_batchnorm_workspace_bytes(B, C, HW)
     return torch.empty(n // 4, dtype=torch.float32, device=device) if n else None
 
 
@@ -1281,8 +1273,8 @@ def batchnorm_fwd(x, gamma, beta, run_mean, run_var, eps, momentum, act, slope):
     mean = torch.empty(C, dtype=torch.float32, device=x.device)
     rstd = torch.empty(C, dtype=torch.float32, device=x.device)
     ws = _bn_ws(B, C, H * W, x.device)
-    _check(lib().scda_batchnorm_fwd_hip(_p(x), _p(y), _p(gamma), _p(beta), _p(run_mean), _p(run_var), _p(mean), _p(rstd), i32(B), i32(C),
-                                        i32(H * W), f32(eps), f32(momentum), i32(act), f32(slope), _p(ws), _stream()), "scda_batchnorm_fwd_hip")
+    _check(lib().scda_batchnorm_fwd_hip(_p(x), _p(y), _p(gamma), _p(beta), _p(run_mean), _p(run_var), _p(mean), _p(rstd), B, C, H * W, eps,
+                                        momentum, act, slope, _p(ws), _stream()), "scda_batchnorm_fwd_hip")
     return y, mean, rstd
 
 
@@ -1293,16 +1285,16 @@ def batchnorm_bwd(dy, x, gamma, beta, mean, rstd, act, slope, need_dx=True, out=
     dx = torch.empty_like(x) if need_dx else None
     dg, db = out if out is not None else (torch.empty(C, dtype=torch.float32, device=x.device),
                                           torch.empty(C, dtype=torch.float32, device=x.device))
-    _check(lib().scda_batchnorm_bwd_hip(_p(dy), _p(x), _p(gamma), _p(beta), _p(mean), _p(rstd), _p(dx), _p(dg), _p(db), i32(B), i32(C),
-                                        i32(H * W), i32(act), f32(slope), i32(0 if out is None else 1), _p(_bn_ws(B, C, H * W, x.device)),
-                                        _stream()), "scda_batchnorm_bwd_hip")
+    _check(lib().scda_batchnorm_bwd_hip(_p(dy), _p(x), _p(gamma), _p(beta), _p(mean), _p(rstd), _p(dx), _p(dg), _p(db), B, C, H * W, act,
+                                        slope, 0 if out is None else 1, _p(_bn_ws(B, C, H * W, x.device)), _stream()),
+           "scda_batchnorm_bwd_hip")
     return dx, dg, db
 
 
 def batchnorm_add_relu_ok(x):
     """is relu(bn(x) + residual) served as one kernel for this map?  (batch 1, plane of a multiple of 4 up to 40960 elements)"""
     B, C, H, W = x.shape
-    return bool(lib().scda_batchnorm_add_relu_ok(i32(B), i32(H * W)))
+    return bool(lib().scda_batchnorm_add_relu_ok(B, H * W))
 
 
 def aligned16(*tensors):
@@ -1320,8 +1312,7 @@ def batchnorm_add_relu_fwd(x, residual, gamma, beta, run_mean, run_var, eps, mom
     mean = torch.empty(C, dtype=torch.float32, device=x.device)
     rstd = torch.empty(C, dtype=torch.float32, device=x.device)
     _check(lib().scda_batchnorm_add_relu_fwd_hip(_p(x), _p(residual), _p(y), _p(gamma), _p(beta), _p(run_mean), _p(run_var), _p(mean),
-                                                 _p(rstd), i32(B), i32(C), i32(H * W), f32(eps), f32(momentum), _stream()),
-           "scda_batchnorm_add_relu_fwd_hip")
+                                                 _p(rstd), B, C, H * W, eps, momentum, _stream()), "scda_batchnorm_add_relu_fwd_hip")
     return y, mean, rstd
 
 
@@ -1334,7 +1325,7 @@ def batchnorm_add_relu_bwd(dy, x, y, gamma, beta, mean, rstd, need_dx=True, out=
     dg, db = out if out is not None else (torch.empty(C, dtype=torch.float32, device=x.device),
                                           torch.empty(C, dtype=torch.float32, device=x.device))
     _check(lib().scda_batchnorm_add_relu_bwd_hip(_p(dy), _p(x), _p(y), _p(gamma), _p(beta), _p(mean), _p(rstd), _p(dx), _p(dres), _p(dg),
-                                                 _p(db), i32(B), i32(C), i32(H * W), i32(0 if out is None else 1), _stream()),
+                                                 _p(db), B, C, H * W, 0 if out is None else 1, _stream()),
            "scda_batchnorm_add_relu_bwd_hip")
     return dx, dres, dg, db
 
@@ -1346,8 +1337,8 @@ def batchnorm_eval(x, gamma, beta, run_mean, run_var, eps, act, slope, dy=None):
         _req(dy, "dy")
     B, C, H, W = x.shape
     out = torch.empty_like(x)
-    _check(lib().scda_batchnorm_eval_hip(_p(x), _p(dy), _p(out), _p(gamma), _p(beta), _p(run_mean), _p(run_var), i32(B), i32(C),
-                                         i32(H * W), f32(eps), i32(act), f32(slope), _stream()), "scda_batchnorm_eval_hip")
+    _check(lib().scda_batchnorm_eval_hip(_p(x), _p(dy), _p(out), _p(gamma), _p(beta), _p(run_mean), _p(run_var), B, C, H * W, eps, act,
+                                         slope, _stream()), "scda_batchnorm_eval_hip")
     return out
 
 
@@ -1355,14 +1346,14 @@ def upsample2x_fwd(x):
     _req(x, "x")
     B, C, H, W = x.shape
     y = torch.empty(B, C, 2 * H, 2 * W, dtype=torch.float32, device=x.device)
-    _check(lib().scda_upsample2x_fwd_hip(_p(x), _p(y), i32(B * C), i32(H), i32(W), _stream()), "scda_upsample2x_fwd_hip")
+    _check(lib().scda_upsample2x_fwd_hip(_p(x), _p(y), B * C, H, W, _stream()), "scda_upsample2x_fwd_hip")
     return y
 
 
 def instnorm_up2_ok(x):
     """instance norm + the bilinear x2 behind it can run as one launch on this tensor (scda_instnorm_up2_supported + alignment)"""
     return (x.dim() == 4 and x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and aligned16(x)
-            and bool(lib().scda_instnorm_up2_supported(i32(x.shape[2]), i32(x.shape[3]))))
+            and bool(lib().scda_instnorm_up2_supported(x.shape[2], x.shape[3])))
 
 
 def instnorm_up2_fwd(x, eps, act, slope):
@@ -1372,8 +1363,8 @@ def instnorm_up2_fwd(x, eps, act, slope):
     y2 = torch.empty(B, C, 2 * H, 2 * W, dtype=torch.float32, device=x.device)
     mean = torch.empty(B * C, dtype=torch.float32, device=x.device)
     rstd = torch.empty(B * C, dtype=torch.float32, device=x.device)
-    _check(lib().scda_instnorm_up2_fwd_hip(_p(x), _p(y2), _p(mean), _p(rstd), i32(B * C), i32(H), i32(W), f32(eps), i32(act), f32(slope),
-                                           _stream()), "scda_instnorm_up2_fwd_hip")
+    _check(lib().scda_instnorm_up2_fwd_hip(_p(x), _p(y2), _p(mean), _p(rstd), B * C, H, W, eps, act, slope, _stream()),
+           "scda_instnorm_up2_fwd_hip")
     return y2, mean, rstd
 
 
@@ -1388,12 +1379,11 @@ def instnorm_drop_add_up2_fwd(x, residual, eps, p, seed):
     rstd = torch.empty(B * C, dtype=torch.float32, device=x.device)
     if torch.is_tensor(seed):     # a slot of a scda_amd.seeds.SeedArena (see instnorm_drop_add_fwd)
         _req(seed, "seed", torch.int64)
-        _check(lib().scda_instnorm_drop_add_up2_fwd_dev_hip(_p(x), _p(residual), _p(y2), _p(mean), _p(rstd), i32(B * C), i32(H), i32(W),
-                                                            f32(eps), f32(p), _p(seed), f32(1.0 / (1.0 - p)), _stream()),
-               "scda_instnorm_drop_add_up2_fwd_dev_hip")
+        _check(lib().scda_instnorm_drop_add_up2_fwd_dev_hip(_p(x), _p(residual), _p(y2), _p(mean), _p(rstd), B * C, H, W, eps, p, _p(seed),
+                                                            1.0 / (1.0 - p), _stream()), "scda_instnorm_drop_add_up2_fwd_dev_hip")
         return y2, mean, rstd
-    _check(lib().scda_instnorm_drop_add_up2_fwd_hip(_p(x), _p(residual), _p(y2), _p(mean), _p(rstd), i32(B * C), i32(H), i32(W), f32(eps),
-                                                    f32(p), u64(seed & 0xFFFFFFFFFFFFFFFF), f32(1.0 / (1.0 - p)), _stream()),
+    _check(lib().scda_instnorm_drop_add_up2_fwd_hip(_p(x), _p(residual), _p(y2), _p(mean), _p(rstd), B * C, H, W, eps, p,
+                                                    seed & 0xFFFFFFFFFFFFFFFF, 1.0 / (1.0 - p), _stream()),
            "scda_instnorm_drop_add_up2_fwd_hip")
     return y2, mean, rstd
 
@@ -1403,8 +1393,8 @@ def instnorm_up2_bwd(dy2, x, mean, rstd, act, slope):
     _req(dy2, "dy2"); _req(x, "x")
     B, C, H, W = x.shape
     dx = torch.empty_like(x)
-    _check(lib().scda_instnorm_up2_bwd_hip(_p(dy2), _p(x), _p(mean), _p(rstd), _p(dx), i32(B * C), i32(H), i32(W), i32(act), f32(slope),
-                                           _stream()), "scda_instnorm_up2_bwd_hip")
+    _check(lib().scda_instnorm_up2_bwd_hip(_p(dy2), _p(x), _p(mean), _p(rstd), _p(dx), B * C, H, W, act, slope, _stream()),
+           "scda_instnorm_up2_bwd_hip")
     return dx
 
 
@@ -1415,11 +1405,11 @@ def instnorm_drop_up2_bwd(dy2, x, mean, rstd, p, seed):
     dx = torch.empty_like(x)
     dres = torch.empty_like(x)
     if torch.is_tensor(seed):
-        _check(lib().scda_instnorm_drop_up2_bwd_dev_hip(_p(dy2), _p(x), _p(mean), _p(rstd), _p(dx), _p(dres), i32(B * C), i32(H), i32(W), f32(p),
-                                                        _p(seed), f32(1.0 / (1.0 - p)), _stream()), "scda_instnorm_drop_up2_bwd_dev_hip")
+        _check(lib().scda_instnorm_drop_up2_bwd_dev_hip(_p(dy2), _p(x), _p(mean), _p(rstd), _p(dx), _p(dres), B * C, H, W, p, _p(seed),
+                                                        1.0 / (1.0 - p), _stream()), "scda_instnorm_drop_up2_bwd_dev_hip")
         return dx, dres
-    _check(lib().scda_instnorm_drop_up2_bwd_hip(_p(dy2), _p(x), _p(mean), _p(rstd), _p(dx), _p(dres), i32(B * C), i32(H), i32(W), f32(p),
-                                                u64(seed & 0xFFFFFFFFFFFFFFFF), f32(1.0 / (1.0 - p)), _stream()), "scda_instnorm_drop_up2_bwd_hip")
+    _check(lib().scda_instnorm_drop_up2_bwd_hip(_p(dy2), _p(x), _p(mean), _p(rstd), _p(dx), _p(dres), B * C, H, W, p,
+                                                seed & 0xFFFFFFFFFFFFFFFF, 1.0 / (1.0 - p), _stream()), "scda_instnorm_drop_up2_bwd_hip")
     return dx, dres
 
 
@@ -1427,7 +1417,7 @@ def upsample2x_bwd(dy):
     _req(dy, "dy")
     B, C, OH, OW = dy.shape
     dx = torch.empty(B, C, OH // 2, OW // 2, dtype=torch.float32, device=dy.device)
-    _check(lib().scda_upsample2x_bwd_hip(_p(dy), _p(dx), i32(B * C), i32(OH // 2), i32(OW // 2), _stream()), "scda_upsample2x_bwd_hip")
+    _check(lib().scda_upsample2x_bwd_hip(_p(dy), _p(dx), B * C, OH // 2, OW // 2, _stream()), "scda_upsample2x_bwd_hip")
     return dx
 
 
@@ -1436,13 +1426,13 @@ def bce_fwd(p, t):
     if p.numel() != t.numel():
         raise ValueError("bce: shape mismatch")
     out = torch.empty(1, dtype=torch.float32, device=p.device)
-    _check(lib().scda_bce_fwd_hip(_p(p), _p(t), i32(p.numel()), _p(out), _stream()), "scda_bce_fwd_hip")
+    _check(lib().scda_bce_fwd_hip(_p(p), _p(t), p.numel(), _p(out), _stream()), "scda_bce_fwd_hip")
     return out
 
 
 def bce_bwd(p, t, g):
     dp = torch.empty_like(p)
-    _check(lib().scda_bce_bwd_hip(_p(p), _p(t), i32(p.numel()), _p(g), _p(dp), _stream()), "scda_bce_bwd_hip")
+    _check(lib().scda_bce_bwd_hip(_p(p), _p(t), p.numel(), _p(g), _p(dp), _stream()), "scda_bce_bwd_hip")
     return dp
 
 
@@ -1450,7 +1440,7 @@ def avg2x2s1_fwd(x):
     _req(x, "x")
     B, C, H1, W1 = x.shape
     y = torch.empty(B, C, H1 - 1, W1 - 1, dtype=torch.float32, device=x.device)
-    _check(lib().scda_avg2x2s1_fwd_hip(_p(x), _p(y), i32(B * C), i32(H1 - 1), i32(W1 - 1), _stream()), "scda_avg2x2s1_fwd_hip")
+    _check(lib().scda_avg2x2s1_fwd_hip(_p(x), _p(y), B * C, H1 - 1, W1 - 1, _stream()), "scda_avg2x2s1_fwd_hip")
     return y
 
 
@@ -1458,7 +1448,7 @@ def avg2x2s1_bwd(dy):
     _req(dy, "dy")
     B, C, H, W = dy.shape
     dx = torch.empty(B, C, H + 1, W + 1, dtype=torch.float32, device=dy.device)
-    _check(lib().scda_avg2x2s1_bwd_hip(_p(dy), _p(dx), i32(B * C), i32(H), i32(W), _stream()), "scda_avg2x2s1_bwd_hip")
+    _check(lib().scda_avg2x2s1_bwd_hip(_p(dy), _p(dx), B * C, H, W, _stream()), "scda_avg2x2s1_bwd_hip")
     return dx
 
 
@@ -1466,7 +1456,7 @@ def gap_fwd(x):
     _req(x, "x")
     B, C, H, W = x.shape
     y = torch.empty(B, C, dtype=torch.float32, device=x.device)
-    _check(lib().scda_gap_fwd_hip(_p(x), _p(y), i32(B * C), i32(H * W), _stream()), "scda_gap_fwd_hip")
+    _check(lib().scda_gap_fwd_hip(_p(x), _p(y), B * C, H * W, _stream()), "scda_gap_fwd_hip")
     return y
 
 
@@ -1474,7 +1464,7 @@ def gap_bwd(dy, x_shape):
     _req(dy, "dy")
     B, C, H, W = x_shape
     dx = torch.empty(B, C, H, W, dtype=torch.float32, device=dy.device)
-    _check(lib().scda_gap_bwd_hip(_p(dy), _p(dx), i32(B * C), i32(H * W), _stream()), "scda_gap_bwd_hip")
+    _check(lib().scda_gap_bwd_hip(_p(dy), _p(dx), B * C, H * W, _stream()), "scda_gap_bwd_hip")
     return dx
 
 
@@ -1482,14 +1472,14 @@ def row_mean(x):
     _req(x, "x")
     R, C = x.shape
     y = torch.empty(R, dtype=torch.float32, device=x.device)
-    _check(lib().scda_row_mean_hip(_p(x), _p(y), i32(R), i32(C), _stream()), "scda_row_mean_hip")
+    _check(lib().scda_row_mean_hip(_p(x), _p(y), R, C, _stream()), "scda_row_mean_hip")
     return y
 
 
 def adam_step(param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay, step, max_blocks=0):
     _req(param, "param"); _req(grad, "grad"); _req(exp_avg, "exp_avg"); _req(exp_avg_sq, "exp_avg_sq")
-    _check(lib().scda_adam_limited_hip(_p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), i64(param.numel()), f32(lr), f32(beta1),
-                                       f32(beta2), f32(eps), f32(weight_decay), i32(step), i32(max_blocks), _stream()), "scda_adam_hip")
+    _check(lib().scda_adam_limited_hip(_p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), param.numel(), lr, beta1, beta2, eps, weight_decay,
+                                       step, max_blocks, _stream()), "scda_adam_hip")
 
 
 def last_plan():
@@ -1509,11 +1499,10 @@ def plan_conv(direction, batch, cin, ih, iw, cout, k, stride, pad, row_period=0,
     needed; ws_bytes defaults to what the operators pass (scda_conv2d_workspace_bytes)"""
     L = lib()
     if ws_bytes is None:
-        L.scda_conv2d_workspace_bytes.restype = ctypes.c_size_t
-        ws_bytes = L.scda_conv2d_workspace_bytes(i32(batch), i32(cin), i32(ih), i32(iw), i32(cout), i32(k), i32(k), i32(stride), i32(pad))
+        ws_bytes = L.scda_conv2d_workspace_bytes(batch, cin, ih, iw, cout, k, k, stride, pad)
     out = (ctypes.c_int * 16)()
-    L.scda_debug_plan_conv(i32(("fwd", "dgrad", "wgrad", "wgrad_bias").index(direction)), i32(batch), i32(cin), i32(ih), i32(iw), i32(cout),
-                           i32(k), i32(k), i32(stride), i32(pad), i32(row_period), i32(int(aligned)), _sz(ws_bytes), out)
+    L.scda_debug_plan_conv(("fwd", "dgrad", "wgrad", "wgrad_bias").index(direction), batch, cin, ih, iw, cout, k, k, stride, pad,
+                           row_period, int(aligned), ws_bytes, out)
     return dict(zip(PLAN_FIELDS, out))
 
 
@@ -1522,8 +1511,7 @@ def plan_gemm(M, N, K, lda, ldb, trans_a=False, trans_b=False, aligned=True, ws_
     if ws_bytes is None:      # scda_gemm_workspace_bytes at 256 CUs (the entry itself asks the device)
         ws_bytes = max(16 * M * N * 4, 2 * 256 * 256 * 128 * 4)
     out = (ctypes.c_int * 16)()
-    lib().scda_debug_plan_gemm(i32(M), i32(N), i32(K), i32(lda), i32(ldb), i32(N if ldc is None else ldc), i32(int(trans_a)), i32(int(trans_b)),
-                               i32(int(aligned)), _sz(ws_bytes), out)
+    lib().scda_debug_plan_gemm(M, N, K, lda, ldb, N if ldc is None else ldc, int(trans_a), int(trans_b), int(aligned), ws_bytes, out)
     return dict(zip(PLAN_FIELDS, out))
 
 
@@ -1537,12 +1525,11 @@ def plan_wino(kind, batch, cin, ih, iw, cout, row_period=0, ws_bytes=None):
     what the operators pass"""
     L = lib()
     if ws_bytes is None:
-        L.scda_conv2d_workspace_bytes.restype = ctypes.c_size_t
-        ws_bytes = 0 if kind == "fwd_pool" else L.scda_conv2d_workspace_bytes(i32(batch), i32(cin), i32(ih), i32(iw), i32(cout), i32(3), i32(3), i32(1), i32(1))
+        ws_bytes = 0 if kind == "fwd_pool" else L.scda_conv2d_workspace_bytes(batch, cin, ih, iw, cout, 3, 3, 1, 1)
     C, M = (cout, cin) if kind.startswith("dgrad") else (cin, cout)      # the data gradient reduces over Cout
     fwd, wgrad = (ctypes.c_int * 9)(), (ctypes.c_int * 6)()
-    L.scda_debug_plan_wino(i32(batch), i32(C), i32(ih), i32(iw), i32(M), i32(wino_stacked(batch, ih, iw, row_period)), i32(int(kind == "fwd_pool")),
-                           i32(int(kind == "dgrad_mask")), i32(int(kind == "wgrad_bias")), _sz(ws_bytes), fwd, wgrad)
+    L.scda_debug_plan_wino(batch, C, ih, iw, M, wino_stacked(batch, ih, iw, row_period), int(kind == "fwd_pool"), int(kind == "dgrad_mask"),
+                           int(kind == "wgrad_bias"), ws_bytes, fwd, wgrad)
     return dict(zip(WINO_WGRAD_PLAN_FIELDS, wgrad)) if kind.startswith("wgrad") else dict(zip(WINO_PLAN_FIELDS, fwd))
 
 
@@ -1561,8 +1548,7 @@ def wino_last_order():
 # ------------------------------------------------------------ profiler ------
 def prof_kernel_names():
     L = lib()
-    L.scda_prof_kernel_name.restype = ctypes.c_char_p
-    return [L.scda_prof_kernel_name(i32(k)).decode() for k in range(L.scda_prof_num_kernels())]
+    return [L.scda_prof_kernel_name(k).decode() for k in range(L.scda_prof_num_kernels())]
 
 
 def prof_enable(kernels):
@@ -1576,22 +1562,21 @@ def prof_enable(kernels):
         mask = 0
         for k in kernels:
             mask |= 1 << names.index(k)
-    lib().scda_prof_enable(ctypes.c_uint(mask))
+    lib().scda_prof_enable(mask)
 
 
 def prof_collect():
     """after torch.cuda.synchronize(): {kernel name: (launches, total_ms, total_flops, total_algorithmic_bytes)} for the
     kernel classes that ran"""
     L = lib()
-    L.scda_prof_kernel_name.restype = ctypes.c_char_p
     n = L.scda_prof_num_kernels()
     launches = (ctypes.c_longlong * n)()
     ms = (ctypes.c_double * n)()
     fl = (ctypes.c_double * n)()
     by = (ctypes.c_double * n)()
     _check(L.scda_prof_collect(launches, ms, fl, by), "scda_prof_collect")
-    return {L.scda_prof_kernel_name(i32(k)).decode(): (int(launches[k]), float(ms[k]), float(fl[k]), float(by[k]))
-            for k in range(n) if launches[k] > 0}
+    return {L.scda_prof_kernel_name(k).decode(): (int(launches[k]), float(ms[k]), float(fl[k]),
+                                                  float(by[k])) for k in range(n) if launches[k] > 0}
 
 
 # ------------------------------------------------------------ data path -----
@@ -1605,13 +1590,11 @@ def image_resize_normalize(src, tables, out_h, out_w, normalize=True, mean=0.5, 
     for t, name in ((bh, "bounds_h"), (kh, "kk_h"), (bv, "bounds_v"), (kv, "kk_v")):
         _req(t, name, torch.int32)
     L = lib()
-    L.scda_image_resize_tmp_bytes.restype = ctypes.c_size_t
-    nb = int(L.scda_image_resize_tmp_bytes(i32(rows), i32(out_w), i32(C)))
+    nb = int(L.scda_image_resize_tmp_bytes(rows, out_w, C))
     tmp = torch.empty(nb, dtype=torch.uint8, device=src.device)
     out = torch.empty(C, out_h, out_w, dtype=torch.float32, device=src.device)
-    _check(L.scda_image_resize_normalize_hip(_p(src), i32(H), i32(W), i32(C), _p(bh), _p(kh), i32(ksh), i32(out_w), _p(bv), _p(kv),
-                                             i32(ksv), i32(out_h), i32(row0), i32(rows), _p(tmp), ctypes.c_size_t(nb),
-                                             i32(1 if normalize else 0), f32(mean), f32(std), i32(1 if flip else 0), _p(out), _stream()),
+    _check(L.scda_image_resize_normalize_hip(_p(src), H, W, C, _p(bh), _p(kh), ksh, out_w, _p(bv), _p(kv), ksv, out_h, row0, rows, _p(tmp),
+                                             nb, 1 if normalize else 0, mean, std, 1 if flip else 0, _p(out), _stream()),
            "scda_image_resize_normalize_hip")
     return out
 
