@@ -242,16 +242,17 @@ __global__ __launch_bounds__(256) void sigmoid_bce_rows_bwd_kernel(const float *
 // ------------------------------------------------------- bias gradients -----
 // db[c] (+)= sum_{b,p} dy[b][c][p].  Stage 1: grid (C, nsplit) -- each workgroup reduces one contiguous slice of a
 // channel's pixels (float4 loads), partial[c][s]; stage 2: one wave per channel adds the slices in fixed order.
+// vec4: dy is 16-byte aligned (decided by the launcher); with HW and s0 multiples of 4 every slice start then is too.
 __global__ __launch_bounds__(256) void bias_grad_partial_kernel(const float *__restrict__ dy, float *__restrict__ partial,
                                                                 const int B, const int C, const int HW,
-                                                                const int slice) {
+                                                                const int slice, const int vec4) {
     __shared__ float red[16];
     const int c = blockIdx.x, s0 = blockIdx.y * slice;
     const int s1 = min(HW, s0 + slice);
     float s = 0.f;
     for (int b = 0; b < B; ++b) {
         const float *p = dy + ((size_t)b * C + c) * HW;
-        if (((HW | s0) & 3) == 0) {
+        if (vec4 && ((HW | s0) & 3) == 0) {
             const float4 *p4 = reinterpret_cast<const float4 *>(p + s0);
             const int n4 = (s1 - s0) >> 2;
             for (int i = threadIdx.x; i < n4; i += blockDim.x) { const float4 v = p4[i]; s += (v.x + v.y) + (v.z + v.w); }
@@ -411,7 +412,7 @@ __global__ __launch_bounds__(256) void smooth_l1_bwd_kernel(const float *__restr
 // HBM-bound: the plane is read ONCE with float4 loads and kept in registers across the mean / centred-variance /
 // normalise passes when it fits (VPT float4 per thread: 64x64, 128x128 and 256x256 planes = VPT 1, 4, 16); other sizes
 // take the generic path, which re-reads the plane (L2) with scalar loads.  Two-pass statistics (mean, then centred sum of
-// squares), fixed reduction order.
+// squares), fixed reduction order; the generic path also carries the centred values' own mean (the corrected two-pass form).
 __device__ __forceinline__ float inorm_act(float o, const int act, const float slope) {
     if (act == 1) return o > 0.f ? o : 0.f;
     if (act == 2) return o > 0.f ? o : o * slope;
@@ -478,10 +479,18 @@ __global__ __launch_bounds__(1024) void instnorm_fwd_kernel(const float *__restr
         float s = 0.f;
         for (int i = threadIdx.x; i < HW; i += blockDim.x) s += x[base + i];
         mean = block_sum(s, red) / (float)HW;
-        float q = 0.f;
-        for (int i = threadIdx.x; i < HW; i += blockDim.x) { const float d = x[base + i] - mean; q += d * d; }
-        rstd = 1.f / sqrtf(block_sum(q, red) / (float)HW + eps);
-        for (int i = threadIdx.x; i < HW; i += blockDim.x) y[base + i] = tail(inorm_act((x[base + i] - mean) * rstd, act, slope), base + i);
+        // corrected two-pass: c = mean of the centred values = what the fp32 `mean` lost to rounding (up to an ulp of the mean, which
+        // is most of a standard deviation for a plane of mean 1e3 and std 1e-2); it is taken off every centred value and off the
+        // variance.  The generic backward recomputes the same c from x and the saved mean (one more pass over the L2-resident plane), so
+        // a generic forward and a generic backward see one xh.  The launchers choose per call (forward: x, y, residual aligned;
+        // backward: x, dy, dx), so a pair can mix this form with the register form, which has no c: their xh then differ by
+        // c * rstd, at most an ulp of the mean in units of the standard deviation.
+        float q = 0.f, r = 0.f;
+        for (int i = threadIdx.x; i < HW; i += blockDim.x) { const float d = x[base + i] - mean; r += d; q += d * d; }
+        const float c = block_sum(r, red) / (float)HW;
+        rstd = 1.f / sqrtf(fmaxf(block_sum(q, red) / (float)HW - c * c, 0.f) + eps);
+        for (int i = threadIdx.x; i < HW; i += blockDim.x)
+            y[base + i] = tail(inorm_act(((x[base + i] - mean) - c) * rstd, act, slope), base + i);
     }
     if (threadIdx.x == 0) { mean_out[blockIdx.x] = mean; rstd_out[blockIdx.x] = rstd; }
 }
@@ -559,9 +568,12 @@ __global__ __launch_bounds__(1024) void instnorm_bwd_kernel(const float *__restr
             if (act == 2) return xh > 0.f ? g : g * slope;
             return g;
         };
+        float r = 0.f;      // the forward's centre correction, recomputed in the forward's order: the same bits
+        for (int i = threadIdx.x; i < HW; i += blockDim.x) r += x[base + i] - mean;
+        const float c = block_sum(r, red) / (float)HW;
         float s1 = 0.f, s2 = 0.f;
         for (int i = threadIdx.x; i < HW; i += blockDim.x) {
-            const float xh = (x[base + i] - mean) * rstd;
+            const float xh = ((x[base + i] - mean) - c) * rstd;
             const float g = gate(drop(dy[base + i], base + i), xh);
             s1 += g;
             s2 += g * xh;
@@ -569,7 +581,7 @@ __global__ __launch_bounds__(1024) void instnorm_bwd_kernel(const float *__restr
         const float m1 = block_sum(s1, red) / (float)HW;
         const float m2 = block_sum(s2, red) / (float)HW;
         for (int i = threadIdx.x; i < HW; i += blockDim.x) {
-            const float xh = (x[base + i] - mean) * rstd;
+            const float xh = ((x[base + i] - mean) - c) * rstd;
             dx[base + i] = rstd * (gate(drop(dy[base + i], base + i), xh) - m1 - xh * m2);
         }
     }
@@ -1084,11 +1096,11 @@ __global__ __launch_bounds__(1024) void instnorm_up2_fwd_kernel(const float *__r
 // (y0|y1) equals iy -- deterministic, no atomics.
 __device__ __forceinline__ void up2_candidates(int i, int In, int On, float s, int &lo, int &hi) {
     // outputs o with floor(s*o) in {i-1, i}:  o in [ceil((i-1)/s), floor((i+1)/s)] (clamped), checked exactly by the caller
+    if (In == 1) { lo = 0; hi = On - 1; return; }   // s = 0: every output reads the one input row / column
     lo = (int)floorf((float)(i - 1) / s) - 1;
     hi = (int)ceilf((float)(i + 1) / s) + 1;
     if (lo < 0) lo = 0;
     if (hi > On - 1) hi = On - 1;
-    (void)In;
 }
 
 // Separable gather: a workgroup owns one input row.  Pass A adds the (4-5) output rows that touch it, weighted, into an LDS
@@ -1491,7 +1503,8 @@ SCDA_API int scda_bias_grad_nchw_hip(const float *dy, float *db, int B, int C, i
     if (slice < 2048) slice = 2048;
     slice = (slice + 3) & ~3;
     nsplit = (HW + slice - 1) / slice;
-    hipLaunchKernelGGL(bias_grad_partial_kernel, dim3(C, nsplit), dim3(256), 0, as_stream(stream), dy, ws, B, C, HW, slice);
+    const int vec4 = (((uintptr_t)dy) & 15) == 0;   // a contiguous view at an odd element offset takes the scalar loads
+    hipLaunchKernelGGL(bias_grad_partial_kernel, dim3(C, nsplit), dim3(256), 0, as_stream(stream), dy, ws, B, C, HW, slice, vec4);
     int rc = launch_status("bias_grad_partial_kernel");
     if (rc) return rc;
     hipLaunchKernelGGL(bias_grad_finish_kernel, dim3(cdiv(C, 256)), dim3(256), 0, as_stream(stream), (const float *)ws, db, C, nsplit, accumulate);
@@ -1743,7 +1756,7 @@ SCDA_API int scda_upsample2x_fwd_hip(const float *x, float *y, int planes, int I
 }
 
 SCDA_API int scda_upsample2x_bwd_hip(const float *dy, float *dx, int planes, int IH, int IW, void *stream) {
-    NN_CHECK(dy && dx && planes > 0 && IH > 1 && IW > 1, "scda_upsample2x_bwd_hip")
+    NN_CHECK(dy && dx && planes > 0 && IH > 0 && IW > 0, "scda_upsample2x_bwd_hip")
     const int OH = IH * 2, OW = IW * 2;
     if (OW > kUpMaxOW) { set_error("scda_upsample2x_bwd_hip: rows wider than %d are not supported", kUpMaxOW); return SCDA_EINVAL; }
     const bool row_at_a_time = getenv("SCDA_UPSAMPLE_BWD_ROWWISE") != nullptr;   // A/B knob (read per launch: the test compares both kernels)

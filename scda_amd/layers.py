@@ -291,6 +291,8 @@ class BatchNorm2d(nn.BatchNorm2d):
                                            self.eps, self.fused_act, self.slope)
         if self.momentum is None:   # cumulative moving average: needs the counter on the device at every call; no SCDA net uses it
             raise NotImplementedError("scda_amd.BatchNorm2d: momentum=None (cumulative average) is not implemented")
+        if x.dim() == 4 and x.shape[0] * x.shape[2] * x.shape[3] == 1:   # as F.batch_norm: the unbiased running variance is n / (n - 1)
+            raise ValueError(f"Expected more than 1 value per channel when training, got input size {tuple(x.shape)}")
         if self.num_batches_tracked is not None:
             self._nbt_pending = getattr(self, "_nbt_pending", 0) + 1    # counted on the host, written into the buffer when it is read
         if P.replay() is not None and self.fused_act != A.ACT_NONE:   # parity tests: see InstanceNorm2d
