@@ -16,8 +16,10 @@ from scda_amd.autograd_ops import ACT_LEAKY, ACT_NONE, ACT_RELU, AddFn, InstNorm
 from scda_amd.dropin.models.faster_rcnn.init import gaussian_weights_init, xavier_weights_init  # noqa: F401
 
 
-class INSResBlock(nn.Module):
-    """x + [conv3x3 - IN - ReLU - conv3x3 - IN - (Dropout)](x)"""
+class INSResBlock(L.FusedProducer, nn.Module):
+    """x + [conv3x3 - IN - ReLU - conv3x3 - IN - (Dropout)](x); the fused tail may also run the Upsample2x behind this block, if the
+    block's output feeds nothing else (layers.pair_norm_upsample)"""
+    _fusion_off_switch = "SCDA_NO_NORM_UP_FUSION"
 
     def conv3x3(self, inplanes, out_planes, stride=1):
         return L.Conv2d(inplanes, out_planes, kernel_size=3, stride=stride, padding=1)
@@ -30,12 +32,6 @@ class INSResBlock(nn.Module):
             seq.append(L.Dropout(p=dropout))
         self.model = nn.Sequential(*seq)
         self.model.apply(gaussian_weights_init)
-        self._up_ref = None      # layers.pair_norm_upsample: the Upsample2x behind this block, if this block's output feeds nothing else
-
-    def __getstate__(self):
-        state = dict(self.__dict__)
-        state["_up_ref"] = None
-        return state
 
     def tail_fusable(self):
         """IN -> Dropout -> (+ x) of this block can run as one launch each way (training mode, a real dropout rate)"""
@@ -50,11 +46,11 @@ class INSResBlock(nn.Module):
             # Dropout module draws it, so the torch generator is consumed identically
             h = self.model[:-2](x)
             seed = seeds.draw()      # an int, or a device slot while the trainer records a hipGraph (scda_amd/seeds.py)
-            up = L.my_upsample(self)
+            up = self.fused_consumer()
             if up is not None and N.instnorm_up2_ok(h) and x.is_contiguous() and N.aligned16(x):
                 # ... and the Interpolate of the up-sampling block behind this (the decoder's last) residual block in the same launch
                 y2 = InstNormDropAddUpFn.apply(h, x, tail[0].eps, tail[1].p, seed)
-                up.expect_upsampled(tuple(y2.shape))
+                up.announce(tuple(y2.shape))
                 return y2
             return InstNormDropAddFn.apply(h, x, tail[0].eps, tail[1].p, seed)
         return AddFn.apply(self.model(x), x)

@@ -17,7 +17,71 @@ from . import native as N
 from . import probe as P
 
 
-class Conv2d(nn.Conv2d):
+class FusedProducer:
+    """Producer side of the ONE hand-over protocol between a module and the only consumer of its output (Conv2d -> MaxPool2x2,
+    InstanceNorm2d / INSResBlock -> Upsample2x): the producer may run the consumer's operation in its own launch and hand the finished
+    tensor over.  The hand-over is structural: the producer tells ITS consumer module (a weak reference set by the plan) that the tensor
+    it is about to receive is finished, with the shape to expect -- not an attribute on the tensor, which a hook or wrapper that returns
+    a new tensor (detach, clone, checkpointing) would drop, running the operation a second time without a word."""
+    _consumer_ref = None           # weak reference to the consumer (hand_over_to)
+    _fusion_off_switch = None      # name of an environment variable that, when set, keeps this kind of producer un-fused
+
+    def hand_over_to(self, consumer):
+        """declare that `consumer` (a FusedConsumer) is the ONLY reader of this module's output"""
+        self._consumer_ref = weakref.ref(consumer)
+        consumer._producer = weakref.ref(self)
+
+    def fused_consumer(self):
+        """the consumer paired with THIS module object, or None.  The pairing is checked from both sides: a shallow copy of the model
+        (nn.DataParallel replicas copy __dict__) carries the original's weak reference, but the original's consumer names the original
+        as its producer -- the copy then simply runs un-fused instead of signalling a consumer it does not feed.  An announcement left
+        behind by a call that raised between the two modules is cleared.  A forward hook on the producer, or a forward (pre-)hook on
+        the consumer, is owed the tensor the module nominally produces / receives: such a pair runs the separate launches."""
+        consumer = self._consumer_ref() if self._consumer_ref is not None else None
+        if consumer is None or consumer._producer is None or consumer._producer() is not self:
+            return None
+        consumer._announced = None
+        if self._forward_hooks or consumer._forward_pre_hooks or consumer._forward_hooks:
+            return None
+        if self._fusion_off_switch and os.environ.get(self._fusion_off_switch):
+            return None
+        return consumer
+
+    def __getstate__(self):
+        # copy.deepcopy / pickle / torch.save(model): weak references do not travel.  The copy runs un-fused until it is planned again
+        # (the model constructors do that; a deep copy of a planned model can call plan_act_fusion / pair_decoder_upsamples again).
+        state = dict(self.__dict__)
+        state.pop("_consumer_ref", None)
+        return state
+
+
+class FusedConsumer:
+    """Consumer side: passes a tensor its producer announced through, after checking that it IS the announced one."""
+    _producer = None               # weak reference to the producer (FusedProducer.hand_over_to)
+    _announced = None              # set by the producer when IT ran this module's operation: the shape of the tensor to pass through
+    _done_in_front = ""            # "<who> in front <did what>", for the arrival check's message
+
+    def announce(self, shape):
+        self._announced = shape
+
+    def handed_over(self, x):
+        """True when x is the finished tensor the producer announced; the announcement is consumed either way"""
+        if self._announced is None:
+            return False
+        want, self._announced = self._announced, None
+        if tuple(x.shape) != want:
+            raise RuntimeError("%s: the %s and announced %s, but a tensor of shape %s arrived (a hook between the two modules?)"
+                               % (type(self).__name__, self._done_in_front, want, tuple(x.shape)))
+        return True
+
+    def __getstate__(self):
+        state = dict(self.__dict__)
+        state.pop("_producer", None)
+        state.pop("_announced", None)
+        return state
+
+
+class Conv2d(FusedProducer, nn.Conv2d):
     """nn.Conv2d with an optional activation fused into the MFMA kernel's epilogue."""
 
     def __init__(self, *args, fused_act=A.ACT_NONE, slope=0.01, **kw):
@@ -34,41 +98,21 @@ class Conv2d(nn.Conv2d):
         # > 0: the input is a vertical stack of independent maps of that many rows (the channel-major RoI-head layout
         # [1, C, R*7, 7] of the ResNet-C4 detector); set per call by the owner (dropin/models/mask_rcnn/resnet.py)
         self.row_period = 0
-        # fusion plan: a MaxPool2x2 consumes this conv's ReLU output (plan_act_fusion): the pool can run in this conv's epilogue.
-        # The hand-over is structural: the conv tells ITS pool module (a weak reference set by the plan) that the tensor it is about
-        # to receive is already pooled, with the shape to expect -- not an attribute on the tensor, which a hook or wrapper that
-        # returns a new tensor (detach, clone, checkpointing) would drop, pooling a second time without a word.
-        self.pool_next = False
-        self._pool_ref = None
 
-    def _my_pool(self):
-        """the MaxPool2x2 the fusion plan paired with THIS module object, or None.  The pairing is checked from both sides: a shallow
-        copy of the model (nn.DataParallel replicas copy __dict__) carries the original's weak reference, but the original's pool names
-        the original conv as its producer -- the copy then simply runs un-fused instead of signalling a pool it does not feed."""
-        pool = self._pool_ref() if self._pool_ref is not None else None
-        if pool is None or pool._producer is None or pool._producer() is not self:
-            return None
-        return pool
-
-    def __getstate__(self):
-        # copy.deepcopy / pickle / torch.save(model): weak references do not travel.  The copy runs un-fused until plan_act_fusion is
-        # called on it (the model constructors do that; a deep copy of a planned model can call it again).
-        state = dict(self.__dict__)
-        state["_pool_ref"] = None
-        state["pool_next"] = False
-        return state
+    @property
+    def pool_next(self):
+        """fusion plan: a MaxPool2x2 consumes this conv's ReLU output (plan_act_fusion) and can run in this conv's epilogue"""
+        return self._consumer_ref is not None
 
     def forward(self, x):
-        pool = self._my_pool() if self.pool_next else None
-        if pool is not None:
-            pool._pooled_shape = None        # (an announcement left behind by a call that raised between this conv and its pool)
+        pool = self.fused_consumer()
         if pool is not None and P.replay() is None and self.fused_act == A.ACT_RELU and self.defer_act_bwd:
             B, Cin, IH, IW = x.shape
             if x.is_cuda and N.conv_pool_fusable(B, Cin, IH, IW, self.out_channels, self.kernel_size[0], self.kernel_size[1],
                                                  self.stride[0], self.padding[0], self.row_period):
                 # conv + ReLU + the 2x2 max-pool behind it in one launch; the pool module recognises the pooled tensor and passes it on
                 y = A.ConvPoolFn.apply(x, self.weight, self.bias, self.slope, self.input_act)
-                pool.expect_pooled(tuple(y.shape))
+                pool.announce(tuple(y.shape))
                 return y
         return A.conv2d(x, self.weight, self.bias, self.stride[0], self.padding[0], self.fused_act, self.slope,
                         (self.input_act, self.defer_act_bwd), self.row_period)
@@ -133,26 +177,12 @@ class Linear(nn.Linear):
         return A.linear(x, self.weight, self.bias, self.fused_act, self.defer_act_bwd)
 
 
-class MaxPool2x2(nn.Module):
+class MaxPool2x2(FusedConsumer, nn.Module):
     relu_input = False             # fusion plan: this pool's backward also applies the ReLU gradient of the conv in front of it
-    _pooled_shape = None           # set by the conv in front (Conv2d.forward) when IT pooled: the shape of the tensor to pass through
-    _producer = None               # weak reference to that conv (plan_act_fusion): see Conv2d._my_pool
-
-    def __getstate__(self):
-        state = dict(self.__dict__)
-        state["_producer"] = None
-        state["_pooled_shape"] = None
-        return state
-
-    def expect_pooled(self, shape):
-        self._pooled_shape = shape
+    _done_in_front = "convolution in front pooled in its epilogue"
 
     def forward(self, x):
-        if self._pooled_shape is not None:     # the producing conv already pooled (layers.Conv2d.forward / A.ConvPoolFn)
-            want, self._pooled_shape = self._pooled_shape, None
-            if tuple(x.shape) != want:
-                raise RuntimeError("MaxPool2x2: the convolution in front pooled in its epilogue and announced %s, but a tensor of shape %s "
-                                   "arrived (a hook between the two modules?)" % (want, tuple(x.shape)))
+        if self.handed_over(x):                # the producing conv already pooled (layers.Conv2d.forward / A.ConvPoolFn)
             return x
         return A.MaxPool2x2Fn.apply(x, self.relu_input)
 
@@ -235,9 +265,7 @@ def plan_act_fusion(*sequentials):
                 a.defer_act_bwd, b.input_act = True, (a.fused_act, a.slope)
             elif isinstance(a, Conv2d) and a.fused_act == A.ACT_RELU and isinstance(b, MaxPool2x2):
                 a.defer_act_bwd, b.relu_input = True, True
-                a.pool_next = True
-                a._pool_ref = weakref.ref(b)
-                b._producer = weakref.ref(a)
+                a.hand_over_to(b)
             elif isinstance(a, Linear) and a.fused_act == A.ACT_RELU and isinstance(b, Dropout):
                 a.defer_act_bwd, b.relu_input = True, True
             else:
@@ -246,8 +274,10 @@ def plan_act_fusion(*sequentials):
     return n
 
 
-class InstanceNorm2d(nn.Module):
-    """nn.InstanceNorm2d(C) (affine=False, track_running_stats=False) with optional fused activation."""
+class InstanceNorm2d(FusedProducer, nn.Module):
+    """nn.InstanceNorm2d(C) (affine=False, track_running_stats=False) with optional fused activation.  When an Upsample2x consumes
+    this norm's output and nothing else does (pair_norm_upsample), the norm's launch may write the up-sampled map."""
+    _fusion_off_switch = "SCDA_NO_NORM_UP_FUSION"
 
     def __init__(self, num_features, eps=1e-5, fused_act=A.ACT_NONE, slope=0.01):
         super().__init__()
@@ -255,22 +285,16 @@ class InstanceNorm2d(nn.Module):
         self.eps = eps
         self.fused_act = fused_act
         self.slope = slope
-        self._up_ref = None        # weak reference to the Upsample2x that consumes this norm's output and nothing else does (pair_norm_upsample)
-
-    def __getstate__(self):
-        state = dict(self.__dict__)
-        state["_up_ref"] = None     # weak references do not travel (see Conv2d.__getstate__): a copy runs un-fused until paired again
-        return state
 
     def forward(self, x):
         if P.replay() is not None and self.fused_act != A.ACT_NONE:   # parity tests: activation un-fused so its mask can be replayed
             y = A.InstanceNormFn.apply(x, self.eps, A.ACT_NONE, self.slope)
             return A.ActFn.apply(y, 0 if self.fused_act == A.ACT_RELU else 1, self.slope)
-        up = my_upsample(self)
+        up = self.fused_consumer()
         if up is not None and N.instnorm_up2_ok(x):
             # the norm AND the bilinear x2 behind it in one launch; the Upsample2x module recognises the up-sampled tensor and passes it on
             y2 = A.InstanceNormUpFn.apply(x, self.eps, self.fused_act, self.slope)
-            up.expect_upsampled(tuple(y2.shape))
+            up.announce(tuple(y2.shape))
             return y2
         return A.InstanceNormFn.apply(x, self.eps, self.fused_act, self.slope)
 
@@ -352,48 +376,22 @@ def flush_counters(module):
             _flush_nbt(m)
 
 
-class Upsample2x(nn.Module):
+class Upsample2x(FusedConsumer, nn.Module):
     """Interpolate(scale_factor=2, mode='bilinear', align_corners=True).  In the decoders its input is the output of an instance norm
     that nothing else reads (pair_norm_upsample): that norm's launch then writes the up-sampled map itself and announces it here --
-    the hand-over is structural, as Conv2d -> MaxPool2x2's (a shape announced by the producer, checked on arrival)."""
-    _upsampled_shape = None        # set by the producer when IT up-sampled: the shape of the tensor to pass through
-    _producer = None               # weak reference to that producer (an InstanceNorm2d, or the INSResBlock whose fused tail holds the norm)
-
-    def __getstate__(self):
-        state = dict(self.__dict__)
-        state["_producer"] = None
-        state["_upsampled_shape"] = None
-        return state
-
-    def expect_upsampled(self, shape):
-        self._upsampled_shape = shape
+    the hand-over is FusedProducer / FusedConsumer's, as Conv2d -> MaxPool2x2's."""
+    _done_in_front = "instance norm in front up-sampled in its own launch"
 
     def forward(self, x):
-        if self._upsampled_shape is not None:
-            want, self._upsampled_shape = self._upsampled_shape, None
-            if tuple(x.shape) != want:
-                raise RuntimeError("Upsample2x: the instance norm in front up-sampled in its own launch and announced %s, but a tensor of "
-                                   "shape %s arrived (a hook between the two modules?)" % (want, tuple(x.shape)))
+        if self.handed_over(x):
             return x
         return A.Upsample2xFn.apply(x)
-
-
-def my_upsample(producer):
-    """the Upsample2x paired with THIS producer object (pair_norm_upsample), or None; checked from both sides like Conv2d._my_pool, and
-    a stale announcement (a call that raised between producer and consumer) is cleared"""
-    ref = getattr(producer, "_up_ref", None)
-    up = ref() if ref is not None else None
-    if up is None or up._producer is None or up._producer() is not producer or os.environ.get("SCDA_NO_NORM_UP_FUSION"):
-        return None
-    up._upsampled_shape = None
-    return up
 
 
 def pair_norm_upsample(producer, up):
     """declare that `up` (an Upsample2x) is the ONLY consumer of `producer`'s output (an InstanceNorm2d, or a module that runs one in a
     fused tail): the producer may then write the up-sampled map itself"""
-    producer._up_ref = weakref.ref(up)
-    up._producer = weakref.ref(producer)
+    producer.hand_over_to(up)
 
 
 class GlobalAvgPool(nn.Module):

@@ -70,29 +70,25 @@ def builder_gan(cluster_num=4, threshold=128, recon_size=256, neww=64, newh=64):
     return GAN_dis_AE(params_dis), GAN_decoder_AE(params_dec), GAN_dis_AE_patch(params_patch)
 
 
-def _soft(flag, shape, device):
-    """generate_soft_label: U(0.8,1) for 1, U(0,0.3) for 0, drawn from numpy's global RNG (:440-448)"""
-    lo, hi = (0.8, 1.0) if flag == 1 else (0.0, 0.3)
-    return N.upload(np.random.uniform(lo, hi, size=tuple(shape)), device, torch.float32)
+# generate_soft_label ('s': U(0.8,1) for 1, U(0,0.3) for 0) and generate_hard_label ('h': constant, but still one numpy draw per
+# element), both from numpy's global RNG (:440-458)
+_LABEL_RANGE = {('s', 1): (0.8, 1.0), ('s', 0): (0.0, 0.3), ('h', 1): (1.0, 1.0), ('h', 0): (0.0, 0.0)}
+
+
+def _draw(kind, flag, shape):
+    lo, hi = _LABEL_RANGE[kind, flag]
+    return np.random.uniform(lo, hi, size=tuple(shape))
 
 
 def _hard(flag, shape, device):
-    """generate_hard_label: constant, but still one numpy draw per element (:450-458)"""
-    v = 1.0 if flag == 1 else 0.0
-    return N.upload(np.random.uniform(v, v, size=tuple(shape)), device, torch.float32)
+    return N.upload(_draw('h', flag, shape), device, torch.float32)
 
 
 def _labels(specs, device):
-    """several label tensors in ONE host-to-device copy: specs = [(kind, flag, shape)], kind 's' (generate_soft_label) or 'h'
-    (generate_hard_label), drawn in this order from numpy's global RNG exactly as the separate calls would (the reference's order of
-    draws, :442-458).  Each upload is a tiny copy on the compute stream, and the GAN phases are a chain of tiny launches."""
-    draws = []
-    for kind, flag, shape in specs:
-        if kind == 's':
-            lo, hi = (0.8, 1.0) if flag == 1 else (0.0, 0.3)
-        else:
-            lo = hi = 1.0 if flag == 1 else 0.0
-        draws.append(np.random.uniform(lo, hi, size=tuple(shape)).astype(np.float32))
+    """several label tensors in ONE host-to-device copy: specs = [(kind, flag, shape)], drawn in this order from numpy's global RNG
+    exactly as the separate calls would (the reference's order of draws, :442-458).  Each upload is a tiny copy on the compute stream,
+    and the GAN phases are a chain of tiny launches."""
+    draws = [_draw(*spec).astype(np.float32) for spec in specs]
     offs, total = [], 0
     for d in draws:
         offs.append(total)
@@ -128,22 +124,62 @@ class _Frozen:
             p.requires_grad_(True)
 
 
+# The GAN part of the iteration as three regions without a host decision inside (ScdaTrainer._region_a / _b / _c):
+#   keys    the entries of the iteration's tensor dict the region reads (as a hipGraph: copied into the recorded tensors)
+#   copies  output positions handed out as copies, because they outlive the region's next replay
+#   nets    the nets whose all-reduce belongs to the region (data parallel), in the order the eager region issues them
+REGIONS = {
+    'a': {'keys': ('src_patch', 'tgt_patch', 'x_small', 't_small', 'score1', 'score0', 'score0p', 'score1p'),
+          'copies': (2, 3), 'nets': ('dis', 'dis_patch')},
+    'b': {'keys': ('x_small', 't_small', 'tgt_patch', 'one_t', 'zero_t', 'one_s', 'zero_s'), 'copies': (0, 1), 'nets': ('dec',)},
+    'c': {'keys': ('src_patch', 'tgt_patch', 'ones_all', 'ones_row'), 'copies': (0, 1), 'nets': ()},
+}
+
+
+def run_region(graphs, name, t, fn, all_reduce):
+    """Run region `name`, fn(inputs, reduce) -> tuple of tensors, on the tensor dict t: eagerly (graphs is None, or in its two warm-up
+    iterations), or recorded as a hipGraph and replayed, or replayed.  The ONE place that makes this choice, and that decides who
+    issues the region's collectives, all_reduce(net name) -> work handle or None:
+        eager               fn issues each through `reduce` where the phase's gradients are final (the discriminators' right after
+                            phase 1's backward, underneath phase 2);
+        recorded / replayed a collective is a host call and cannot be recorded: `reduce` does nothing, and the region's all-reduces are
+                            issued here, behind the replay.
+    -> (outputs, {net name: work handle})"""
+    if graphs is not None and graphs.ready(name):
+        out = graphs.run(name, t)
+    elif graphs is not None and graphs.recording():
+        out = graphs.record(name, t, lambda st: fn(st, lambda net: None))
+    else:
+        works = {}
+
+        def reduce(net):
+            works[net] = all_reduce(net)
+        return fn(t, reduce), works
+    reg = REGIONS[name]
+    out = tuple(o.clone() if i in reg['copies'] else o for i, o in enumerate(out))
+    return out, {net: all_reduce(net) for net in reg['nets']}
+
+
 class _GanGraphs:
-    """hipGraphs of the three GAN regions of ScdaTrainer.step (A, B, C).  Two eager iterations first (planner caches, workspaces, packed
+    """hipGraphs of the three GAN regions of ScdaTrainer.step (REGIONS).  Two eager iterations first (planner caches, workspaces, packed
     weights, BN state), the third records each region -- `torch.cuda.graph` records the library's ctypes-launched kernels, the A / B
     fork-join on the branch stream and the autograd backward inside a region -- and replays it at once (recording does not execute);
     every later iteration copies the region's inputs into the recorded tensors, draws the dropout seeds of the region on the host in the
     eager modules' order (scda_amd/seeds.py) and replays.  All regions share one memory pool: B differentiates through the autograd graph
-    region A's recording built, whose saved activations live in that pool."""
-    KEYS = {'a': ('src_patch', 'tgt_patch', 'x_small', 't_small', 'score1', 'score0', 'score0p', 'score1p'),
-            'b': ('x_small', 't_small', 'tgt_patch', 'one_t', 'zero_t', 'one_s', 'zero_s'),
-            'c': ('src_patch', 'tgt_patch', 'ones_all', 'ones_row')}
+    region A's recording built, whose saved activations live in that pool.  record() and run() return the recorded output tensors
+    themselves; which of them are copied is run_region's business."""
 
     def __init__(self, trainer):
         from . import seeds
         self.tr, self.calls, self.reg, self.static = trainer, 0, {}, {}
         self.arena = seeds.SeedArena(trainer.device)
         self.pool = None
+        self._loaded = set()
+
+    def begin_iteration(self):
+        """at the top of every iteration that may use the graphs: counts it, and nothing is loaded yet"""
+        self.calls += 1
+        self._loaded = set()
 
     def ready(self, name):
         return name in self.reg
@@ -162,9 +198,8 @@ class _GanGraphs:
     def _load(self, name, t):
         """this iteration's inputs of region `name` into the recorded tensors -- each ONCE per iteration: B and C read what A loaded
         (and while B is being recorded, autograd still holds A's inputs as saved tensors: an in-place copy would invalidate them)"""
-        if name == 'a':
-            self._loaded = set()
-        for k in self.KEYS[name]:
+        keys = REGIONS[name]['keys']
+        for k in keys:
             if k in self._loaded:
                 continue
             self._loaded.add(k)
@@ -175,10 +210,10 @@ class _GanGraphs:
                 if dst.shape != t[k].shape:
                     raise RuntimeError("GAN hipGraph: input %s changed shape %s -> %s" % (k, tuple(dst.shape), tuple(t[k].shape)))
                 dst.copy_(t[k], non_blocking=True)
-        return {k: self.static[k] for k in self.KEYS[name]}
+        return {k: self.static[k] for k in keys}
 
     def record(self, name, t, fn):
-        """record region `name` (fn(static inputs) -> tuple of tensors / None) and run it once by replaying"""
+        """record region `name` (fn(static inputs) -> tuple of tensors) and run it once by replaying"""
         from . import seeds
         st = self._load(name, t)
         bns = self._bns()
@@ -212,35 +247,7 @@ class _GanGraphs:
 
     def run(self, name, t):
         self._load(name, t)
-        out = self._replay(name)
-        if name == 'a':
-            return out[0], out[1], out[2].clone(), out[3].clone()
-        if name == 'b':
-            return out[0].clone(), out[1].clone(), out[2]
-        return out[0].clone(), out[1].clone()
-
-
-class _recording:
-    """`with _recording(graphs, name, t) as rec: outs = rec(fn)`: run fn eagerly, or -- from the third iteration of a trainer with
-    hipGraphs enabled -- record it as region `name` and replay it"""
-
-    def __init__(self, graphs, name, t):
-        self.g, self.name, self.t = graphs, name, t
-
-    def __enter__(self):
-        def rec(fn):
-            if self.g is not None and self.g.recording():
-                out = self.g.record(self.name, self.t, fn)
-                if self.name == 'a':
-                    return out[0], out[1], out[2].clone(), out[3].clone(), None, None
-                if self.name == 'b':
-                    return out[0].clone(), out[1].clone(), out[2], None
-                return out[0].clone(), out[1].clone()
-            return fn(self.t)
-        return rec
-
-    def __exit__(self, *a):
-        return False
+        return self._replay(name)
 
 
 class ScdaTrainer:
@@ -281,6 +288,7 @@ class ScdaTrainer:
         for m in (self.model, self.dec, self.dis, self.dis_patch):
             m.train()
         named = (("det", self.model), ("dec", self.dec), ("dis", self.dis), ("dis_patch", self.dis_patch))
+        self.nets = dict(named)
         if reference_style:
             self.flat = {}
             self.opt = {k: torch.optim.Adam([p for p in m.parameters() if p.requires_grad], lr, betas=(0.9, 0.999),
@@ -290,7 +298,15 @@ class ScdaTrainer:
             self.opt = {k: FlatAdam(f, lr, betas=(0.9, 0.999), weight_decay=weight_decay) for k, f in self.flat.items()}
         self._warmup = None          # per-iteration schedulers while warming up (begin_warmup / end_warmup)
         self._epoch_sched = None     # per-epoch MultiStepLR (set_epoch_schedule / begin_epoch)
-        self._in_graph = False   # a GAN region is being recorded / replayed: its all-reduces are issued by step(), behind it
+        self._gg = None                # the GAN regions' hipGraphs (_GanGraphs), from the first iteration that may use them
+        self._graphable_nets = None    # _gan_graph_ok: no dropout of the GAN nets takes its seed as a kernel argument (decided once)
+        self._ones_row_cache = None
+        # element range of the detector bucket whose gradients are final behind the RoI head's backward (the model names the
+        # parameters: VGG.EARLY_REDUCE_PREFIXES), or None (SCDA_SEGMENTED_REDUCE=0, other detectors, a non-contiguous layout)
+        self._early_span = None
+        pre, flat = getattr(self.model, 'EARLY_REDUCE_PREFIXES', None), getattr(self.model, '_scda_flat', None)
+        if pre and flat is not None and os.environ.get("SCDA_SEGMENTED_REDUCE", "1") != "0":
+            self._early_span = flat.span_of([p for n, p in self.model.named_parameters() if n.startswith(tuple(pre)) and p.requires_grad])
         self.capture = False   # debugging / parity tests: keep a copy of each phase's gradients in self.trace
         self.trace = {}        # ... as computed by this rank, and in self.trace_reduced after the all-reduce (world_size > 1)
         self.trace_reduced = {}
@@ -363,28 +379,23 @@ class ScdaTrainer:
     def _all_reduce(self, module, async_op):
         """host side: gradient capture (tests) and the phase's all-reduce -- never inside a recorded region"""
         if self.capture:
-            name = {id(self.model): 'det', id(self.dec): 'dec', id(self.dis): 'dis', id(self.dis_patch): 'dis_patch'}[id(module)]
+            name = next(k for k, m in self.nets.items() if m is module)
             self.trace[name] = {k: p.grad.detach().clone() for k, p in module.named_parameters()}
         if self.collectives:
             return average_gradients(module, async_op=async_op)
         return None
 
     def _det_early_span(self):
-        """element range of the detector bucket whose gradients are final behind the RoI head's backward (the model names the
-        parameters: VGG.EARLY_REDUCE_PREFIXES), or None (SCDA_SEGMENTED_REDUCE=0, other detectors, a non-contiguous layout)"""
-        if not hasattr(self, '_early_span'):
-            self._early_span = None
-            pre = getattr(self.model, 'EARLY_REDUCE_PREFIXES', None)
-            flat = getattr(self.model, '_scda_flat', None)
-            if pre and flat is not None and os.environ.get("SCDA_SEGMENTED_REDUCE", "1") != "0":
-                self._early_span = flat.span_of([p for n, p in self.model.named_parameters() if n.startswith(tuple(pre)) and p.requires_grad])
+        """element range of the detector bucket that is all-reduced from inside the backward, or None (__init__)"""
         return self._early_span
 
-    def _reduce(self, module, async_op):
-        self._finish_grads(module)
-        return self._all_reduce(module, async_op)
+    def _wait_and_step(self, name, work):
+        """the end of a phase: its all-reduce (if one is in flight) has landed, then the optimiser steps"""
+        if work is not None:
+            work.wait()
+            self._grab_reduced(name, self.nets[name])
+        self.opt[name].step()
 
-    # ---- phases 1 + 2 (image discriminators, patch discriminator): forward, losses, both backward passes ----------------------
     def _dis_out_len(self, crops):
         """elements per cluster row of the image discriminator's output for crops [C, 3, h, w] (n_layer stride-2 convs, 1x1 head)"""
         h, w = crops.shape[2], crops.shape[3]
@@ -397,49 +408,39 @@ class ScdaTrainer:
     def _dis_patch_out_len(self):
         return 2 * self.dis_patch.n_out
 
-    def _phase12(self, dev_in):
-        """device work of phases 1 and 2 given their inputs and label tensors (:560-640).  No host decision inside: this is what
-        the hipGraph of _phase12_graph records."""
-        src_fake, tgt_fake, x_small, t_small, tgt_patch, src_patch, score1, score0, score0p, score1p = dev_in
+    # ---- the GAN part of the iteration as three regions without a host decision inside (REGIONS, run_region) -------------------
+    # A: decoder forward + phases 1 and 2 (:560-640)        B: phase 3 (forward, losses, backward into the decoders)
+    # C: the forward-only part of phase 4 (the logged adversarial term of the detector loss)
+    # Between them sit the optimiser steps (and, data-parallel, the waits for the all-reduces).  Each takes the tensor dict and
+    # `reduce(net name)`, which it calls where that net's gradients are final, and returns tensors only.
+    def _region_a(self, t, reduce):
         ws = float(self.world_size)
         bce, adv = A.binary_cross_entropy, A.adversarial_loss
+        src_recon, tgt_recon = self.dec(t['src_patch'], t['tgt_patch'])        # [C, 3, recon, recon]
+        mark('crops+dec_fwd_enqueued')
         self.opt['dis'].zero_grad()
-        d_src_fake, d_tgt_fake = self.dis(src_fake, tgt_fake)
-        d_src_real, d_tgt_real = self.dis(x_small, t_small)
-        tgt_pro = self.dis_patch(tgt_patch)                          # [C, 512] in (0,1); also updates BN statistics
+        d_src_fake, d_tgt_fake = self.dis(src_recon.detach(), tgt_recon.detach())
+        d_src_real, d_tgt_real = self.dis(t['x_small'], t['t_small'])
+        tgt_pro = self.dis_patch(t['tgt_patch'])                     # [C, 512] in (0,1); also updates BN statistics
         w_tgt = N.row_mean(tgt_pro.detach().contiguous())            # per-cluster weight (its gradient is dead here)
-        src_pro = self.dis_patch(src_patch)
+        src_pro = self.dis_patch(t['src_patch'])
         # The adversarial terms are the reference's sums over clusters of F.binary_cross_entropy(torch.sigmoid(d)[c], label) (one
         # mean per cluster row), each group evaluated by ONE fused kernel (A.adversarial_loss) on the logits.
-        adloss = adv([(d_src_fake, score1, None), (d_src_real, score0, None),          # ad_src  (:584-588)
-                      (d_tgt_fake, score0, w_tgt), (d_tgt_real, score1, None)],         # ad_tgt  (:596-600)
+        adloss = adv([(d_src_fake, t['score1'], None), (d_src_real, t['score0'], None),          # ad_src  (:584-588)
+                      (d_tgt_fake, t['score0'], w_tgt), (d_tgt_real, t['score1'], None)],         # ad_tgt  (:596-600)
                      scale=1.0 / ws)
         adloss.backward()
         self._finish_grads(self.dis)
-        # eager: the discriminators' all-reduce starts here, underneath phase 2; as a hipGraph region the collectives are issued by
-        # the caller behind the replay (step): 0.75 + 15 MB, still underneath phase 3
-        w1 = None if self._in_graph else self._all_reduce(self.dis, async_op=True)
+        reduce('dis')        # eager: the discriminators' all-reduce starts here, underneath phase 2 (0.75 + 15 MB)
         mark('phase1')
         self.opt['dis_patch'].zero_grad()
-        dis_patch_loss = (bce(src_pro, score1p) + bce(tgt_pro, score0p)) / ws
+        dis_patch_loss = (bce(src_pro, t['score1p']) + bce(tgt_pro, t['score0p'])) / ws
         dis_patch_loss.backward()
         self._finish_grads(self.dis_patch)
-        w2 = None if self._in_graph else self._all_reduce(self.dis_patch, async_op=True)
-        return adloss.detach(), dis_patch_loss.detach(), w1, w2
+        reduce('dis_patch')
+        return src_recon, tgt_recon, adloss.detach(), dis_patch_loss.detach()
 
-    # ---- the GAN part of the iteration as three regions without a host decision inside --------------------------------------
-    # A: decoder forward + phases 1 and 2        B: phase 3 (forward, losses, backward into the decoders)
-    # C: the forward-only part of phase 4 (the logged adversarial term of the detector loss)
-    # Between them sit the optimiser steps (and, data-parallel, the waits for the all-reduces).  The eager iteration calls them as
-    # plain functions; with SCDA_GAN_GRAPH=1 each is recorded ONCE as a hipGraph and replayed (_GanGraphs below).
-    def _region_a(self, t):
-        src_recon, tgt_recon = self.dec(t['src_patch'], t['tgt_patch'])        # [C, 3, recon, recon]
-        mark('crops+dec_fwd_enqueued')
-        adloss, dis_patch_loss, w1, w2 = self._phase12((src_recon.detach(), tgt_recon.detach(), t['x_small'], t['t_small'], t['tgt_patch'],
-                                                        t['src_patch'], t['score1'], t['score0'], t['score0p'], t['score1p']))
-        return src_recon, tgt_recon, adloss, dis_patch_loss, w1, w2
-
-    def _region_b(self, src_recon, tgt_recon, t):
+    def _region_b(self, src_recon, tgt_recon, t, reduce):
         ws = float(self.world_size)
         adv = A.adversarial_loss
         self.opt['dec'].zero_grad()
@@ -453,8 +454,8 @@ class ScdaTrainer:
             recon_loss = (fake1_src + fake1_tgt) / ws
             recon_loss.backward()
         self._finish_grads(self.dec)
-        w3 = None if self._in_graph else self._all_reduce(self.dec, async_op=True)
-        return recon_loss.detach(), fake1_src.detach(), w_tgt2, w3
+        reduce('dec')
+        return recon_loss.detach(), fake1_src.detach(), w_tgt2
 
     def _region_c(self, t, w_tgt2):
         adv = A.adversarial_loss
@@ -469,7 +470,7 @@ class ScdaTrainer:
         """The three regions above as hipGraphs (~330 of the iteration's ~700 launches, fixed shapes; SCDA_GAN_GRAPH=0 turns them off).
         Not with gradient capture, the reference-style schedule or the parity tests' hooks; not when a dropout of the decoders would
         take its seed as a kernel argument (a recording would freeze it: only the residual blocks' fused tail reads a device seed).
-        The all-reduces of a data-parallel run are host calls: issued behind each replay (step), never recorded."""
+        The all-reduces of a data-parallel run are host calls: issued behind each replay (run_region), never recorded."""
         from . import layers as L
         from .dropin.models.faster_rcnn.common_net import INSResBlock
         from .hostenv import blocking_sync_selected
@@ -481,29 +482,20 @@ class ScdaTrainer:
         if not (os.environ.get("SCDA_GAN_GRAPH", "1") != "0" and self.device.type == "cuda" and not self.capture and self.early_backward
                 and not P.active() and self.flat):
             return False
-        ok = getattr(self, "_graphable_nets", None)
-        if ok is None:
+        if self._graphable_nets is None:
             fused = set()
             for blk in self.dec.modules():
                 if isinstance(blk, INSResBlock) and blk.tail_fusable():
                     fused.add(id(blk.model[-1]))
-            ok = all(id(m) in fused or m.p == 0.0 for net in (self.dec, self.dis, self.dis_patch) for m in net.modules()
-                     if isinstance(m, L.Dropout))
-            self._graphable_nets = ok
-        return ok
+            self._graphable_nets = all(id(m) in fused or m.p == 0.0 for net in (self.dec, self.dis, self.dis_patch)
+                                       for m in net.modules() if isinstance(m, L.Dropout))
+        return self._graphable_nets
 
     def _ones_row(self, row):
-        c = getattr(self, "_ones_row_cache", None)
+        c = self._ones_row_cache
         if c is None or tuple(c.shape) != tuple(row):
             c = self._ones_row_cache = torch.ones(row, dtype=torch.float32, device=self.device)
         return c
-
-    def _gan_graphs(self):
-        g = getattr(self, "_gg", None)
-        if g is None:
-            g = self._gg = _GanGraphs(self)
-        g.calls += 1
-        return g
 
     def step(self, image, gts, image_info, target, gt_masks=None):
         """image/target [1,3,H,W] on the device; gts [1,G,5]; image_info [1,3]; gt_masks [1,G,H,W] binary (detectors with a mask
@@ -518,7 +510,6 @@ class ScdaTrainer:
         if gt_masks is not None:
             x['ground_truth_masks'] = gt_masks
         pending = {}
-        self._in_graph = False
         for sch in self._warmup or ():     # :510-514 -- the warm-up schedulers step at the top of the iteration
             sch.step()
 
@@ -533,12 +524,12 @@ class ScdaTrainer:
             self.opt['det'].zero_grad()
             det_loss.backward()
             pending['det_loss'] = det_loss.detach()
+            self._finish_grads(self.model)
             seg = pending.get('seg')
             if seg is not None:          # the head's slice left from inside the backward; the conv body's (and what else is left) now
-                self._finish_grads(self.model)
                 pending['w4'] = seg.launch_rest()
             else:
-                pending['w4'] = self._reduce(self.model, async_op=True)
+                pending['w4'] = self._all_reduce(self.model, async_op=True)
 
         if self.early_backward:
             x['_after_source_losses'] = detector_backward
@@ -561,10 +552,16 @@ class ScdaTrainer:
         t = {'x_small': _crops(image, get_corner_from_center(ctr_s, self.recon, self.new_w, self.new_h), self.recon),
              't_small': _crops(target, get_corner_from_center(ctr_t, self.recon, self.new_w, self.new_h), self.recon),
              'src_patch': src_patch, 'tgt_patch': tgt_patch}
-        graphs = self._gan_graphs() if self._gan_graph_ok() else None
-        if graphs is not None and not graphs.fits(t):
-            graphs = None              # other cluster / crop shapes than the recorded ones: this iteration runs eagerly
-        in_graph = graphs is not None and graphs.recording()
+        graphs = None
+        if self._gan_graph_ok():
+            if self._gg is None:
+                self._gg = _GanGraphs(self)
+            self._gg.begin_iteration()
+            if self._gg.fits(t):       # (other cluster / crop shapes than the recorded ones: this iteration runs eagerly)
+                graphs = self._gg
+
+        def reduce(net):
+            return self._all_reduce(self.nets[net], async_op=True)
 
         # The adversarial terms below are the reference's sums over clusters of F.binary_cross_entropy(torch.sigmoid(d)[c], label)
         # (one mean per cluster row), each group evaluated by ONE fused kernel (A.adversarial_loss) on the logits.
@@ -575,43 +572,15 @@ class ScdaTrainer:
         pro_shape = (src_patch.shape[0], self._dis_patch_out_len())
         t['score1'], t['score0'], t['score0p'], t['score1p'] = _labels(
             [('s', 1, row), ('s', 0, row), ('s', 0, pro_shape), ('s', 1, pro_shape)], dev)
-        self._in_graph = in_graph      # (reset in a finally: an exception inside a region -- an OOM while recording, a shape error -- must
-        try:                           # not leave the flag set, or the next eager step would skip every phase's all-reduce)
-            if graphs is not None and graphs.ready('a'):
-                src_recon, tgt_recon, adloss, dis_patch_loss = graphs.run('a', t)
-                w1 = w2 = None
-            else:
-                with _recording(graphs, 'a', t) as rec:
-                    src_recon, tgt_recon, adloss, dis_patch_loss, w1, w2 = rec(lambda tt: self._region_a(tt))
-        finally:
-            self._in_graph = False
-        if in_graph:                   # the region's collectives, behind the replay
-            w1 = self._all_reduce(self.dis, async_op=True)
-            w2 = self._all_reduce(self.dis_patch, async_op=True)
+        (src_recon, tgt_recon, adloss, dis_patch_loss), works = run_region(graphs, 'a', t, self._region_a, reduce)
         mark('phase2')
-        if w1 is not None:
-            w1.wait()
-            self._grab_reduced('dis', self.dis)
-        self.opt['dis'].step()
-        if w2 is not None:
-            w2.wait()
-            self._grab_reduced('dis_patch', self.dis_patch)
-        self.opt['dis_patch'].step()
+        self._wait_and_step('dis', works['dis'])
+        self._wait_and_step('dis_patch', works['dis_patch'])
 
         # ---------------- (3) decoders ----------------
         t['one_t'], t['zero_t'], t['one_s'], t['zero_s'] = _labels([('h', 1, row), ('h', 0, row), ('h', 1, row), ('h', 0, row)], dev)
-        self._in_graph = in_graph
-        try:
-            if graphs is not None and graphs.ready('b'):
-                recon_loss, fake1_src, w_tgt2 = graphs.run('b', t)
-                w3 = None
-            else:
-                with _recording(graphs, 'b', t) as rec:
-                    recon_loss, fake1_src, w_tgt2, w3 = rec(lambda tt: self._region_b(src_recon, tgt_recon, tt))
-        finally:
-            self._in_graph = False
-        if in_graph:
-            w3 = self._all_reduce(self.dec, async_op=True)
+        (recon_loss, fake1_src, w_tgt2), works = run_region(
+            graphs, 'b', t, lambda tt, rd: self._region_b(src_recon, tgt_recon, tt, rd), reduce)     # (A's recorded reconstructions, un-copied)
         mark('phase3')
 
         # ---------------- (4) detector ----------------
@@ -624,22 +593,12 @@ class ScdaTrainer:
         if not self.early_backward:
             detector_backward(outputs['losses'])
         det_loss, w4 = pending['det_loss'], pending['w4']
-        if w3 is not None:
-            w3.wait()
-            self._grab_reduced('dec', self.dec)
-        self.opt['dec'].step()
+        self._wait_and_step('dec', works['dec'])
         t['ones_all'] = _hard(1, (src_patch.shape[0], n_dis), dev)
         t['ones_row'] = self._ones_row(row)
-        if graphs is not None and graphs.ready('c'):
-            fake_loss_source, fake_loss_target = graphs.run('c', t)
-        else:
-            with _recording(graphs, 'c', t) as rec:
-                fake_loss_source, fake_loss_target = rec(lambda tt: self._region_c(tt, w_tgt2))
+        (fake_loss_source, fake_loss_target), _ = run_region(graphs, 'c', t, lambda tt, rd: self._region_c(tt, w_tgt2), reduce)
         loss = det_loss + 0.1 * (fake_loss_source + fake_loss_target) / ws
-        if w4 is not None:
-            w4.wait()
-            self._grab_reduced('det', self.model)
-        self.opt['det'].step()
+        self._wait_and_step('det', w4)
         mark('phase4+det_step')
 
         self.last_num_proposals = outputs.get('num_proposals')     # post-NMS proposal counts (source, target) of this iteration

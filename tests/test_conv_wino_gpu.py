@@ -155,7 +155,8 @@ def test_wino_wgrad_routes_through_conv2d_entry_points(cuda):
 def test_conv_pool_fusion_is_bit_identical_to_separate_launches(cuda, monkeypatch):
     """conv3x3 + ReLU + MaxPool2d(2, 2) in the Winograd kernel's epilogue (scda_conv2d_wino_pool_hip, layers.Conv2d.pool_next) against
     the same chain with the pool as its own launch (SCDA_CONV_POOL_FUSE=0): pooled values, winners and every gradient bit for bit --
-    ties inside a window included (ReLU zeros) -- and against torch on the CPU at the kernels' usual tolerance."""
+    ties inside a window included (ReLU zeros) -- and against torch on the CPU at the kernels' usual tolerance.  A forward hook on a
+    fused conv is owed the conv's own output: that pair then runs the separate launches (layers.FusedProducer), with the same bits."""
     import torch.nn as nn
     from scda_amd import layers as L
     from scda_amd import native
@@ -171,11 +172,13 @@ def test_conv_pool_fusion_is_bit_identical_to_separate_launches(cuda, monkeypatc
         L.plan_act_fusion(seq)
         return seq.to(cuda)
 
-    res = {}
-    for fuse in ("1", "0"):
-        monkeypatch.setenv("SCDA_CONV_POOL_FUSE", fuse)
+    res, seen = {}, []
+    for fuse in ("1", "0", "hooked"):
+        monkeypatch.setenv("SCDA_CONV_POOL_FUSE", "0" if fuse == "0" else "1")
         net = build()
         assert net[2].pool_next and net[5].pool_next and not net[0].pool_next
+        if fuse == "hooked":
+            net[2].register_forward_hook(lambda mod, inp, out: seen.append(tuple(out.shape)))
         x = x0.to(cuda).requires_grad_()
         native.prof_enable(["conv_wino_kernel<fwd>"])
         y = net(x)
@@ -184,10 +187,12 @@ def test_conv_pool_fusion_is_bit_identical_to_separate_launches(cuda, monkeypatc
         launches = native.prof_collect()["conv_wino_kernel<fwd>"][0]
         (y * up.to(cuda)).sum().backward()
         res[fuse] = (y.detach().clone(), x.grad.clone(), [p.grad.clone() for p in net.parameters()], launches)
-    assert res["1"][3] == res["0"][3] == 3
-    assert torch.equal(res["1"][0], res["0"][0]) and torch.equal(res["1"][1], res["0"][1])
-    for a, b in zip(res["1"][2], res["0"][2]):
-        assert torch.equal(a, b)
+    assert res["1"][3] == res["0"][3] == res["hooked"][3] == 3
+    assert seen == [(1, 128, 256, 256)]            # the hook saw the un-pooled map
+    for other in ("0", "hooked"):
+        assert torch.equal(res["1"][0], res[other][0]) and torch.equal(res["1"][1], res[other][1])
+        for a, b in zip(res["1"][2], res[other][2]):
+            assert torch.equal(a, b)
     # ... and the chain itself against torch (CPU, fp32)
     net = build().cpu()
     ref = nn.Sequential(nn.Conv2d(64, 64, 3, padding=1), nn.ReLU(), nn.Conv2d(64, 128, 3, padding=1), nn.ReLU(), nn.MaxPool2d(2, 2),

@@ -497,7 +497,8 @@ def test_norm_upsample_unsupported_shapes_fail_loudly(cuda):
 def test_decoder_fuses_norm_upsample_pairs_with_identical_results(cuda, monkeypatch):
     """a decoder branch (residual blocks -> two up-sampling blocks -> 1x1 -> tanh) with the norm + Interpolate pairs as one launch each
     (common_net.pair_decoder_upsamples: both Interpolates have a paired producer) and with SCDA_NO_NORM_UP_FUSION=1: same seed draws,
-    outputs, input gradient and every parameter gradient bit for bit; a deep copy runs un-fused until paired again"""
+    outputs, input gradient and every parameter gradient bit for bit; a deep copy runs un-fused until paired again; a pair whose norm
+    carries a forward hook runs its two launches, and the hook sees the norm's own (small) plane"""
     import copy
     from scda_amd import layers as L
     from scda_amd.dropin.models.faster_rcnn.faster_rcnn_adver_expansion_reweight_cluster import GAN_decoder_AE
@@ -527,6 +528,19 @@ def test_decoder_fuses_norm_upsample_pairs_with_identical_results(cuda, monkeypa
     assert torch.equal(f[1], u[1]) and torch.equal(f[2], u[2]) and torch.equal(f[3], u[3]) and torch.equal(f[4], u[4])
     assert all(torch.equal(p, q) for p, q in zip(f[5], u[5])) and f[6] == u[6]
     monkeypatch.delenv("SCDA_NO_NORM_UP_FUSION")
+    norm = next(u._producer() for u in ups if isinstance(u._producer(), L.InstanceNorm2d))
+    seen = []
+    handle = norm.register_forward_hook(lambda mod, inp, out: seen.append((tuple(inp[0].shape), tuple(out.shape))))
+    torch.manual_seed(11)
+    a, b = xa.clone().requires_grad_(), xb.clone().requires_grad_()
+    n0 = len(calls)
+    ya, yb = dec(a, b)
+    assert len(calls) - n0 == 1 and len(seen) == 1 and seen[0][0] == seen[0][1]       # that pair alone, once per pass
+    (ya.square().sum() + yb.square().sum()).backward()
+    assert torch.equal(ya, f[1]) and torch.equal(yb, f[2]) and torch.equal(a.grad, f[3]) and torch.equal(b.grad, f[4])
+    assert all(torch.equal(p.grad, q) for p, q in zip(dec.parameters(), f[5])) and torch.rand(1).item() == f[6]
+    handle.remove()
+    dec.zero_grad()
     clone = copy.deepcopy(dec)
     n0 = len(calls)
     clone(xa, xb)
@@ -536,7 +550,7 @@ def test_decoder_fuses_norm_upsample_pairs_with_identical_results(cuda, monkeypa
 def test_upsample_rejects_a_tensor_that_is_not_the_announced_one(cuda):
     from scda_amd import layers as L
     up = L.Upsample2x()
-    up.expect_upsampled((1, 2, 8, 8))
+    up.announce((1, 2, 8, 8))
     with pytest.raises(RuntimeError, match="announced"):
         up(torch.zeros(1, 2, 4, 4, device=cuda))
     assert up(torch.ones(1, 2, 4, 4, device=cuda)).shape == (1, 2, 8, 8)       # the announcement is consumed either way
