@@ -329,6 +329,47 @@ size_t scda_mask_iou_workspace_bytes(int M, int N, int H, int Wd);
 int scda_mask_iou_hip(const uint32_t *dt_bits, int M, const uint32_t *gt_bits, int N, int H, int Wd, int h, int w,
                       const unsigned char *iscrowd_or_null, void *ws, double *iou, uint32_t *inter, void *stream);
 
+/* ---- COCO ground-truth masks from annotations (scda_amd/csrc/mask_poly.hip; opt-in: scda_amd.coco_gt.GroundTruth) --------------------
+ * COCO.annToMask of the reference's datasets/pycocotools/coco.py:411-439 -- rleFrPoly (maskApi.c:161-201), rleMerge with intersect = 0
+ * (:49-70), frUncompressedRLE and rleDecode (:43-47) -- from vertices / run counts to scda_mask_paste_hip's packed planes, bit for bit
+ * (integers plus single IEEE double operations, no FMA contraction).  The only atomics are integer XORs and adds: two runs give the same
+ * bytes.  tests/mask_poly_np.py restates the rule in numpy; tests/golden/mask_poly_ref.npz holds what the reference's C gives.
+ *
+ * Inputs, all DEVICE memory: polygon p has the vertices xy[poly_first[p] .. poly_first[p + 1]) (float64 (x, y) pairs, V in all) and
+ * belongs to output plane poly_plane[p]; RLE q has the counts rle_counts[rle_first[q] .. rle_first[q + 1]) (uint32, C in all; a
+ * compressed string is decoded on the host first: rleFrString, maskApi.c:217-230) and belongs to plane rle_plane[q].  poly_first,
+ * rle_first, poly_plane and rle_plane are non-decreasing.  sizes int32 [N, 2] = (h, w) of the image inside plane n, 1 <= h <= H,
+ * 1 <= w <= 32 Wd.  The rule, for one polygon of k vertices in an h x w image:
+ *   1. x[j] = (int)(5 * xy[2j] + .5), y[j] likewise (a double multiply, a double add, truncation towards zero); x[k] = x[0], y[k] = y[0].
+ *   2. Edge j runs from (x[j], y[j]) to (x[j+1], y[j+1]) and has n_j = max(|dx|, |dy|) + 1 points d = 0 .. n_j - 1 (dx = |xe - xs|,
+ *      dy = |ye - ys|): flip = (dx >= dy && xs > xe) || (dx < dy && ys > ye) swaps the ends, t = flip ? n_j - 1 - d : d; if dx >= dy:
+ *      s = (double)(ye - ys) / dx, u = t + xs, v = (int)(ys + s * t + .5); else s = (double)(xe - xs) / dy, v = t + ys,
+ *      u = (int)(xs + s * t + .5).  The last point of an edge is NOT always the next vertex ((int)(negative + .5) truncates towards 0).
+ *   3. dx == dy == 0: the one point is u = xs, v = INT_MIN (s = 0.0 / 0 is NaN and (int)NaN is INT_MIN on the reference's x86-64
+ *      build).  A duplicated vertex therefore changes the reference's mask, and it changes this one in the same way.
+ *   4. Every point q but the very first has the predecessor p in the concatenated sequence of all edges (point d - 1 of its edge, or
+ *      the last point of the edge before).  u_q == u_p gives nothing.  Otherwise xd = (double)(u_q < u_p ? u_q : u_q - 1),
+ *      xd = (xd + .5) / 5 - .5; dropped if floor(xd) != xd, xd < 0 or xd > w - 1; yd = (double)min(v_q, v_p), yd = (yd + .5) / 5 - .5,
+ *      clamped to [0, h], yd = ceil(yd); the point TOGGLES position (int)xd * h + (int)yd of the column-major pixel sequence
+ *      (index = x * h + y).
+ *   5. Pixel i, 0 <= i < h * w, is the parity of the number of toggles at positions <= i -- over the LINEAR sequence, not per column:
+ *      yd == h toggles the top of the next column, a toggle at h * w does nothing.  (The reference's sort, difference and zero-run
+ *      merge, :192-199, amount to this.)
+ * An RLE is the same fill with toggles at the running sums of its counts; the pixels behind the last run stay 0 (rleDecode into a
+ * zeroed image).  A plane is the union (OR) of the fills of its polygons and RLEs; a plane that nothing maps to is empty.
+ * Outputs: bits uint32 [N, H, Wd], bit c % 32 of word c / 32 of row y = pixel (y, c) -- EVERY word is written, bits outside the h x w
+ * sub-plane are zero --, and area_or_null uint32 [N] = the set pixels (rleArea).
+ * Limits, checked here: N, H <= 65535, H * 32 Wd < 2^31; status < 0 and nothing launched otherwise.  The limits on the DATA -- sizes
+ * in range, coordinates finite with |coordinate| <= 65535, the counts of an RLE summing to at most h * w (the reference writes past its
+ * buffer there) -- are checked on the host by scda_amd.coco_gt.flatten_annotations, which raises ValueError; the kernels skip a shape or
+ * edge that violates them (its plane is then unspecified), so that nothing is read or written out of bounds.
+ * ws: scda_mask_frpoly_workspace_bytes(P, Q, H, Wd) bytes (one column-major toggle plane per polygon and RLE), 16-byte aligned.  Two
+ * clears and four launches ordered by the kernel boundary alone, no host wait, no allocation: graph-capturable. */
+size_t scda_mask_frpoly_workspace_bytes(int P, int Q, int H, int Wd);
+int scda_mask_frpoly_hip(const double *xy, int V, const int *poly_first, const int *poly_plane, int P, const uint32_t *rle_counts, int C,
+                         const int *rle_first, const int *rle_plane, int Q, const int *sizes, int N, int H, int Wd, void *ws,
+                         uint32_t *bits, uint32_t *area_or_null, void *stream);
+
 /* ---- COCO AP on the device (scda_amd/csrc/coco_eval.hip; opt-in: scda_amd.coco_eval.CocoEvaluator) ---------------------------------
  * The detection evaluator of the reference's datasets/pycocotools/cocoeval.py (COCOeval.evaluate / accumulate / summarize, iouType
  * 'bbox' and 'segm', useCats = 1) and bbIou of datasets/pycocotools/common/maskApi.c, bit for bit: integer work plus single IEEE double
@@ -336,7 +377,7 @@ int scda_mask_iou_hip(const uint32_t *dt_bits, int M, const uint32_t *gt_bits, i
  * the rules in numpy; tests/golden/coco_eval_ref.npz holds what the reference's own code gives.  Thresholds, area ranges and maxDets
  * are DEVICE arrays filled by the host (np.linspace values as Params.setDetParams computes them); the limits are T <= 16 thresholds,
  * A <= 8 area ranges, M <= 4 maxDets, R <= 128 recall thresholds, K <= 255 categories (indices 1..K), D, G <= 1024 detection slots /
- * ground truths per image.  Not covered: keypoints / OKS, useCats = 0, the JSON round trip, anything of coco.py.  No call waits for
+ * ground truths per image.  Not covered: keypoints / OKS, useCats = 0, the JSON round trip, annotation loading (annToMask: see above).  No call waits for
  * the host or allocates.
  *
  * scda_coco_det_rows_hip: detections [B, top_n, 7] = (b, x1, y1, x2, y2, score, class) + detection_counts i32 [B] (scda_box_predict_hip's

@@ -5,8 +5,8 @@ iouType 'bbox' and 'segm' with useCats = 1 and the default detection parameters 
 thresholds, maxDets [1, 10, 100], the four area ranges), bit for bit for precision / recall / scores; include/scda_ops.h states the
 rules, tests/coco_eval_np.py restates them in numpy.  The parameters are numpy values uploaded at construction, never kernel constants.
 
-NOT covered: keypoints / OKS, useCats = 0 (proposal AR), the text / JSON round trip, anything of coco.py (annotation loading, polygon
-conversion): ground truth arrives as device tensors.  Detections and ground truth must be in the SAME coordinates -- dividing the
+NOT covered: keypoints / OKS, useCats = 0 (proposal AR), the text / JSON round trip, annotation loading: ground truth arrives as device tensors
+(scda_amd.coco_gt.GroundTruth builds them, masks included, from annotation dicts).  Detections and ground truth must be in the SAME coordinates -- dividing the
 network-input detections by resize_scale (or scaling the ground truth) stays with the caller.  Image ids must be distinct.
 
     ev = CocoEvaluator(num_categories=80, iou_type='bbox', max_images=5000, max_dets_per_image=100, max_gts_per_image=64, device=dev)

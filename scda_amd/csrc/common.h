@@ -37,6 +37,21 @@ static inline int ew_grid(long long n, int block = 256) {
 
 constexpr int kWave = 64;  // gfx950 wavefront
 
+// in-register transpose of a 32 x 32 bit block (mask_rle.hip, mask_poly.hip): afterwards a[j] bit i = (before) a[i] bit j
+__host__ __device__ inline void transpose32(uint32_t a[32]) {
+    uint32_t m = 0x0000ffffu;
+#pragma unroll
+    for (int j = 16; j != 0; j >>= 1, m ^= m << j) {
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+            const int k = ((q & ~(j - 1)) << 1) | (q & (j - 1));          // the q-th index with bit j clear
+            const uint32_t t = ((a[k] >> j) ^ a[k | j]) & m;
+            a[k] ^= t << j;
+            a[k | j] ^= t;
+        }
+    }
+}
+
 // 4 KB of device zeros (per device, allocated on first use, never freed).  Gathers whose lane falls outside the
 // tensor read from here instead of being predicated: with no select after the load there is nothing that needs the
 // loaded value before the LDS store, so the s_waitcnt lands AFTER the MFMAs of the current K-slab.

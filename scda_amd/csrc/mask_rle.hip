@@ -72,21 +72,6 @@ __device__ inline Geo mask_geo(const Sizes &s, int r, int H, int Wd) {
     return g;
 }
 
-// in-register transpose of a 32 x 32 bit block: afterwards a[j] bit i = (before) a[i] bit j
-__host__ __device__ inline void transpose32(uint32_t a[32]) {
-    uint32_t m = 0x0000ffffu;
-#pragma unroll
-    for (int j = 16; j != 0; j >>= 1, m ^= m << j) {
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            const int k = ((q & ~(j - 1)) << 1) | (q & (j - 1));          // the q-th index with bit j clear
-            const uint32_t t = ((a[k] >> j) ^ a[k | j]) & m;
-            a[k] ^= t << j;
-            a[k | j] ^= t;
-        }
-    }
-}
-
 // the block (rows y0.., word column wc) of one plane cropped to (h, w): col[j] bit i = pixel (y0 + i, 32 wc + j); carry bit j = the pixel
 // before (y0, 32 wc + j) in column-major order; rowmask = the block's rows inside the crop
 __device__ inline void load_block(const uint32_t *__restrict__ plane, int Wd, int h, int w, int wc, int y0, uint32_t col[32],

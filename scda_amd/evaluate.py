@@ -143,17 +143,36 @@ def coco_stats(loader, predictor, evaluator, device=None):
     CocoEvaluator.add takes it -- 'gt_boxes' float64 [B, Gcap, 4] (x, y, w, h), 'gt_areas', 'gt_iscrowd', 'gt_categories', 'gt_counts',
     for 'segm' also 'gt_mask_bits' (infer.pack_masks) and optionally 'sizes' -- IN THE COORDINATES OF THE DETECTIONS (the network input:
     scale the ground truth by resize_scale, nothing is divided here).  Tensors that are on the device already are used as they are; the
-    only wait for the host is the last one.  validate() is not involved."""
+    only wait for the host is the last one.  validate() is not involved.
+
+    An item may carry 'annotations' (per image a list of COCO annotation dicts, with 'sizes' = the (h, w) of every image) INSTEAD of
+    the six gt_* entries: they are then built by a scda_amd.coco_gt.GroundTruth that is kept across the items -- for 'segm' the masks
+    are rasterised on the device (scda_mask_frpoly_hip) into planes of the Predictor's shape, max_gts_per_image slots per image.  The
+    annotations are rasterised AT THEIR OWN COORDINATES: as for every other ground-truth input, bringing polygons, boxes and areas to
+    the detections' coordinates when resize_scale != 1 is the caller's business."""
     segm = evaluator.iou_type == 'segm'
     if segm and not (predictor.masks and predictor.rle):
         raise ValueError("coco_stats: a 'segm' evaluator needs Predictor(masks=True, rle=True)")
     device = evaluator.device if device is None else device
+    ground_truth = None
     with torch.no_grad():
         for item in loader:
             out = predictor(item['image'].to(device, non_blocking=True), item['image_info'])
+            if 'annotations' in item:
+                from scda_amd import coco_gt, native
+                if segm:
+                    if ground_truth is None or (ground_truth.H, ground_truth.Wd) != tuple(out[4].shape[2:]):
+                        ground_truth = coco_gt.GroundTruth(device, evaluator.G, out[4].shape[2], out[4].shape[3])
+                    gt = ground_truth.load(item['annotations'], item['sizes'])
+                else:
+                    flat = coco_gt.flatten_annotations(item['annotations'], item['sizes'], evaluator.G)
+                    gt = tuple(native.upload(flat[k], device) for k in ('gt_boxes', 'gt_areas', 'gt_iscrowd', 'gt_categories', 'gt_counts'))
+                    gt += (None,)
+            else:
+                gt = (item['gt_boxes'], item['gt_areas'], item['gt_iscrowd'], item['gt_categories'], item['gt_counts'],
+                      item['gt_mask_bits'] if segm else None)
             kw = {}
             if segm:
-                kw = {'mask_bits': out[4], 'det_areas': out[5]['area'], 'gt_mask_bits': item['gt_mask_bits'], 'sizes': item.get('sizes')}
-            evaluator.add(item['image_ids'], out[2], out[3], item['gt_boxes'], item['gt_areas'], item['gt_iscrowd'], item['gt_categories'],
-                          item['gt_counts'], **kw)
+                kw = {'mask_bits': out[4], 'det_areas': out[5]['area'], 'gt_mask_bits': gt[5], 'sizes': item.get('sizes')}
+            evaluator.add(item['image_ids'], out[2], out[3], *gt[:5], **kw)
     return evaluator.summarize()

@@ -567,6 +567,40 @@ def mask_iou(dt_bits, gt_bits, size, iscrowd=None, ws=None, out=None):
     return iou, inter
 
 
+# ------------------------------------- COCO ground-truth masks (annToMask) ---
+def mask_frpoly_workspace_bytes(P, Q, H, Wd):
+    return int(lib().scda_mask_frpoly_workspace_bytes(int(P), int(Q), int(H), int(Wd)))
+
+
+def mask_frpoly(xy, poly_first, poly_plane, rle_counts, rle_first, rle_plane, sizes, ws, out, area=None):
+    """COCO.annToMask on the device (include/scda_ops.h states the rule): polygons xy float64 [V, 2], poly_first int32 [P + 1], poly_plane
+    int32 [P]; run lengths rle_counts int32 [C] (uint32 values), rle_first int32 [Q + 1], rle_plane int32 [Q]; sizes int32 [N, 2] = (h, w)
+    of the image inside plane n -- all device tensors as scda_amd.coco_gt.flatten_annotations lays them out (it also checks the limits on
+    the data, which this wrapper cannot see).  ws: uint8, mask_frpoly_workspace_bytes(P, Q, H, Wd); out: int32 [N, H, Wd] words, every one
+    of which is written; area: int32 [N] (uint32 values) or None.  Nothing is allocated and the host is not waited for.  -> out"""
+    _req(xy, "xy", torch.float64); _req(sizes, "sizes", torch.int32); _req(ws, "ws", torch.uint8)
+    for t, name in ((poly_first, "poly_first"), (poly_plane, "poly_plane"), (rle_counts, "rle_counts"), (rle_first, "rle_first"),
+                    (rle_plane, "rle_plane")):
+        _req(t, name, torch.int32)
+    _words(out, "out")
+    N, H, Wd = out.shape
+    V, P, C, Q = xy.shape[0], poly_plane.numel(), rle_counts.numel(), rle_plane.numel()
+    if xy.dim() != 2 or xy.shape[1] != 2 or poly_first.numel() != P + 1 or rle_first.numel() != Q + 1 or tuple(sizes.shape) != (N, 2):
+        raise ValueError("mask_frpoly: xy [V, 2], poly_first [P + 1], poly_plane [P], rle_first [Q + 1], rle_plane [Q], sizes [N, 2]")
+    need = mask_frpoly_workspace_bytes(P, Q, H, Wd)
+    if need == 0 or not (1 <= N <= 65535):
+        raise ValueError("mask_frpoly: at most 65535 planes x 65535 rows and fewer than 2^31 pixels")
+    if ws.numel() < need:
+        raise ValueError("mask_frpoly: workspace too small")
+    if area is not None:
+        _req(area, "area", torch.int32)
+        if area.numel() != N:
+            raise ValueError("mask_frpoly: area must be [N]")
+    _check(lib().scda_mask_frpoly_hip(_p(xy), V, _p(poly_first), _p(poly_plane), P, _p(rle_counts), C, _p(rle_first), _p(rle_plane), Q,
+                                      _p(sizes), N, H, Wd, _p(ws), _p(out), _p(area), _stream()), "scda_mask_frpoly_hip")
+    return out
+
+
 # ------------------------------------------------- COCO AP (COCOeval) -------
 def coco_det_rows(detections, detection_counts, K, xywh, area, score, cat, mask_area=None):
     """detections float32 [B, top_n, 7] + detection_counts int32 [B] -> the caller's xywh float64 [B, top_n, 4], area float64, score
