@@ -436,6 +436,59 @@ int scda_coco_accumulate_hip(const int *image_ids, int n_images, int D, const in
 int scda_coco_summarize_hip(const double *precision, const double *recall, int T, int R, int K, int A, int M, const int *spec,
                             int n_stats, double *stats, void *stream);
 
+/* ---- Cityscapes mAP on the device (scda_amd/csrc/map_eval.hip; opt-in: scda_amd.map_eval.MapEvaluator) -------------------------------
+ * The reference's metric: the rows validate() writes (tools/faster_rcnn_train_val.py:826-858) scored by utils/cal_mAP.py (parse_res,
+ * calIoU, cal_mAP), and the RPN recall of bbox_helper.compute_recall -- bit for bit: integer work plus single IEEE operations in the
+ * reference's order.  The only atomics are integer adds; two runs give the same bytes.  tests/voc_map_np.py restates the rules in numpy;
+ * tests/golden/voc_map_ref.npz holds what the reference's own code gives.  Limits: D, G <= 1024 detection / ground-truth slots per
+ * image, 2 <= num_classes C <= 256 (classes 1..C-1), 1 <= keep_num <= D.  No call waits for the host or allocates; every capacity
+ * violation is refused with SCDA_EINVAL before anything is launched.
+ *
+ * R1, scda_map_rows_hip (validate() :838-857, then parse_res): detections f32 [B, D, 7] = (b, x1, y1, x2, y2, score, class) and
+ *   detection_counts i32 [B] (scda_box_predict_hip's outputs), image_info f32 [B, info_w] = (h, w, ...).  Per image the live rows are
+ *   d < detection_counts[b].  rank = a live row's position under the stable sort by descending float32 score (equal scores: the
+ *   earlier row first; padding rows keep rank = d, so rank is a permutation of 0..D-1); kept = live && rank < keep_num && 1 <= class
+ *   <= C-1 (validate() never writes the other classes).  Each coordinate in float32: x -> fmin(fmax(x, 0), w - 1), y -> fmin(fmax(y,
+ *   0), h - 1), then the correctly rounded quotient by image_info[b, scale_column], then truncation toward zero -> box i32 [B, D, 4]
+ *   (int(float(str(np.float32))) is that truncation: the shortest repr of a float32 cannot cross an integer).  score f32 (0 for
+ *   padding), cls i32 = (int) class of a live row (0 for padding).  The rows of an image in the file are class ascending, then rank
+ *   ascending.  validate() orders with argsort()[::-1], whose order among EQUAL scores is numpy's, not this one.  Also resets the
+ *   slots' later outputs: tp = 0, dbg_match = -1, dbg_claimed [B, G] = 0.
+ * R2, scda_map_match_hip (calIoU, cal_mAP :67-114): one wave per (image, class c = 1..C-1).  gt_boxes i32 [B, G, 5] = (x1, y1, x2, y2,
+ *   label), rows < gt_counts[b]; the class's ground truths are those of label == c in row (meta) order; gt_num[c] += their number
+ *   (integer atomic add; ACCUMULATES over calls).  The class's kept detections are visited in rank order (= descending score, ties in
+ *   row order).  Per detection, over the ground truths in order: ix1 = max(x1, gx1), iy1 = max(y1, gy1), ix2 = min(x2, gx2), iy2 =
+ *   min(y2, gy2); the pair counts only if ix1 < ix2 && iy1 < iy2 (both strict); inter = (ix2-ix1+1) * (iy2-iy1+1); IoU = (double) inter
+ *   / (double) (a_dt + a_gt - inter) with the +1 areas, integers in int64, one double division.  best starts at -1 and is replaced on
+ *   strict > only (the first maximum wins; across lanes: the larger IoU, on equal IoU the smaller index).  tp = 1 iff best >= iou_thr
+ *   and that ground truth is unclaimed, which is then claimed; otherwise the detection is a false positive, nothing is claimed, and
+ *   there is no second choice.  tp i32 [B, D]; dbg_match_or_null i32 [B, D] = the claimed ground truth's row or -1;
+ *   dbg_claimed_or_null i32 [B, G].
+ * R4, scda_map_recall_hip (bbox_helper.compute_recall): proposals f32 [B, P, prop_w] (columns 1..4 = the box), rows <
+ *   proposal_counts[b]; gts f32 [B, Gr, gt_w] (columns 0..3), rows < gt_counts[b].  Per (ground truth, proposal) the float32 IoU of
+ *   scda_bbox_overlaps_hip (no +1; boxes = the ground truth, query = the proposal); a ground truth is recalled if its row maximum is
+ *   > 0.5f.  counters i32 [2]: [0] += recalled, [1] += gt_counts[b] (also without proposals) -- integer atomic adds, ACCUMULATE.
+ * R3, scda_map_accumulate_hip (cal_mAP :105-131) over the rows of n_images images (score, cls, rank, kept, tp [n_images, D] as written
+ *   above, the images in the order they were added).  Per class the kept rows in the order of the reference's stable sort by
+ *   descending score -- equal scores keep the image order, then the row order -- produced by the stable LSD radix sort of
+ *   csrc/radix_sort.h over the rows in (image, rank) order: 4 passes by score, 1 by class.  tp, fp cumulative counts; rec = tp /
+ *   sum_gt[c], prec = tp / (tp + fp) in double; env = the running maximum of prec from the right; ap = rec[0] * env[0] + sum_v (rec[v]
+ *   - rec[v-1]) * env[v], summed left to right in double by one lane; max_recall = max(rec), NaN if any rec is NaN.  sum_gt i32 [C] on
+ *   the device: the meta file's counts, or gt_num.  A class with rows and sum_gt == 0 gives NaN as IEEE 0 / 0 does; a class without
+ *   rows gives ap = max_recall = 0 and rows = 0 (the reference raises ValueError there: np.max of an empty array).  ap, max_recall
+ *   f64 [C], rows i32 [C]; entry 0 is 0.  ws: scda_map_accumulate_workspace_bytes(n_images, D) bytes, 16-byte aligned. */
+int scda_map_rows_hip(const float *detections, const int *detection_counts, int B, int D, const float *image_info, int info_w,
+                      int scale_column, int num_classes, int keep_num, int *box, float *score, int *cls, int *rank, int *kept, int *tp,
+                      int *dbg_match_or_null, int G, int *dbg_claimed_or_null, void *stream);
+int scda_map_match_hip(const int *box, const int *cls, const int *rank, const int *kept, int B, int D, const int *gt_boxes,
+                       const int *gt_counts, int G, int num_classes, double iou_thr, int *tp, int *gt_num, int *dbg_match_or_null,
+                       int *dbg_claimed_or_null, void *stream);
+int scda_map_recall_hip(const float *proposals, const int *proposal_counts, int B, int P, int prop_w, const float *gts,
+                        const int *gt_counts, int Gr, int gt_w, int *counters, void *stream);
+size_t scda_map_accumulate_workspace_bytes(int n_images, int D);
+int scda_map_accumulate_hip(int n_images, int D, const float *score, const int *cls, const int *rank, const int *kept, const int *tp,
+                            const int *sum_gt, int num_classes, void *ws, double *ap, double *max_recall, int *rows, void *stream);
+
 /* ------------------------------------------------- convolution / GEMM ---- */
 /* The reference reaches these through torch.nn (cuDNN / cuBLAS): nn.Conv2d in
  * models/faster_rcnn/vgg_adver_expansion_cluster.py:101-114 (VGG body),

@@ -7,11 +7,12 @@
 //   det_rows_kernel     per detection slot: xywh and area in double from the float32 corners, score, category (0 = padding)
 //   box_iou_kernel      per (image, gt, dt) pair: bbIou
 //   match_kernel        per (image, category): ranks, the GT orders, evaluateImg's greedy matching, one lane per (area range, threshold)
-//   sort_*_kernel       stable LSD radix sort, 8 bits per pass: per-tile histograms, one scan, a stable scatter (wave match by ballots)
+//   sort_*_kernel       the stable LSD radix sort of radix_sort.h, 8 bits per pass, over the keys of SortKey
 //   gather_kernel       the rows in sorted order (score, rank, match bits), category segments
 //   pr_kernel           per (category, area range, maxDets): tp / fp scans, precision envelope, the recall thresholds
 //   stats_kernel        the 12 numbers of _summarizeDets
 #include "common.h"
+#include "radix_sort.h"
 
 namespace {
 using namespace scda;
@@ -216,8 +217,8 @@ __global__ __launch_bounds__(kMatchThreads) void match_kernel(MatchArgs p) {
     }
 }
 
-// ------------------------------------------------------------------------------------------------ the stable radix sort
-constexpr int kSortRounds = 16, kSortTile = 64 * kSortRounds;
+// ------------------------------------------------------------------------------------------------ the sort keys (radix_sort.h)
+using radix::sort_pass;
 
 struct SortKey {
     int kind;                                   // 0: image id, 1: score (descending), 2: category (0 = the row takes no part)
@@ -226,21 +227,18 @@ struct SortKey {
     const float *score;
     const int *cat, *rank;
     int max_det;
-};
-
-__device__ inline uint32_t sort_digit(const SortKey &k, uint32_t e) {
-    uint32_t v;
-    if (k.kind == 0) {
-        v = (uint32_t)k.ids[e] ^ 0x80000000u;
-    } else if (k.kind == 1) {
-        const float s = k.score[e];
-        const uint32_t u = s == 0.0f ? 0u : __float_as_uint(s);
-        v = ~((u & 0x80000000u) ? ~u : (u | 0x80000000u));
-    } else {
-        v = (k.cat[e] > 0 && k.rank[e] < k.max_det) ? (uint32_t)k.cat[e] : 0u;
+    __device__ uint32_t digit(uint32_t e) const {
+        uint32_t v;
+        if (kind == 0) {
+            v = (uint32_t)ids[e] ^ 0x80000000u;
+        } else if (kind == 1) {
+            v = radix::score_descending(score[e]);
+        } else {
+            v = (cat[e] > 0 && rank[e] < max_det) ? (uint32_t)cat[e] : 0u;
+        }
+        return (v >> shift) & 255u;
     }
-    return (v >> k.shift) & 255u;
-}
+};
 
 __global__ __launch_bounds__(256) void iota_kernel(uint32_t *out, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -251,86 +249,6 @@ __global__ __launch_bounds__(256) void iota_kernel(uint32_t *out, int n) {
 __global__ __launch_bounds__(256) void rows_kernel(const uint32_t *__restrict__ img_order, int D, uint32_t *out, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = img_order[i / D] * (uint32_t)D + (uint32_t)(i % D);
-}
-
-// grid (tiles), 64 threads: hist [tiles, 256]
-__global__ __launch_bounds__(64) void sort_hist_kernel(const uint32_t *__restrict__ src, int n, SortKey key, uint32_t *__restrict__ hist) {
-    __shared__ uint32_t h[256];
-    const int lane = threadIdx.x;
-    for (int q = lane; q < 256; q += 64) h[q] = 0;
-    __syncthreads();
-    for (int r = 0; r < kSortRounds; ++r) {
-        const int i = blockIdx.x * kSortTile + r * 64 + lane;
-        if (i < n) atomicAdd(&h[sort_digit(key, src[i])], 1u);
-    }
-    __syncthreads();
-    for (int q = lane; q < 256; q += 64) hist[(size_t)blockIdx.x * 256 + q] = h[q];
-}
-
-// exclusive scan of one value per thread over 256 threads
-__device__ inline uint32_t block_excl_scan256(uint32_t v, uint32_t *wave_sums, uint32_t *total) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    uint32_t inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t o = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += o;
-    }
-    __syncthreads();
-    if (lane == 63) wave_sums[wv] = inc;
-    __syncthreads();
-    uint32_t before = 0, all = 0;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        if (q < wv) before += wave_sums[q];
-        all += wave_sums[q];
-    }
-    *total = all;
-    return before + inc - v;
-}
-
-// one block of 256 threads: hist [tiles, 256] -> each (tile, digit)'s first output index, digits major
-__global__ __launch_bounds__(256) void sort_scan_kernel(uint32_t *__restrict__ hist, int tiles) {
-    __shared__ uint32_t wave_sums[4];
-    const int d = threadIdx.x;
-    uint32_t tot = 0;
-    for (int b = 0; b < tiles; ++b) tot += hist[(size_t)b * 256 + d];
-    uint32_t all;
-    uint32_t run = block_excl_scan256(tot, wave_sums, &all);
-    for (int b = 0; b < tiles; ++b) {
-        const uint32_t v = hist[(size_t)b * 256 + d];
-        hist[(size_t)b * 256 + d] = run;
-        run += v;
-    }
-}
-
-// grid (tiles), 64 threads: 64 elements per round; a lane's place among the lanes of its digit comes from 8 ballots
-__global__ __launch_bounds__(64) void sort_scatter_kernel(const uint32_t *__restrict__ src, uint32_t *__restrict__ dst, int n, SortKey key,
-                                                          const uint32_t *__restrict__ offs) {
-    __shared__ uint32_t base[256];
-    const int lane = threadIdx.x;
-    for (int q = lane; q < 256; q += 64) base[q] = offs[(size_t)blockIdx.x * 256 + q];
-    __syncthreads();
-    for (int r = 0; r < kSortRounds; ++r) {
-        const int i = blockIdx.x * kSortTile + r * 64 + lane;
-        const bool valid = i < n;
-        const uint32_t e = valid ? src[i] : 0u;
-        const uint32_t dg = valid ? sort_digit(key, e) : 0u;
-        unsigned long long peers = __ballot(valid);
-#pragma unroll
-        for (int bit = 0; bit < 8; ++bit) {
-            const bool s = (dg >> bit) & 1u;
-            const unsigned long long m = __ballot(valid && s);
-            peers &= s ? m : ~m;
-        }
-        const int before = __popcll(peers & ((1ull << lane) - 1ull)), all = __popcll(peers);
-        uint32_t pos = 0;
-        if (valid) pos = base[dg] + before;
-        __syncthreads();
-        if (valid && before == all - 1) base[dg] += all;
-        __syncthreads();
-        if (valid && pos < (uint32_t)n) dst[pos] = e;
-    }
 }
 
 // the rows in sorted order.  s_bits [A, n]
@@ -527,7 +445,7 @@ struct AccLayout { size_t perm_a, perm_b, img_a, img_b, hist, seg, s_score, s_ra
 AccLayout acc_layout(int n_images, int D, int K, int A) {
     AccLayout l;
     const size_t n = (size_t)n_images * D;
-    l.tiles = (int)((n + kSortTile - 1) / kSortTile);
+    l.tiles = (int)((n + radix::kSortTile - 1) / radix::kSortTile);
     size_t o = 0;
     auto take = [&](size_t bytes) { const size_t at = o; o += align256(bytes); return at; };
     l.perm_a = take(n * 4); l.perm_b = take(n * 4);
@@ -538,14 +456,6 @@ AccLayout acc_layout(int n_images, int D, int K, int A) {
     l.s_bits = take(n * 4 * A);
     l.total = o;
     return l;
-}
-
-// one stable pass: src -> dst
-void sort_pass(const uint32_t *src, uint32_t *dst, int n, const SortKey &key, uint32_t *hist, hipStream_t st) {
-    const int tiles = (n + kSortTile - 1) / kSortTile;
-    hipLaunchKernelGGL(sort_hist_kernel, dim3(tiles), dim3(64), 0, st, src, n, key, hist);
-    hipLaunchKernelGGL(sort_scan_kernel, dim3(1), dim3(256), 0, st, hist, tiles);
-    hipLaunchKernelGGL(sort_scatter_kernel, dim3(tiles), dim3(64), 0, st, src, dst, n, key, (const uint32_t *)hist);
 }
 
 }  // namespace

@@ -1,8 +1,10 @@
 """utils.cal_mAP -- Cityscapes-style detection mAP, the contract of the reference's utils/cal_mAP.py.
 
-Host-side bookkeeping over text lists (a few thousand rows per validation pass), so it stays on the CPU; the matching
-is done per class with the IoUs of one detection against all ground truths of its image computed as one numpy
-expression.  Everything a caller of the reference can observe is kept:
+Host-side bookkeeping over text lists: the file path of validate(), and the one a data-parallel validation keeps.  The
+matching is done per class with the IoUs of one detection against all ground truths of its image computed as one numpy
+expression.  The same metric without the text files and without a wait for the host per batch is scda_amd.map_eval
+(MapEvaluator, evaluate.map_stats: these rules in HIP on the Predictor's device-resident results, bit for bit).
+Everything a caller of the reference can observe is kept:
   * results rows `name x1 y1 x2 y2 score label`, coordinates truncated with int(float(.))        (cal_mAP.py:49-66)
   * IoU with the +1 pixel convention, only for boxes that STRICTLY overlap in both axes; the first ground truth with
     the largest IoU wins; no overlap at all -> (-1, -1)                                         (cal_mAP.py:68-93)

@@ -176,3 +176,60 @@ def coco_stats(loader, predictor, evaluator, device=None):
                 kw = {'mask_bits': out[4], 'det_areas': out[5]['area'], 'gt_mask_bits': gt[5], 'sizes': item.get('sizes')}
             evaluator.add(item['image_ids'], out[2], out[3], *gt[:5], **kw)
     return evaluator.summarize()
+
+
+def meta_ground_truth(val_meta_file, num_classes):
+    """The validation meta file (or its lines) as MapEvaluator takes ground truth: {pure_name: int32 [n, 5] = (x1, y1, x2, y2, label), in
+    meta order, 'num': int64 [num_classes]}.  The record layout is the one utils.cal_mAP.parse_gts reads: a '#' line, +1 the path (the
+    pure name is its last component without the 4-character extension), +7 the box count, +8... `label x1 y1 x2 y2`.  Every row is kept
+    as written; rows with a label outside 1..num_classes-1 take no part in the matching and are not counted in 'num'."""
+    if isinstance(val_meta_file, (list, tuple)):
+        lines = list(val_meta_file)
+    else:
+        with open(val_meta_file, 'r', encoding='utf-8') as f:
+            lines = f.readlines()
+    gts = {'num': np.zeros(num_classes, dtype=np.int64)}
+    for at, line in enumerate(lines):
+        if not line.startswith('#'):
+            continue
+        name = lines[at + 1].strip().split('/')[-1][0:-4]
+        count = int(lines[at + 7])
+        rows = np.zeros((count, 5), dtype=np.int32)
+        for k, row in enumerate(lines[at + 8: at + 8 + count]):
+            f = row.split()
+            rows[k] = (int(f[1]), int(f[2]), int(f[3]), int(f[4]), int(f[0]))
+        gts[name] = rows
+        labels = rows[:, 4]
+        gts['num'] += np.bincount(labels[(labels >= 1) & (labels < num_classes)], minlength=num_classes)[:num_classes]
+    return gts
+
+
+def map_stats(loader, predictor, evaluator, ground_truth, scale_column=-1, device=None):
+    """Drives a scda_amd.infer.Predictor over validate()'s loader into a scda_amd.map_eval.MapEvaluator and returns its summary: what
+    Cal_MAP computes from validate()'s rows (ap, max_recall, mAP) plus validate()'s RPN recall, without the text files and with one
+    wait for the host, the last one.  Loader items are validate()'s tuples: item[0] image [b, 3, h, w], item[1] image_info [b, >= 3],
+    item[2] gts [b, G, 5] (for the recall, every row counted as the reference counts them), item[-1] filenames.  ground_truth:
+    meta_ground_truth(...); each file's pure name is looked up there, an image missing there gets zero ground truths.  scale_column:
+    the image_info column the boxes are divided by (-1; 2 is the reference's dataset == 'coco' choice).  validate() is not involved."""
+    from scda_amd import native
+    device = evaluator.device if device is None else device
+    G = evaluator.G
+    with torch.no_grad():
+        for item in loader:
+            img, img_info, gt_boxes, filenames = item[0], item[1], item[2], item[-1]
+            B = img.shape[0]
+            out = predictor(img.to(device, non_blocking=True), img_info)
+            on_device = torch.is_tensor(img_info) and img_info.is_cuda and img_info.dtype == torch.float32 and img_info.is_contiguous()
+            info = img_info if on_device else predictor.image_info          # the Predictor's own upload of a host image_info
+            boxes, counts = np.zeros((B, G, 5), dtype=np.int32), np.zeros(B, dtype=np.int32)
+            for b in range(B):
+                rows = ground_truth.get(filenames[b].rsplit('/', 1)[-1].rsplit('.', 1)[0])
+                if rows is None:
+                    continue
+                if len(rows) > G:
+                    raise ValueError("map_stats: %s has %d ground truths, max_gts_per_image = %d" % (filenames[b], len(rows), G))
+                boxes[b, :len(rows)], counts[b] = rows, len(rows)
+            evaluator.add(out[2], out[3], info, native.upload(boxes, device), native.upload(counts, device), proposals=out[0],
+                          proposal_counts=out[1], recall_gts=native.upload(_np(gt_boxes).astype(np.float32), device),
+                          scale_column=scale_column)
+    return evaluator.summarize()

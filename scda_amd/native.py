@@ -707,6 +707,85 @@ def coco_summarize(precision, recall, shape, spec, stats):
     return stats
 
 
+# ------------------------------------------------- Cityscapes mAP (cal_mAP) --
+def _req_all(what, specs):
+    for t, name, dt, n in specs:
+        _req(t, name, dt)
+        if t.numel() < n:
+            raise ValueError(f"{what}: {name} holds {t.numel()} elements, {n} needed")
+
+
+def map_rows(detections, detection_counts, image_info, scale_column, num_classes, keep_num, box, score, cls, rank, kept, tp,
+             dbg_match=None, dbg_claimed=None, G=1):
+    """validate()'s rows of B images (include/scda_ops.h: scda_map_rows_hip, rule R1).  detections float32 [B, D, 7], detection_counts
+    int32 [B], image_info float32 [B, >= 2] -> the caller's box int32 [B, D, 4], score float32, cls / rank / kept / tp int32 [B, D];
+    dbg_match int32 [B, D] and dbg_claimed int32 [B, G] are reset when given."""
+    _req(detections, "detections"); _req(image_info, "image_info")
+    if detections.dim() != 3 or detections.shape[2] != 7 or image_info.dim() != 2 or image_info.shape[0] != detections.shape[0]:
+        raise ValueError("map_rows: detections [B, D, 7] and image_info [B, >= 2]")
+    B, D = detections.shape[:2]
+    info_w = image_info.shape[1]
+    scale_column = scale_column % info_w if -info_w <= scale_column < info_w else -1
+    _req_all("map_rows", ((detection_counts, "detection_counts", torch.int32, B), (box, "box", torch.int32, B * D * 4),
+                          (score, "score", torch.float32, B * D), (cls, "cls", torch.int32, B * D), (rank, "rank", torch.int32, B * D),
+                          (kept, "kept", torch.int32, B * D), (tp, "tp", torch.int32, B * D))
+             + (((dbg_match, "dbg_match", torch.int32, B * D),) if dbg_match is not None else ())
+             + (((dbg_claimed, "dbg_claimed", torch.int32, B * G),) if dbg_claimed is not None else ()))
+    _check(lib().scda_map_rows_hip(_p(detections), _p(detection_counts), B, D, _p(image_info), info_w, scale_column, int(num_classes),
+                                   int(keep_num), _p(box), _p(score), _p(cls), _p(rank), _p(kept), _p(tp), _p(dbg_match), int(G),
+                                   _p(dbg_claimed), _stream()), "scda_map_rows_hip")
+
+
+def map_match(box, cls, rank, kept, gt_boxes, gt_counts, num_classes, iou_thr, tp, gt_num, dbg_match=None, dbg_claimed=None):
+    """calIoU and cal_mAP's claims for B images (include/scda_ops.h: scda_map_match_hip, rule R2).  box int32 [B, D, 4], cls / rank /
+    kept int32 [B, D] as map_rows wrote them, gt_boxes int32 [B, G, 5] = (x1, y1, x2, y2, label), gt_counts int32 [B] -> tp int32
+    [B, D]; gt_num int32 [C] accumulated.  dbg_match int32 [B, D], dbg_claimed int32 [B, G] or None."""
+    if gt_boxes.dim() != 3 or gt_boxes.shape[2] != 5 or cls.dim() != 2 or gt_boxes.shape[0] != cls.shape[0]:
+        raise ValueError("map_match: gt_boxes [B, G, 5] and cls [B, D]")
+    B, D = cls.shape
+    G = gt_boxes.shape[1]
+    _req_all("map_match", ((box, "box", torch.int32, B * D * 4), (cls, "cls", torch.int32, B * D), (rank, "rank", torch.int32, B * D),
+                           (kept, "kept", torch.int32, B * D), (gt_boxes, "gt_boxes", torch.int32, B * G * 5),
+                           (gt_counts, "gt_counts", torch.int32, B), (tp, "tp", torch.int32, B * D),
+                           (gt_num, "gt_num", torch.int32, int(num_classes)))
+             + (((dbg_match, "dbg_match", torch.int32, B * D),) if dbg_match is not None else ())
+             + (((dbg_claimed, "dbg_claimed", torch.int32, B * G),) if dbg_claimed is not None else ()))
+    _check(lib().scda_map_match_hip(_p(box), _p(cls), _p(rank), _p(kept), B, D, _p(gt_boxes), _p(gt_counts), G, int(num_classes),
+                                    float(iou_thr), _p(tp), _p(gt_num), _p(dbg_match), _p(dbg_claimed), _stream()), "scda_map_match_hip")
+
+
+def map_recall(proposals, proposal_counts, gts, gt_counts, counters):
+    """compute_recall for B images (include/scda_ops.h: scda_map_recall_hip, rule R4).  proposals float32 [B, P, >= 5] (columns 1..4),
+    proposal_counts int32 [B], gts float32 [B, Gr, >= 4], gt_counts int32 [B] -> counters int32 [2] += (recalled, rows given)."""
+    _req(proposals, "proposals"); _req(gts, "gts")
+    if proposals.dim() != 3 or gts.dim() != 3 or gts.shape[0] != proposals.shape[0]:
+        raise ValueError("map_recall: proposals [B, P, >= 5] and gts [B, Gr, >= 4]")
+    B = proposals.shape[0]
+    _req_all("map_recall", ((proposal_counts, "proposal_counts", torch.int32, B), (gt_counts, "gt_counts", torch.int32, B),
+                            (counters, "counters", torch.int32, 2)))
+    _check(lib().scda_map_recall_hip(_p(proposals), _p(proposal_counts), B, proposals.shape[1], proposals.shape[2], _p(gts),
+                                     _p(gt_counts), gts.shape[1], gts.shape[2], _p(counters), _stream()), "scda_map_recall_hip")
+
+
+def map_accumulate_workspace_bytes(n_images, D):
+    return int(lib().scda_map_accumulate_workspace_bytes(n_images, D))
+
+
+def map_accumulate(n_images, score, cls, rank, kept, tp, sum_gt, ws, ap, max_recall, rows):
+    """cal_mAP's accumulation over the first n_images images' rows (include/scda_ops.h: scda_map_accumulate_hip, rule R3); sum_gt int32
+    [C] on the device -> ap, max_recall float64 [C], rows int32 [C]; every tensor is the caller's"""
+    D, C = cls.shape[1], sum_gt.numel()
+    _req_all("map_accumulate", ((score, "score", torch.float32, n_images * D), (cls, "cls", torch.int32, n_images * D),
+                                (rank, "rank", torch.int32, n_images * D), (kept, "kept", torch.int32, n_images * D),
+                                (tp, "tp", torch.int32, n_images * D), (sum_gt, "sum_gt", torch.int32, C), (ap, "ap", torch.float64, C),
+                                (max_recall, "max_recall", torch.float64, C), (rows, "rows", torch.int32, C), (ws, "ws", torch.uint8, 1)))
+    need = map_accumulate_workspace_bytes(n_images, D)
+    if need == 0 or ws.numel() < need:
+        raise ValueError("map_accumulate: workspace too small or sizes out of range")
+    _check(lib().scda_map_accumulate_hip(n_images, D, _p(score), _p(cls), _p(rank), _p(kept), _p(tp), _p(sum_gt), C, _p(ws), _p(ap),
+                                         _p(max_recall), _p(rows), _stream()), "scda_map_accumulate_hip")
+
+
 # ------------------------------------------------- convolution / GEMM -------
 _WS = {}
 
