@@ -253,6 +253,30 @@ size_t scda_box_predict_workspace_bytes(int B, int P, int C);
 int scda_box_predict_hip(const float *rois, const int *roi_counts, int B, int P, const float *prob, const float *loc, int C,
                          const float *image_info, int info_stride, const double *stds_host, const double *means_host,
                          float score_thresh, float nms_thresh, int top_n, void *ws, float *det, int *det_counts, void *stream);
+/* Soft-NMS at test time (scda_amd/csrc/soft_nms.hip): extensions/_cython_bbox/cython_nms.pyx:98-203 for S independent lists in one
+ * launch, one wave per list, bit for bit.  boxes / seg as scda_nms_segments_hip reads them (lists back to back, seg [S][3] = {first
+ * row, length, unused here}); the lists need NOT be sorted.  method 0 hard (ov > Nt drops), 1 linear (ov > Nt: score * (1 - ov)),
+ * 2 Gaussian (score * exp(-ov^2 / sigma)); a rescored row is discarded when its score falls below threshold.  keep: from a list's
+ * first row on, its surviving rows as LOCAL indices in selection order (the reference's returned `inds`); num_out [S]: their
+ * counts; the score column of boxes is rewritten IN PLACE with each surviving row's final score (a discarded row's score is
+ * unspecified), so boxes[first + keep[j]] is the reference's j-th returned row.  No workspace.  A list of length 0 gives count 0.
+ * Capacity: max_n <= scda_soft_nms_capacity() = 2048 rows per list (its working copy fills 48 KB of LDS); a larger max_n, S <= 0 or
+ * a method outside 0..2 returns SCDA_EINVAL before anything is launched.  Inputs are finite: the result for NaN scores is undefined
+ * (it stays within bounds and terminates).  Gaussian caveat: the weight is the DEVICE's double exp rounded to float32, the
+ * reference's is glibc's; the two may differ in the last place of the double, which changes the float32 weight only when the value
+ * lies within about 2^-53 relative of a float32 rounding midpoint -- about one evaluation in 2^28. */
+int scda_soft_nms_capacity(void);
+int scda_soft_nms_segments_hip(float *boxes, const long long *seg, int S, int max_n, int method, float sigma, float Nt, float threshold,
+                               int64_t *keep, int64_t *num_out, void *stream);
+/* scda_box_predict_hip with that sweep in place of scda_nms_segments_hip: the same decode + sort, the soft sweep of every (image,
+ * class) list, then the per-image top_n ranked by the RESCORED scores (equal scores: the later row of the class-major list of
+ * selections first, as before, a class's rows now standing in selection order).  nms_thresh plays no part, Nt does.  The same ws
+ * (scda_box_predict_workspace_bytes; the mask piece goes unused).  P above scda_soft_nms_capacity() or a method outside 0..2 returns
+ * SCDA_EINVAL before anything is launched. */
+int scda_box_predict_soft_hip(const float *rois, const int *roi_counts, int B, int P, const float *prob, const float *loc, int C,
+                              const float *image_info, int info_stride, const double *stds_host, const double *means_host,
+                              float score_thresh, int top_n, int method, float sigma, float Nt, float threshold, void *ws, float *det,
+                              int *det_counts, void *stream);
 
 /* ---- instance masks of the mask-branch detector (scda_amd/csrc/mask_ops.hip; opt-in: scda_amd.infer.Predictor(masks=True)) ----------
  * The detections as RoIs of the mask head: det [B, top_n, 7] + det_counts i32 [B] (scda_box_predict_hip's outputs) ->

@@ -372,12 +372,16 @@ SCDA_API int scda_rpn_proposals_hip(const float *prob, const float *loc, const d
 
 SCDA_API size_t scda_box_predict_workspace_bytes(int B, int P, int C) { return BoxWs(nullptr, B, P, C).bytes; }
 
-SCDA_API int scda_box_predict_hip(const float *rois, const int *roi_counts, int B, int P, const float *prob, const float *loc, int C,
-                                  const float *image_info, int info_stride, const double *stds_host, const double *means_host,
-                                  float score_thresh, float nms_thresh, int top_n, void *ws, float *det, int *det_counts, void *stream) {
-    INFER_CHECK(rois && roi_counts && prob && loc && image_info && stds_host && means_host && ws && det && det_counts && B > 0 &&
-                P > 0 && P < 65536 && C > 1 && C < 65536 && (long long)B * (C - 1) <= 65535 && info_stride >= 2 && top_n > 0,
-                "scda_box_predict_hip")
+// the three stages of both entry points; method < 0: hard NMS at nms_thresh, else the soft sweep of soft_nms.hip in its place
+static int box_predict(const char *name, const float *rois, const int *roi_counts, int B, int P, const float *prob, const float *loc, int C,
+                       const float *image_info, int info_stride, const double *stds_host, const double *means_host, float score_thresh,
+                       float nms_thresh, int method, float sigma, float Nt, float threshold, int top_n, void *ws, float *det,
+                       int *det_counts, void *stream) {
+    if (!(rois && roi_counts && prob && loc && image_info && stds_host && means_host && ws && det && det_counts && B > 0 && P > 0 &&
+          P < 65536 && C > 1 && C < 65536 && (long long)B * (C - 1) <= 65535 && info_stride >= 2 && top_n > 0)) {
+        set_error("%s: bad arguments", name);
+        return SCDA_EINVAL;
+    }
     BoxNorm norm;
     for (int q = 0; q < 4; ++q) { norm.std[q] = stds_host[q]; norm.mean[q] = means_host[q]; }
     BoxWs w(ws, B, P, C);
@@ -386,8 +390,33 @@ SCDA_API int scda_box_predict_hip(const float *rois, const int *roi_counts, int 
                        info_stride, norm, score_thresh, w.gkeys, w.boxes5, w.seg);
     int e = launch_status("box_decode_sort_kernel");
     if (e) return e;
-    if ((e = scda_nms_segments_hip(w.boxes5, w.seg, B * (C - 1), P, nms_thresh, w.mask, (int64_t *)w.keep, (int64_t *)w.num, stream))) return e;
+    if (method < 0)
+        e = scda_nms_segments_hip(w.boxes5, w.seg, B * (C - 1), P, nms_thresh, w.mask, (int64_t *)w.keep, (int64_t *)w.num, stream);
+    else   // rescoring in place: box_topn_kernel reads boxes5[keep[j]] as before, rank j now being the selection order
+        e = scda_soft_nms_segments_hip(w.boxes5, w.seg, B * (C - 1), P, method, sigma, Nt, threshold, (int64_t *)w.keep, (int64_t *)w.num,
+                                       stream);
+    if (e) return e;
     hipLaunchKernelGGL(box_topn_kernel, dim3(B), dim3(kSortThreads), 0, st, w.boxes5, w.keep, w.num, P, C, top_n, w.gkeys_top, det,
                        det_counts);
     return launch_status("box_topn_kernel");
+}
+
+SCDA_API int scda_box_predict_hip(const float *rois, const int *roi_counts, int B, int P, const float *prob, const float *loc, int C,
+                                  const float *image_info, int info_stride, const double *stds_host, const double *means_host,
+                                  float score_thresh, float nms_thresh, int top_n, void *ws, float *det, int *det_counts, void *stream) {
+    return box_predict("scda_box_predict_hip", rois, roi_counts, B, P, prob, loc, C, image_info, info_stride, stds_host, means_host,
+                       score_thresh, nms_thresh, -1, 0.f, 0.f, 0.f, top_n, ws, det, det_counts, stream);
+}
+
+SCDA_API int scda_box_predict_soft_hip(const float *rois, const int *roi_counts, int B, int P, const float *prob, const float *loc, int C,
+                                       const float *image_info, int info_stride, const double *stds_host, const double *means_host,
+                                       float score_thresh, int top_n, int method, float sigma, float Nt, float threshold, void *ws,
+                                       float *det, int *det_counts, void *stream) {
+    if (method < 0 || method > 2 || P > scda_soft_nms_capacity()) {      // before anything is launched
+        set_error("scda_box_predict_soft_hip: method %d outside 0..2 or P %d above the soft-NMS capacity %d", method, P,
+                  scda_soft_nms_capacity());
+        return SCDA_EINVAL;
+    }
+    return box_predict("scda_box_predict_soft_hip", rois, roi_counts, B, P, prob, loc, C, image_info, info_stride, stds_host, means_host,
+                       score_thresh, 0.f, method, sigma, Nt, threshold, top_n, ws, det, det_counts, stream);
 }

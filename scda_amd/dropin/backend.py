@@ -105,6 +105,54 @@ def nms_segments(lists, thresh):
             for a in lists]
 
 
+def _hip_soft_nms_segments(lists, method, sigma, Nt, threshold):
+    """lists: float32 arrays [n_i, 5] in any order -> list of (rows [k_i, 5] with their final scores, inds [k_i]) in selection order:
+    ONE upload, ONE launch, ONE download"""
+    dev = torch.device("cuda", torch.cuda.current_device())
+    lens = [int(a.shape[0]) for a in lists]
+    rows, max_n = sum(lens), max(lens, default=0)
+    if rows == 0:
+        return [(np.zeros((0, 5), dtype=np.float32), np.zeros(0, dtype=np.int64)) for _ in lists]
+    if max_n > native.soft_nms_capacity():
+        raise ValueError("soft_nms_segments: a list of %d rows exceeds the kernel's capacity of %d" % (max_n, native.soft_nms_capacity()))
+    packed = np.concatenate([np.ascontiguousarray(a[:, :5], dtype=np.float32).reshape(-1, 5) for a in lists], 0)
+    seg = np.zeros((len(lists), 3), dtype=np.int64)
+    seg[:, 1] = lens
+    seg[1:, 0] = np.cumsum(lens)[:-1]
+    aux = _aux_stream(dev)
+    with torch.cuda.stream(aux):
+        b = _pinned(packed).to(dev, non_blocking=True)
+        sg = _pinned(seg).to(dev, non_blocking=True)
+        keep, num = native.soft_nms_segments(b, sg, max_n, method, sigma, Nt, threshold)
+        # [keep | num | the rescored score column as its int32 bits, widened] in one transfer
+        host = torch.empty(2 * rows + len(lists), dtype=torch.int64, pin_memory=True)
+        host[:rows].copy_(keep[:rows], non_blocking=True)
+        host[rows:rows + len(lists)].copy_(num[:len(lists)], non_blocking=True)
+        host[rows + len(lists):].copy_(b[:, 4].contiguous().view(torch.int32), non_blocking=True)
+        aux.synchronize()
+    h = host.numpy()
+    scores = h[rows + len(lists):].astype(np.int32).view(np.float32)
+    out = []
+    for i, o in enumerate(seg[:, 0]):
+        inds = h[o:o + int(h[rows + i])].copy()
+        kept = packed[o + inds]
+        kept[:, 4] = scores[o + inds]
+        out.append((kept, inds))
+    return out
+
+
+def soft_nms_segments(lists, method=0, sigma=0.5, Nt=0.3, threshold=0.001):
+    """cython_nms.soft_nms of several independent lists at once (float32 [n_i, 5], in any order) -> per list the reference's
+    (boxes, inds): the surviving rows with their final scores in selection order and their indices in the list.  With a substituted
+    nms hook (tests on the CPU): the host loop of extensions/_cython_bbox/cython_nms.py per list."""
+    lists = [np.ascontiguousarray(a, dtype=np.float32) for a in lists]
+    if _impl.get("nms") is None:
+        return _hip_soft_nms_segments(lists, int(method), float(sigma), float(Nt), float(threshold))
+    from scda_amd.dropin.extensions._cython_bbox import cython_nms
+    return [tuple(np.asarray(r) for r in cython_nms.soft_nms(a, sigma=sigma, Nt=Nt, threshold=threshold, method=method)) if a.shape[0]
+            else (np.zeros((0, 5), dtype=np.float32), np.zeros(0, dtype=np.int64)) for a in lists]
+
+
 def host_array(x, copy=False):
     """numpy view of `x` on the host.  Device tensors that were built from host data carry their host original along as
     `_scda_host` (ground-truth boxes, sampled RoIs): reading that costs nothing, whereas `.cpu()` is a synchronous copy on

@@ -64,9 +64,16 @@ class Predictor:
     [B, top_n, cap * chars per count], area int32 [B, top_n], bbox int32 [B, top_n, 4] = (x, y, w, h) of the MASK as rleToBbox gives it,
     size int32 [B, 2] = the (h, w) every mask of the image was encoded at (image_info[b, 0:2], read on the device).  Padding detections
     carry the empty-mask code.  rle_capacity: runs kept per detection, default 4 * W (two segments per column on average over the whole
-    width); a default, not a guarantee: segm_rows encodes an overflowing mask on the host."""
+    width); a default, not a guarantee: segm_rows encodes an overflowing mask on the host.
 
-    def __init__(self, model, cfg, masks=False, mask_threshold=0.5, rle=False, rle_capacity=None):
+    soft_nms={'method': 'linear' | 'gaussian' | 'hard', 'sigma': 0.5, 'Nt': 0.3, 'threshold': 0.001} (any subset; the reference's defaults
+    fill the rest): the per-class lists go through cython_nms.soft_nms on the device (scda_amd/csrc/soft_nms.hip, bit for bit) in place
+    of the hard NMS, and the per-image top_n ranks by the rescored scores -- the rows the eval forward gives with the same dict under
+    test_predict_bbox_cfg's `soft_nms` key, which is also where this argument's default comes from (the argument overrides the key).
+    None and no key: hard NMS, the bytes as ever.  ValueError for an unknown method, a sigma <= 0 or a post_nms_top_n above the kernel's
+    capacity of 2048 rows per list.  The RPN stage keeps its hard NMS."""
+
+    def __init__(self, model, cfg, masks=False, mask_threshold=0.5, rle=False, rle_capacity=None, soft_nms=None):
         if model.training:
             raise ValueError("Predictor: put the detector in eval mode first (model.eval())")
         self.masks, self.mask_threshold = bool(masks), float(mask_threshold)
@@ -89,6 +96,11 @@ class Predictor:
                              "(bbox_normalize_stats_precomputed = true); this cfg does not")
         if int(self.box_cfg['top_n']) <= 0:
             raise ValueError("Predictor: test_predict_bbox_cfg.top_n must be > 0 (the detections have a fixed capacity)")
+        # soft-NMS in place of the per-class hard NMS: the explicit argument, else test_predict_bbox_cfg's optional `soft_nms` key
+        self.soft_nms = N.soft_nms_setting(soft_nms if soft_nms is not None else self.box_cfg.get('soft_nms'))
+        if self.soft_nms is not None and int(self.rpn_cfg['post_nms_top_n']) > N.soft_nms_capacity():
+            raise ValueError("Predictor: soft_nms holds a class list of at most %d rows; test_rpn_proposal_cfg.post_nms_top_n is %d"
+                             % (N.soft_nms_capacity(), int(self.rpn_cfg['post_nms_top_n'])))
         self.shape = None
         self.images = self.image_info = None
         self.graph = None
@@ -193,7 +205,7 @@ class Predictor:
             raise ValueError("Predictor: the head's class count differs from cfg num_classes")
         N.box_predict(self.rois, self.counts, cprob, bloc.detach().contiguous(), info, bc['bbox_normalize_stds'],
                       bc['bbox_normalize_means'], float(bc['score_thresh']), float(bc['nms_iou_thresh']), self.top_n, self.box_ws,
-                      self.det, self.det_counts)
+                      self.det, self.det_counts, soft_nms=self.soft_nms)
         self._out = (self.props.view(B, self.P, 6), self.counts, self.det, self.det_counts)
         if self.masks:
             self._out += (self._masks(feat, B, images.shape[2], images.shape[3]),)
@@ -225,19 +237,24 @@ class Predictor:
 _PREDICTORS = {}
 
 
-def predict(model, images, image_info, cfg, masks=False, mask_threshold=0.5, rle=False, rle_capacity=None):
+def predict(model, images, image_info, cfg, masks=False, mask_threshold=0.5, rle=False, rle_capacity=None, soft_nms=None):
     """images [B,3,H,W] on the device, image_info [B,>=2] (host or device) -> device tensors
     (proposals [B,P,6] = (b, x1, y1, x2, y2, score), proposal_counts int32 [B], detections [B,top_n,7] =
     (b, x1, y1, x2, y2, score, class), detection_counts int32 [B]); rows past an image's count are padding.
     masks=True: a fifth tensor, mask_bits int32 [B,top_n,H,ceil(W/32)] (see Predictor); rle=True on top: a sixth element, the dict of
     run-length results (see Predictor, segm_rows).
-    One Predictor per (model, cfg, masks, mask_threshold, rle, rle_capacity) is kept and reused; its buffers are overwritten by the next call."""
+    soft_nms: see Predictor (a dict; None = the cfg's own `soft_nms` key, if any).
+    One Predictor per (model, cfg, masks, mask_threshold, rle, rle_capacity, soft_nms) is kept and reused; its buffers are overwritten by
+    the next call."""
     key = (id(model), id(cfg)) if not masks else (id(model), id(cfg), True, float(mask_threshold))
     if rle:
         key += ('rle', rle_capacity)
+    if soft_nms is not None:
+        key += ('soft_nms', N.soft_nms_setting(soft_nms))
     p = _PREDICTORS.get(key)
     if p is None or p.model is not model:
-        p = _PREDICTORS[key] = Predictor(model, cfg, masks=masks, mask_threshold=mask_threshold, rle=rle, rle_capacity=rle_capacity)
+        p = _PREDICTORS[key] = Predictor(model, cfg, masks=masks, mask_threshold=mask_threshold, rle=rle, rle_capacity=rle_capacity,
+                                         soft_nms=soft_nms)
     return p(images, image_info)
 
 

@@ -135,6 +135,55 @@ def nms_segments(boxes, seg, max_n, thresh):
     return keep, num
 
 
+SOFT_NMS_METHODS = {"hard": 0, "linear": 1, "gaussian": 2}
+SOFT_NMS_DEFAULTS = {"method": "hard", "sigma": 0.5, "Nt": 0.3, "threshold": 0.001}       # the reference's (cython_nms.pyx:98-104)
+
+
+def soft_nms_capacity():
+    """rows of one list the soft-NMS kernel holds in LDS"""
+    return int(lib().scda_soft_nms_capacity())
+
+
+def soft_nms_setting(spec):
+    """a `soft_nms` setting -> None (hard NMS as ever) or (method 0..2, sigma, Nt, threshold).  spec: None, or a dict with any of
+    'method' ('hard' | 'linear' | 'gaussian' or 0 | 1 | 2), 'sigma', 'Nt', 'threshold'; what it leaves out takes the reference's
+    default (method 0 -- the sweep's own hard rule, ov > Nt drops --, sigma 0.5, Nt 0.3, threshold 0.001).  ValueError for an unknown
+    key or method and a sigma <= 0."""
+    if spec is None:
+        return None
+    if not isinstance(spec, dict):
+        raise ValueError("soft_nms: expected None or a dict of %s, got %r" % (sorted(SOFT_NMS_DEFAULTS), spec))
+    unknown = sorted(set(spec) - set(SOFT_NMS_DEFAULTS))
+    if unknown:
+        raise ValueError("soft_nms: unknown keys %s (known: %s)" % (unknown, sorted(SOFT_NMS_DEFAULTS)))
+    s = dict(SOFT_NMS_DEFAULTS, **spec)
+    m = s["method"]
+    if isinstance(m, str):
+        if m not in SOFT_NMS_METHODS:
+            raise ValueError("soft_nms: unknown method %r (one of %s)" % (m, sorted(SOFT_NMS_METHODS)))
+        m = SOFT_NMS_METHODS[m]
+    if isinstance(m, bool) or m not in (0, 1, 2):
+        raise ValueError("soft_nms: unknown method %r (0 hard, 1 linear, 2 gaussian)" % (s["method"],))
+    sigma = float(s["sigma"])
+    if not sigma > 0:
+        raise ValueError("soft_nms: sigma must be > 0, got %r" % (s["sigma"],))
+    return int(m), sigma, float(s["Nt"]), float(s["threshold"])
+
+
+def soft_nms_segments(boxes, seg, max_n, method, sigma, Nt, threshold):
+    """soft-NMS (cython_nms.soft_nms) of S independent lists in one launch (scda_soft_nms_segments_hip): boxes [rows,5] fp32 CUDA (the
+    lists back to back, in any order), seg int64 [S,3] CUDA = (first row, length, unused) -> (keep int64 [rows] CUDA: each list's
+    surviving rows as local indices in selection order from its first row on, num int64 [S] CUDA); the score column of `boxes` is
+    rewritten in place with the survivors' final scores.  method 0 hard, 1 linear, 2 gaussian; max_n <= soft_nms_capacity()."""
+    _req(boxes, "boxes"); _req(seg, "seg", torch.int64)
+    S, rows = seg.shape[0], boxes.shape[0]
+    keep = torch.empty(max(rows, 1), dtype=torch.int64, device=boxes.device)
+    num = torch.zeros(max(S, 1), dtype=torch.int64, device=boxes.device)
+    _check(lib().scda_soft_nms_segments_hip(_p(boxes), _p(seg), S, max_n, method, sigma, Nt, threshold, _p(keep), _p(num), _stream()),
+           "scda_soft_nms_segments_hip")
+    return keep, num
+
+
 def nms_mask(boxes, thresh):
     _req(boxes, "boxes")
     n = boxes.shape[0]
@@ -364,19 +413,31 @@ def box_predict_workspace_bytes(B, P, C):
     return int(lib().scda_box_predict_workspace_bytes(B, P, C))
 
 
-def box_predict(rois, roi_counts, prob, loc, image_info, stds, means, score_thresh, nms_thresh, top_n, ws, det, det_counts):
+def box_predict(rois, roi_counts, prob, loc, image_info, stds, means, score_thresh, nms_thresh, top_n, ws, det, det_counts, soft_nms=None):
     """functions/predict_bbox.py for B images on the device: rois [B*P,5] with roi_counts int32 [B] real rows per image, prob [B*P,C],
-    loc [B*P,4C] -> det [B,top_n,7] (b, x1, y1, x2, y2, score, class), det_counts int32 [B] (the caller's buffers)"""
-    _req(rois, "rois"); _req(roi_counts, "roi_counts", torch.int32); _req(prob, "prob"); _req(loc, "loc")
-    _req(image_info, "image_info"); _req(ws, "ws", torch.uint8); _req(det, "det"); _req(det_counts, "det_counts", torch.int32)
+    loc [B*P,4C] -> det [B,top_n,7] (b, x1, y1, x2, y2, score, class), det_counts int32 [B] (the caller's buffers).
+    soft_nms: None = hard NMS at nms_thresh; a setting (soft_nms_setting's dict, or its tuple) = the soft sweep in its place
+    (scda_box_predict_soft_hip: nms_thresh plays no part, the top_n ranks by the rescored scores; P <= soft_nms_capacity())"""
     B = roi_counts.numel()
     R, C = prob.shape
     P = R // B
+    if soft_nms is not None:                        # the setting and the capacity first: a wrong one is the caller's, whatever the device
+        soft_nms = soft_nms if isinstance(soft_nms, tuple) else soft_nms_setting(soft_nms)
+        if P > soft_nms_capacity():
+            raise ValueError("box_predict: soft_nms holds a list of at most %d rows, P is %d" % (soft_nms_capacity(), P))
+    _req(rois, "rois"); _req(roi_counts, "roi_counts", torch.int32); _req(prob, "prob"); _req(loc, "loc")
+    _req(image_info, "image_info"); _req(ws, "ws", torch.uint8); _req(det, "det"); _req(det_counts, "det_counts", torch.int32)
     if P * B != R or rois.shape != (R, 5) or loc.shape != (R, 4 * C) or det.shape != (B, top_n, 7) or det_counts.numel() != B:
         raise ValueError("box_predict: inconsistent shapes")
     if ws.numel() < box_predict_workspace_bytes(B, P, C):
         raise ValueError("box_predict: workspace too small")
     s4, m4 = (ctypes.c_double * 4)(*[float(v) for v in stds]), (ctypes.c_double * 4)(*[float(v) for v in means])
+    if soft_nms is not None:
+        method, sigma, Nt, threshold = soft_nms
+        _check(lib().scda_box_predict_soft_hip(_p(rois), _p(roi_counts), B, P, _p(prob), _p(loc), C, _p(image_info), image_info.shape[1],
+                                               s4, m4, score_thresh, top_n, method, sigma, Nt, threshold, _p(ws), _p(det), _p(det_counts),
+                                               _stream()), "scda_box_predict_soft_hip")
+        return det, det_counts
     _check(lib().scda_box_predict_hip(_p(rois), _p(roi_counts), B, P, _p(prob), _p(loc), C, _p(image_info), image_info.shape[1], s4, m4,
                                       score_thresh, nms_thresh, top_n, _p(ws), _p(det), _p(det_counts), _stream()), "scda_box_predict_hip")
     return det, det_counts
