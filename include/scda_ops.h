@@ -306,6 +306,40 @@ int scda_mask_select_hip(const float *logits, long long stride_r, long long stri
  * that are not finite or beyond +-5e8, and rows with cls_or_null[r] < 0 (padding) give an empty mask. */
 int scda_mask_paste_hip(const float *rois, int roi_stride, const int *cls_or_null, const float *planes, int R, int ph, int pw, int H,
                         int W, int packed, float threshold, void *out, void *stream);
+/* tools/mask_rcnn_train_val.py:422-423 (write_results_to_file: the pasted float mask resized once more to the ORIGINAL image size,
+ * then `> mask_thresh`) under Pillow >= 7, one plane of [Ho, Wo] per RoI (scda_amd/csrc/mask_rescale.hip; opt-in:
+ * scda_amd.infer.Predictor(masks=True, original_size=(Ho, Wo))).  rois, cls_or_null, planes, ph, pw as scda_mask_paste_hip takes them;
+ * image_info float32 DEVICE rows of info_stride >= 5 floats (h, w, resize_scale, origin_h, origin_w), detection r belongs to image
+ * b = r / masks_per_image.  Per detection r of image b:
+ *   (h, w) = image_info[b][0:2], (oh, ow) = image_info[b][3:5], truncated towards zero;
+ *   P [h, w] = the float plane scda_mask_paste_hip (packed == 0) defines for the RoI, taken as the top-left h x w sub-plane of its
+ *   [H, W] plane: the window is clipped to h x w, and the resize never reads a column >= w or a row >= h (Pillow clamps the taps to
+ *   [0, n_in) of the h x w image, not of the padded batch plane);
+ *   O [oh, ow] = P resized under the axis rule stated above for the paste: BICUBIC, a = -0.5, support = 2 max(scale, 1), weights
+ *   normalised by their left-to-right double sum, each sample (float) of the left-to-right double sum of (double)pixel * w[k], the
+ *   horizontal pass w -> ow into a float32 intermediate [h, ow] first, then the vertical pass h -> oh, a pass of equal sizes skipped
+ *   ((oh, ow) == (h, w) gives P itself).  A down-scaled sample has up to ceil(2 n_in / n_out) * 2 + 1 taps.  One IEEE operation per
+ *   operator: Pillow's result bit for bit (tests/mask_orig_np.py, tests/test_mask_orig_rules.py).
+ * out: packed != 0: uint32 [R, Ho, ceil(Wo / 32)], bit (c % 32) of word c / 32 of row y = (O[y, c] > threshold) -- `>`, the reference's
+ * line 423, NOT the `>=` of scda_mask_paste_hip's packed form; packed == 0: float32 [R, Ho, Wo] = O.  Bits and values outside oh x ow
+ * are zero.  Every element of out, foot_rois and status is written (no clear needed; graph-capturable, no workspace, one launch).
+ * Footprint: an output sample none of whose taps [xmin, xmax) lies inside the RoI's window (clipped to h x w) on either axis is exactly
+ * +0.0f, its bit is (0.0f > threshold); the samples with a tap inside form one rectangle, written as foot_rois [R, 5] =
+ * (b, fx1, fy1, fx2, fy2), inclusive -- (b, 0, 0, -1, -1) when it is empty -- and only there is anything computed.  foot_rois may be
+ * given to scda_mask_rle_hip as its rois hint (with image_info + 3 as its sizes) when threshold >= 0.
+ * Limits, reported per image in status int32 [ceil(R / masks_per_image)] (0 = fine; the masks of a flagged image are EMPTY, all words
+ * zero whatever the threshold, its foot_rois empty; the other images are unaffected; nothing is read or written out of bounds):
+ *   1  oh > Ho or ow > Wo (the capacity of the output planes);
+ *   2  oh < 1 or ow < 1;
+ *   4  h > 4 oh or w > 4 ow: a down-scale above scda_mask_rescale_max_ratio() = 4.  A workgroup owns 32 output columns and blocks of 4
+ *      output rows; its LDS tiles hold the 31 * 4 + 2 * 8 + 1 = 141 columns and 3 * 4 + 2 * 8 + 1 = 29 rows of P those can reach at
+ *      ratio 4, and 17 weights per sample;
+ *   8  h or w outside [1, H] x [1, W], or a size that is not finite.
+ * Empty masks as for scda_mask_paste_hip (cls < 0, an empty or non-finite RoI).  R <= 65535, ph, pw <= 32. */
+int scda_mask_rescale_max_ratio(void);
+int scda_mask_rescale_hip(const float *rois, int roi_stride, const int *cls_or_null, const float *planes, int R, int ph, int pw, int H,
+                          int W, const float *image_info, int info_stride, int masks_per_image, int Ho, int Wo, int packed,
+                          float threshold, void *out, float *foot_rois, int *status, void *stream);
 
 /* ---- COCO run-length results from packed masks (scda_amd/csrc/mask_rle.hip; opt-in: scda_amd.infer.Predictor(masks=True, rle=True)) ----
  * The per-mask primitives of the reference's datasets/pycocotools/common/maskApi.c on scda_mask_paste_hip's packed planes, bit for bit

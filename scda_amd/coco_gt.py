@@ -131,7 +131,9 @@ def flatten_annotations(per_image_anns, sizes, gcap, plane=None):
 
 
 class GroundTruth:
-    """The device side of the ground truth of one loader: gcap slots per image in planes [H, Wd] (the Predictor's mask_bits planes).
+    """The device side of the ground truth of one loader: gcap slots per image in planes [H, Wd] -- the Predictor's mask_bits planes, or
+    with Predictor(original_size=(Ho, Wo)) its mask_bits_orig planes [Ho, ceil(Wo/32)], where COCO's annotations stand at their own
+    coordinates and need no rescaling.
     load() uploads the flat arrays of a batch through native.upload and rasterises them with one scda_mask_frpoly_hip call; the plane
     and workspace buffers are kept and grow only when a batch needs more, so a steady loader allocates nothing but the small uploads.
     The returned tensors are the evaluator's until the next load()."""

@@ -7,6 +7,7 @@
 // IEEE operation per source operator (compiled with -ffp-contract=off), which makes the result Pillow's bit for bit; the rule is
 // stated in include/scda_ops.h and restated in numpy by tests/test_mask_infer_rules.py.
 #include "common.h"
+#include "mask_resample.h"      // bicubic, axis_ksize, axis_taps, trunc_ok
 
 namespace {
 using namespace scda;
@@ -20,59 +21,6 @@ constexpr int kTmpStride = kStrip + kStrip / 32;    // room for the bit form's o
 // n_in - 1 samples
 constexpr int kTabH = kStrip * 5 > (kMaxIn - 1) * kMaxIn ? kStrip * 5 : (kMaxIn - 1) * kMaxIn;
 constexpr int kTabV = kRows * 5 > (kMaxIn - 1) * kMaxIn ? kRows * 5 : (kMaxIn - 1) * kMaxIn;
-
-__device__ inline double bicubic(double x) {
-    const double a = -0.5;
-    if (x < 0.0) x = -x;
-    if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1;
-    if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
-    return 0.0;
-}
-
-// the table stride of an axis n_in -> n_out: Pillow's ksize = ceil(support) * 2 + 1, never more than the n_in taps a sample can have
-__device__ inline int axis_ksize(int n_in, int n_out) {
-    if (n_in == n_out) return 1;
-    double fs = (double)n_in / n_out;
-    if (fs < 1.0) fs = 1.0;
-    const int ks = (int)ceil(2.0 * fs) * 2 + 1;
-    return ks < n_in ? ks : n_in;
-}
-
-// Pillow's precompute_coeffs for ONE output sample xx of an axis n_in -> n_out: first tap and tap count, normalised weights into w[]
-// (equal sizes: Pillow skips the pass -- one tap of weight 1 reproduces the sample)
-__device__ inline void axis_taps(int n_in, int n_out, int xx, int ks, int *first, int *count, double *w) {
-    if (n_in == n_out) {
-        *first = xx; *count = 1; w[0] = 1.0;
-        return;
-    }
-    const double scale = (double)n_in / n_out;
-    const double fs = scale < 1.0 ? 1.0 : scale;
-    const double support = 2.0 * fs, ss = 1.0 / fs;
-    const double center = (xx + 0.5) * scale;
-    int xmin = (int)(center - support + 0.5);
-    if (xmin < 0) xmin = 0;
-    int xmax = (int)(center + support + 0.5);
-    if (xmax > n_in) xmax = n_in;
-    int n = xmax - xmin;
-    if (n > ks) n = ks;
-    if (n < 0) n = 0;
-    double ww = 0.0;
-    for (int k = 0; k < n; ++k) {
-        const double v = bicubic((k + xmin - center + 0.5) * ss);
-        w[k] = v;
-        ww += v;
-    }
-    if (ww != 0.0)
-        for (int k = 0; k < n; ++k) w[k] /= ww;
-    *first = xmin; *count = n;
-}
-
-// float32 -> int as Python's int(): towards zero; what does not fit an int makes the RoI empty
-__device__ inline bool trunc_ok(float v, int *out) {
-    if (!(v > -5.0e8f && v < 5.0e8f)) return false;
-    *out = (int)v;
-    return true;
-}
 
 template <bool BITS> __device__ inline int tmp_col(int x) { return BITS ? x + (x >> 5) : x; }
 

@@ -109,22 +109,30 @@ def write_segm_results(writer, image_info, image_ids, out, category_of=None, inp
     The masks are at the NETWORK-INPUT resolution.  The reference resizes each mask once more to the original image size before it
     thresholds (:422); that resize is not done here, so an image with resize_scale != 1 raises ValueError -- unless the caller passes
     input_resolution=True and then gets box AND mask of such an image at the network-input resolution (the box NOT divided by
-    resize_scale, so the two agree) and rescales them himself."""
+    resize_scale, so the two agree) and rescales them himself.
+
+    A pass of Predictor(masks=True, rle=True, original_size=(Ho, Wo)) carries that second resize (infer.OriginalSizeResult): its lines
+    are the reference's for any resize_scale -- `bbox` from det_orig (the box divided by resize_scale in float32, :408), `segmentation`
+    the RLE of the mask resized to the original size and thresholded there with `>` (:422-423), 'size' = [origin_h, origin_w].
+    input_resolution=True has no meaning for such a pass (ValueError); an image beyond the device limits (orig_status) raises ValueError."""
     from scda_amd import infer
     info = _np(image_info)
     if info.ndim != 2 or info.shape[1] < 3 or len(image_ids) != info.shape[0]:
         raise ValueError("write_segm_results: image_info [B, >=3] and B image ids")
-    if not input_resolution:
+    original = isinstance(out, infer.OriginalSizeResult)
+    if original and input_resolution:
+        raise ValueError("write_segm_results: the pass carries original-size results; input_resolution=True does not apply to it")
+    if not input_resolution and not original:
         bad = [b for b in range(info.shape[0]) if float(info[b, 2]) != 1.0]
         if bad:
             raise ValueError("write_segm_results: images %s have resize_scale != 1; the masks are encoded at the network-input "
                              "resolution (pass input_resolution=True to get box and mask at that resolution)" % bad)
     segs, fallbacks = infer.segm_rows(out, with_fallbacks=True)
-    det, det_counts = _np(out[2]), _np(out[3])
+    det, det_counts = _np(out.det_orig if original else out[2]), _np(out[3])
     for b in range(info.shape[0]):
         d = det[b, :int(det_counts[b])]
         order = np.argsort(-d[:, 5], kind='stable')[:keep_num]
-        scale = 1.0 if input_resolution else float(info[b, 2])
+        scale = 1.0 if input_resolution or original else float(info[b, 2])
         for ix in order:
             box = (d[ix, 1:5] / np.float32(scale)).tolist()
             cls = int(d[ix, 6])
@@ -149,23 +157,38 @@ def coco_stats(loader, predictor, evaluator, device=None):
     the six gt_* entries: they are then built by a scda_amd.coco_gt.GroundTruth that is kept across the items -- for 'segm' the masks
     are rasterised on the device (scda_mask_frpoly_hip) into planes of the Predictor's shape, max_gts_per_image slots per image.  The
     annotations are rasterised AT THEIR OWN COORDINATES: as for every other ground-truth input, bringing polygons, boxes and areas to
-    the detections' coordinates when resize_scale != 1 is the caller's business."""
+    the detections' coordinates when resize_scale != 1 is the caller's business.
+
+    A Predictor with original_size=(Ho, Wo) (image_info rows (h, w, resize_scale, origin_h, origin_w)) puts the DETECTIONS at the
+    original image's coordinates instead: the evaluator is fed det_orig, mask_bits_orig, the areas of the original-size masks and
+    'sizes' = every image's (origin_h, origin_w) -- the item's 'sizes' if it has them, else image_info[:, 3:5] --, and the GroundTruth
+    of 'annotations' is built at the planes of mask_bits_orig.  COCO's own annotations then need no rescaling, for 'bbox' and 'segm'
+    alike.  The orig_status of every pass is kept on the device and read after the last one: ValueError, in place of stats that empty
+    masks would have entered silently, if any image was beyond the device limits (it names the image ids)."""
     segm = evaluator.iou_type == 'segm'
     if segm and not (predictor.masks and predictor.rle):
         raise ValueError("coco_stats: a 'segm' evaluator needs Predictor(masks=True, rle=True)")
     device = evaluator.device if device is None else device
     ground_truth = None
+    statuses = []
     with torch.no_grad():
         for item in loader:
             out = predictor(item['image'].to(device, non_blocking=True), item['image_info'])
+            original = getattr(predictor, 'original_size', None) is not None
+            if original:
+                statuses.append((item['image_ids'], out.orig_status.clone()))        # the Predictor's buffer is overwritten by the next pass
+            det, bits = (out.det_orig, out.mask_bits_orig) if original else (out[2], out[4] if segm else None)
+            sizes = item.get('sizes')
+            if original and sizes is None:
+                sizes = _np(item['image_info'])[:, 3:5].astype(np.int64)
             if 'annotations' in item:
                 from scda_amd import coco_gt, native
                 if segm:
-                    if ground_truth is None or (ground_truth.H, ground_truth.Wd) != tuple(out[4].shape[2:]):
-                        ground_truth = coco_gt.GroundTruth(device, evaluator.G, out[4].shape[2], out[4].shape[3])
-                    gt = ground_truth.load(item['annotations'], item['sizes'])
+                    if ground_truth is None or (ground_truth.H, ground_truth.Wd) != tuple(bits.shape[2:]):
+                        ground_truth = coco_gt.GroundTruth(device, evaluator.G, bits.shape[2], bits.shape[3])
+                    gt = ground_truth.load(item['annotations'], sizes if original else item['sizes'])
                 else:
-                    flat = coco_gt.flatten_annotations(item['annotations'], item['sizes'], evaluator.G)
+                    flat = coco_gt.flatten_annotations(item['annotations'], sizes if original else item['sizes'], evaluator.G)
                     gt = tuple(native.upload(flat[k], device) for k in ('gt_boxes', 'gt_areas', 'gt_iscrowd', 'gt_categories', 'gt_counts'))
                     gt += (None,)
             else:
@@ -173,9 +196,14 @@ def coco_stats(loader, predictor, evaluator, device=None):
                       item['gt_mask_bits'] if segm else None)
             kw = {}
             if segm:
-                kw = {'mask_bits': out[4], 'det_areas': out[5]['area'], 'gt_mask_bits': gt[5], 'sizes': item.get('sizes')}
-            evaluator.add(item['image_ids'], out[2], out[3], *gt[:5], **kw)
-    return evaluator.summarize()
+                kw = {'mask_bits': bits, 'det_areas': out[5]['area'], 'gt_mask_bits': gt[5], 'sizes': sizes}
+            evaluator.add(item['image_ids'], det, out[3], *gt[:5], **kw)
+    stats = evaluator.summarize()
+    flagged = [(int(i), int(v)) for ids, st in statuses for i, v in zip(_np(ids).reshape(-1), _np(st).reshape(-1)) if v]
+    if flagged:
+        raise ValueError("coco_stats: images %s (image id, orig_status) are beyond the limits of the original-size masks (see "
+                         "infer.Predictor); their masks are empty and the stats would be wrong" % flagged)
+    return stats
 
 
 def meta_ground_truth(val_meta_file, num_classes):

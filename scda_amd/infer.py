@@ -23,7 +23,15 @@ COCO results (opt-in on top, `Predictor(model, cfg, masks=True, rle=True)`): beh
 on the device at its image's (h, w) (scda_amd/csrc/mask_rle.hip: pycocotools' rleEncode / rleToString / rleArea / rleToBbox bit for bit),
 so what leaves the device is the result -- a few kilobytes per mask -- not the raster.  `segm_rows` is the call that waits and returns
 the `{'size', 'counts'}` dictionaries; a mask with more runs than the device capacity is encoded on the host from its own plane
-(scda_amd/mask_rle_host.py, the same rule) and counted."""
+(scda_amd/mask_rle_host.py, the same rule) and counted.
+
+Results at the original image size (opt-in on top, `Predictor(model, cfg, masks=True, original_size=(Ho, Wo))`, image_info rows
+(h, w, resize_scale, origin_h, origin_w)): behind the paste every detection's float plane is resized once more to its image's
+(origin_h, origin_w) as the reference's write_results_to_file does (tools/mask_rcnn_train_val.py:422, Pillow's resize bit for bit;
+scda_amd/csrc/mask_rescale.hip, one fused kernel that never writes the float plane to memory) and thresholded there with `>` (:423)
+into mask_bits_orig; det_orig holds the boxes divided by resize_scale (:408).  With rle=True the run-length results are those of
+mask_bits_orig.  The limits (original sizes above (Ho, Wo), a down-scale above native.mask_rescale_max_ratio() = 4) are flagged per
+image on the device; mask_rows and segm_rows raise for a flagged image."""
 import numpy as np
 import torch
 
@@ -42,6 +50,32 @@ def _sections(cfg):
     rpn = dict(shared, **cfg['test_rpn_proposal_cfg'])
     box = dict(shared, **cfg['test_predict_bbox_cfg'])
     return rpn, box
+
+
+class OriginalSizeResult(tuple):
+    """The output tuple of a Predictor(original_size=...) pass.  Entries 0..4 (and 5 with rle=True) stand where they stand without
+    original_size; the new entries follow them and also have names: .mask_bits_orig int32 [B, top_n, Ho, ceil(Wo/32)], .det_orig
+    float32 [B, top_n, 7], .orig_status int32 [B] (0 = fine, see include/scda_ops.h), and .rle (entry 5, the run-length results of
+    mask_bits_orig; None without rle=True)."""
+
+    def __new__(cls, entries, names):
+        self = super().__new__(cls, entries)
+        self._names = dict(names)
+        return self
+
+    def __getattr__(self, name):
+        names = self.__dict__.get('_names', {})
+        if name in names:
+            return None if names[name] is None else self[names[name]]
+        raise AttributeError(name)
+
+
+def _check_status(status, what):
+    flagged = [(b, int(v)) for b, v in enumerate(status.cpu().numpy().reshape(-1)) if v]
+    if flagged:
+        raise ValueError("%s: no original-size masks for images %s (image, status): 1 = the original size exceeds the Predictor's "
+                         "original_size capacity, 2 = an original size below 1, 4 = a down-scale above %d, 8 = a bad (h, w)"
+                         % (what, flagged, N.mask_rescale_max_ratio()))
 
 
 class Predictor:
@@ -66,6 +100,14 @@ class Predictor:
     carry the empty-mask code.  rle_capacity: runs kept per detection, default 4 * W (two segments per column on average over the whole
     width); a default, not a guarantee: segm_rows encodes an overflowing mask on the host.
 
+    original_size=(Ho, Wo) (with masks=True; image_info [B, >= 5] = (h, w, resize_scale, origin_h, origin_w)): the capacity of the
+    original-size planes.  The result becomes an OriginalSizeResult: today's entries where they are, then mask_bits_orig int32
+    [B, top_n, Ho, ceil(Wo/32)] -- bit = (the pasted float plane of the image's (h, w), resized by Pillow's rule to (origin_h, origin_w),
+    > mask_threshold), zero outside origin_h x origin_w --, det_orig float32 [B, top_n, 7] = the detections with their box divided by
+    resize_scale in float32, and orig_status int32 [B], non-zero for an image beyond the kernel's limits (its masks are empty).  With
+    rle=True entry 5 holds the run-length results of mask_bits_orig, `size` = (origin_h, origin_w), rle_capacity defaulting to 4 * Wo.
+    mask_bits (entry 4) stays the input-resolution plane with its `>=`.  One more fixed buffer, one more launch, no wait for the host.
+
     soft_nms={'method': 'linear' | 'gaussian' | 'hard', 'sigma': 0.5, 'Nt': 0.3, 'threshold': 0.001} (any subset; the reference's defaults
     fill the rest): the per-class lists go through cython_nms.soft_nms on the device (scda_amd/csrc/soft_nms.hip, bit for bit) in place
     of the hard NMS, and the per-image top_n ranks by the rescored scores -- the rows the eval forward gives with the same dict under
@@ -73,7 +115,7 @@ class Predictor:
     None and no key: hard NMS, the bytes as ever.  ValueError for an unknown method, a sigma <= 0 or a post_nms_top_n above the kernel's
     capacity of 2048 rows per list.  The RPN stage keeps its hard NMS."""
 
-    def __init__(self, model, cfg, masks=False, mask_threshold=0.5, rle=False, rle_capacity=None, soft_nms=None):
+    def __init__(self, model, cfg, masks=False, mask_threshold=0.5, rle=False, rle_capacity=None, soft_nms=None, original_size=None):
         if model.training:
             raise ValueError("Predictor: put the detector in eval mode first (model.eval())")
         self.masks, self.mask_threshold = bool(masks), float(mask_threshold)
@@ -82,6 +124,12 @@ class Predictor:
             raise ValueError("Predictor: rle=True encodes the instance masks; it needs masks=True")
         if self.rle_capacity is not None and self.rle_capacity < 1:
             raise ValueError("Predictor: rle_capacity must be >= 1")
+        self.original_size = None if original_size is None else (int(original_size[0]), int(original_size[1]))
+        if self.original_size is not None:
+            if not self.masks:
+                raise ValueError("Predictor: original_size resizes the instance masks; it needs masks=True")
+            if min(self.original_size) < 1:
+                raise ValueError("Predictor: original_size = (Ho, Wo) must be >= 1")
         if self.masks:
             if not getattr(model, 'with_mask', False):
                 raise ValueError("Predictor: masks=True needs a detector with the mask branch (cfg with_mask)")
@@ -129,6 +177,36 @@ class Predictor:
         self.mask_cls = torch.zeros(R, dtype=torch.int32, device=dev)
         self.mask_planes = None                                               # [R, h, w] once the head's output size is known
         self.mask_bits = torch.zeros(B, self.top_n, H, (W + 31) // 32, dtype=torch.int32, device=dev)
+
+    def _allocate_orig(self, B, dev):
+        Ho, Wo = self.original_size
+        R = B * self.top_n
+        self.mask_bits_orig = torch.zeros(B, self.top_n, Ho, (Wo + 31) // 32, dtype=torch.int32, device=dev)
+        self.det_orig = torch.zeros(B, self.top_n, 7, dtype=torch.float32, device=dev)
+        self.foot_rois = torch.zeros(R, 5, dtype=torch.float32, device=dev)
+        self.orig_status = torch.zeros(B, dtype=torch.int32, device=dev)
+
+    def _orig(self, info, B, H, W):
+        """behind _masks: every detection's pasted plane resized to its image's original size and thresholded there; the boxes divided
+        by resize_scale"""
+        Ho, Wo = self.original_size
+        N.mask_rescale(self.mask_rois, self.mask_planes, H, W, info, Ho, Wo, cls=self.mask_cls, packed=True,
+                       threshold=self.mask_threshold, out=self.mask_bits_orig.view(B * self.top_n, Ho, -1), foot_rois=self.foot_rois,
+                       status=self.orig_status)
+        self.det_orig.copy_(self.det)
+        self.det_orig[:, :, 1:5].div_(info[:, 2].view(B, 1, 1))
+
+    def _rle_orig(self, info, B):
+        """the run-length code of mask_bits_orig at (origin_h, origin_w); the footprints limit the columns read (outside its footprint
+        a plane is 0.0, which is not > a threshold >= 0)"""
+        Ho, Wo = self.original_size
+        N.mask_rle(self.mask_bits_orig.view(B * self.top_n, Ho, -1), image_info=info, info_column=3,
+                   rois=self.foot_rois if self.mask_threshold >= 0 else None, cap_runs=self.rle_cap, ws=self.rle_ws, out=self.rle_flat)
+        size = self.rle_out['size']
+        size.copy_(info[:, 3:5])
+        size[:, 0].clamp_(1, Ho)
+        size[:, 1].clamp_(1, 32 * ((Wo + 31) // 32))
+        return self.rle_out
 
     def _allocate_rle(self, B, H, W, dev):
         R, Wd = B * self.top_n, (W + 31) // 32
@@ -182,6 +260,8 @@ class Predictor:
         info = self._info(image_info, B, dev)
         if info.shape[0] != B or info.shape[1] < 2:
             raise ValueError("Predictor: image_info must be [B, >=2] (h, w, ...)")
+        if self.original_size is not None and info.shape[1] < 5:
+            raise ValueError("Predictor: original_size needs image_info [B, >=5] (h, w, resize_scale, origin_h, origin_w)")
         feat = model.feature_extractor(images)
         rpn_cls, rpn_loc = model.rpn(feat)
         prob = _objectness(rpn_cls).contiguous()
@@ -193,8 +273,10 @@ class Predictor:
             self._allocate(B, fh, fw, A4 // 4, C, dev)
             if self.masks:
                 self._allocate_masks(B, images.shape[2], images.shape[3], dev)
+            if self.original_size is not None:
+                self._allocate_orig(B, dev)
             if self.rle:
-                self._allocate_rle(B, images.shape[2], images.shape[3], dev)
+                self._allocate_rle(B, *(self.original_size or images.shape[2:]), dev)
             self.shape = shape
             self.graph = None
         N.rpn_proposals_batched(prob, loc, self.anchors64, info, int(rc['pre_nms_top_n']), float(rc['roi_min_size']),
@@ -209,7 +291,14 @@ class Predictor:
         self._out = (self.props.view(B, self.P, 6), self.counts, self.det, self.det_counts)
         if self.masks:
             self._out += (self._masks(feat, B, images.shape[2], images.shape[3]),)
-        if self.rle:
+        if self.original_size is not None:
+            self._orig(info, B, images.shape[2], images.shape[3])
+            if self.rle:
+                self._out += (self._rle_orig(info, B),)
+            n = len(self._out)
+            self._out = OriginalSizeResult(self._out + (self.mask_bits_orig, self.det_orig, self.orig_status),
+                                           {'mask_bits_orig': n, 'det_orig': n + 1, 'orig_status': n + 2, 'rle': 5 if self.rle else None})
+        elif self.rle:
             self._out += (self._rle(info, B, images.shape[2], images.shape[3]),)
         return self._out
 
@@ -237,24 +326,28 @@ class Predictor:
 _PREDICTORS = {}
 
 
-def predict(model, images, image_info, cfg, masks=False, mask_threshold=0.5, rle=False, rle_capacity=None, soft_nms=None):
+def predict(model, images, image_info, cfg, masks=False, mask_threshold=0.5, rle=False, rle_capacity=None, soft_nms=None,
+            original_size=None):
     """images [B,3,H,W] on the device, image_info [B,>=2] (host or device) -> device tensors
     (proposals [B,P,6] = (b, x1, y1, x2, y2, score), proposal_counts int32 [B], detections [B,top_n,7] =
     (b, x1, y1, x2, y2, score, class), detection_counts int32 [B]); rows past an image's count are padding.
     masks=True: a fifth tensor, mask_bits int32 [B,top_n,H,ceil(W/32)] (see Predictor); rle=True on top: a sixth element, the dict of
     run-length results (see Predictor, segm_rows).
     soft_nms: see Predictor (a dict; None = the cfg's own `soft_nms` key, if any).
-    One Predictor per (model, cfg, masks, mask_threshold, rle, rle_capacity, soft_nms) is kept and reused; its buffers are overwritten by
+    original_size=(Ho, Wo): see Predictor; the result is then an OriginalSizeResult (image_info [B,>=5]).
+    One Predictor per (model, cfg, masks, mask_threshold, rle, rle_capacity, soft_nms, original_size) is kept and reused; its buffers are overwritten by
     the next call."""
     key = (id(model), id(cfg)) if not masks else (id(model), id(cfg), True, float(mask_threshold))
     if rle:
         key += ('rle', rle_capacity)
     if soft_nms is not None:
         key += ('soft_nms', N.soft_nms_setting(soft_nms))
+    if original_size is not None:
+        key += ('original_size', int(original_size[0]), int(original_size[1]))
     p = _PREDICTORS.get(key)
     if p is None or p.model is not model:
         p = _PREDICTORS[key] = Predictor(model, cfg, masks=masks, mask_threshold=mask_threshold, rle=rle, rle_capacity=rle_capacity,
-                                         soft_nms=soft_nms)
+                                         soft_nms=soft_nms, original_size=original_size)
     return p(images, image_info)
 
 
@@ -267,10 +360,13 @@ def rows(proposals, proposal_counts, detections, detection_counts):
     return props, dets
 
 
-def mask_rows(mask_bits, detection_counts, width=None):
+def mask_rows(mask_bits, detection_counts, width=None, status=None):
     """mask_bits [B, top_n, H, ceil(W/32)] + detection_counts [B] -> a list of B boolean arrays [n_b, H, W]: each image's real
     detections in `rows`' order.  width: W when it is not a multiple of 32 (default: every stored column).  Like `rows`, this waits for
-    the device."""
+    the device.  status: the orig_status of a Predictor(original_size=...) pass when mask_bits is its mask_bits_orig (every image's rows
+    are then [n_b, Ho, Wo]: crop them to the image's own (origin_h, origin_w)); ValueError for a flagged image."""
+    if status is not None:
+        _check_status(status, "mask_rows")
     words = mask_bits.cpu().numpy().view(np.uint32)
     counts = detection_counts.cpu().numpy()
     B, _, H, Wd = words.shape
@@ -307,10 +403,17 @@ def segm_rows(out, with_fallbacks=False):
     at the network-input resolution, 'area' / 'bbox' its rleArea / rleToBbox.  A detection whose run count exceeded the device capacity
     is encoded here from its own plane of mask_bits by scda_amd.mask_rle_host (the same rule, the same bytes); their number is logged and,
     with with_fallbacks=True, returned as a second value.  This call waits for the device.  What crosses to the host: 28 bytes per
-    detection slot, 12 per image, each image's strings (its real detections x the longest of them) and one plane per fallback."""
+    detection slot, 12 per image, each image's strings (its real detections x the longest of them) and one plane per fallback.
+    The result of a pass with original_size (an OriginalSizeResult): the same at the ORIGINAL image size -- 'size' = [origin_h, origin_w],
+    the masks those of mask_bits_orig; ValueError for an image whose orig_status is set."""
     import logging
     from scda_amd import mask_rle_host
     det_counts, mask_bits, rle = out[3], out[4], out[5]
+    if isinstance(out, OriginalSizeResult):
+        if out.rle is None:
+            raise ValueError("segm_rows: the pass has no run-length results (Predictor(rle=True))")
+        _check_status(out.orig_status, "segm_rows")
+        mask_bits = out.mask_bits_orig
     dc = det_counts.cpu().numpy()
     n_runs, n_bytes, area = (rle[k].cpu().numpy() for k in ('n_runs', 'n_bytes', 'area'))
     bbox, size = rle['bbox'].cpu().numpy(), rle['size'].cpu().numpy()

@@ -513,6 +513,51 @@ def mask_paste(rois, planes, H, W, cls=None, packed=False, threshold=0.5, out=No
     return out
 
 
+def mask_rescale_max_ratio():
+    """the largest down-scale h / oh, w / ow of mask_rescale (a capacity of the kernel's LDS tables)"""
+    return int(lib().scda_mask_rescale_max_ratio())
+
+
+def mask_rescale(rois, planes, H, W, image_info, Ho, Wo, cls=None, packed=False, threshold=0.5, out=None, foot_rois=None, status=None):
+    """tools/mask_rcnn_train_val.py:422-423 on the device (include/scda_ops.h states the rule): rois [R, >=5], planes [R, h, w] as
+    mask_paste takes them at the padded (H, W); image_info float32 [B, >=5] on the device, rows (h, w, resize_scale, origin_h, origin_w),
+    R % B == 0 (detection r belongs to image r // (R // B)).  Each detection's pasted plane, cut to its image's (h, w), is resized to the
+    image's (origin_h, origin_w) as Pillow does and written into planes of (Ho, Wo): float32 [R, Ho, Wo], or with packed=True uint32
+    [R, Ho, ceil(Wo/32)] of (value > threshold), stored as int32.  -> (out, foot_rois float32 [R, 5] = (b, fx1, fy1, fx2, fy2), the
+    rectangle outside which nothing was computed -- mask_rle's `rois` hint when threshold >= 0 --, status int32 [B], non-zero for an image
+    beyond the limits, whose masks are empty).  Every element of the three is written.  No wait for the host."""
+    _req(rois, "rois"); _req(planes, "planes"); _req(image_info, "image_info")
+    if rois.dim() != 2 or rois.shape[1] < 5 or planes.dim() != 3 or planes.shape[0] != rois.shape[0]:
+        raise ValueError("mask_rescale: rois must be [R, >=5] and planes [R, h, w]")
+    R, h, w = planes.shape
+    if h > MASK_PLANE_MAX or w > MASK_PLANE_MAX:
+        raise ValueError("mask_rescale: planes of at most %d x %d" % (MASK_PLANE_MAX, MASK_PLANE_MAX))
+    if image_info.dim() != 2 or image_info.shape[1] < 5 or image_info.shape[0] < 1 or R % image_info.shape[0]:
+        raise ValueError("mask_rescale: image_info must be [B, >=5] (h, w, resize_scale, origin_h, origin_w) with R a multiple of B")
+    B = image_info.shape[0]
+    if cls is not None:
+        _req(cls, "cls", torch.int32)
+        if cls.numel() != R:
+            raise ValueError("mask_rescale: cls must be [R]")
+    H, W, Ho, Wo = int(H), int(W), int(Ho), int(Wo)
+    if min(H, W, Ho, Wo) < 1:
+        raise ValueError("mask_rescale: H, W, Ho, Wo must be >= 1")
+    shape, dtype = ((R, Ho, (Wo + 31) // 32), torch.int32) if packed else ((R, Ho, Wo), torch.float32)
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device=rois.device)
+    if foot_rois is None:
+        foot_rois = torch.empty(R, 5, dtype=torch.float32, device=rois.device)
+    if status is None:
+        status = torch.empty(B, dtype=torch.int32, device=rois.device)
+    _req(out, "out", dtype); _req(foot_rois, "foot_rois"); _req(status, "status", torch.int32)
+    if tuple(out.shape) != shape or tuple(foot_rois.shape) != (R, 5) or status.numel() != B:
+        raise ValueError("mask_rescale: out must be %s, foot_rois [R, 5] and status [B]" % (shape,))
+    _check(lib().scda_mask_rescale_hip(_p(rois), rois.shape[1], _p(cls), _p(planes), R, h, w, H, W, _p(image_info), image_info.shape[1],
+                                       R // B, Ho, Wo, 1 if packed else 0, threshold, _p(out), _p(foot_rois), _p(status), _stream()),
+           "scda_mask_rescale_hip")
+    return out, foot_rois, status
+
+
 # ------------------------------------------------- COCO run-length results ---
 def mask_rle_max_chars(h, w):
     """characters one count of an h x w plane can take in the 6-bit string: ceil((bitlength(h * w) + 1) / 5)"""
@@ -531,14 +576,16 @@ def _words(t, name):
     return t
 
 
-def mask_rle(bits, size=None, image_info=None, rois=None, cap_runs=None, ws=None, out=None):
+def mask_rle(bits, size=None, image_info=None, rois=None, cap_runs=None, ws=None, out=None, info_column=0):
     """maskApi.c's rleEncode / rleToString / rleArea / rleToBbox of packed masks on the device (include/scda_ops.h states the rules).
     bits int32 [R, H, Wd] words as mask_paste(packed=True) writes them.  The image of each mask: size=(h, w) for all, or image_info
     float32 [B, >=2] on the device with R % B == 0 (mask r belongs to image r // (R // B)); default: the whole plane.  rois [R, >=5]: the
     rows given to mask_paste, a hint that limits the columns read (planes pasted with threshold > 0 only).  cap_runs: runs kept per mask
     (default 4 * 32 * Wd).  -> dict of device tensors n_runs int32 [R] (the true count; > cap_runs = overflow), counts int32 [R, cap_runs]
     (uint32 values), n_bytes int32 [R], chars uint8 [R, cap_runs * mask_rle_max_chars(H, 32 Wd)], area int32 [R], bbox int32 [R, 4]
-    (x, y, w, h).  ws / out: buffers of an earlier call of the same shape, reused.  No wait for the host."""
+    (x, y, w, h).  ws / out: buffers of an earlier call of the same shape, reused.  No wait for the host.
+    info_column: the column of image_info where (h, w) stand -- 3 reads the (origin_h, origin_w) of the loader's rows, for planes that
+    mask_rescale wrote."""
     _words(bits, "bits")
     R, H, Wd = bits.shape
     cap_runs = 4 * 32 * Wd if cap_runs is None else int(cap_runs)
@@ -550,8 +597,9 @@ def mask_rle(bits, size=None, image_info=None, rois=None, cap_runs=None, ws=None
         if size is not None:
             raise ValueError("mask_rle: give size or image_info, not both")
         _req(image_info, "image_info")
-        if image_info.dim() != 2 or image_info.shape[1] < 2 or R % image_info.shape[0]:
-            raise ValueError("mask_rle: image_info must be [B, >=2] with R a multiple of B")
+        info_column = int(info_column)
+        if image_info.dim() != 2 or info_column < 0 or image_info.shape[1] < info_column + 2 or R % image_info.shape[0]:
+            raise ValueError("mask_rle: image_info must be [B, >= info_column + 2] with R a multiple of B")
         per, stride = R // image_info.shape[0], image_info.shape[1]
     else:
         h_all, w_all = (H, 32 * Wd) if size is None else (int(size[0]), int(size[1]))
@@ -582,7 +630,8 @@ def mask_rle(bits, size=None, image_info=None, rois=None, cap_runs=None, ws=None
         _req(out[k], k, dt)
         if out[k].numel() != R * (shape[1] if len(shape) > 1 else 1):
             raise ValueError("mask_rle: out[%r] must hold %s" % (k, shape))
-    _check(lib().scda_mask_rle_hip(_p(bits), R, H, Wd, _p(image_info), stride, per, h_all, w_all, _p(rois), rstride, cap_runs, cap_bytes,
+    info_ptr = None if image_info is None else image_info.data_ptr() + 4 * info_column
+    _check(lib().scda_mask_rle_hip(_p(bits), R, H, Wd, info_ptr, stride, per, h_all, w_all, _p(rois), rstride, cap_runs, cap_bytes,
                                    _p(ws), _p(out['n_runs']), _p(out['counts']), _p(out['n_bytes']), _p(out['chars']), _p(out['area']),
                                    _p(out['bbox']), _stream()), "scda_mask_rle_hip")
     return out
