@@ -477,7 +477,10 @@ int scda_mask_frpoly_hip(const double *xy, int V, const int *poly_first, const i
  * scda_coco_summarize_hip: _summarizeDets.  spec i32 [n_stats, 4] (device) = (ap, t, a, m): the mean over the entries > -1 of
  *   precision[t, :, :, a, m] (ap != 0) or recall[t, :, a, m]; t = -1 every threshold, t = -2 none (the reference's np.where found no
  *   such threshold); -1 when no entry qualifies -> stats f64 [n_stats].  The sum is taken in a fixed order (deterministic); it differs
- *   from numpy's pairwise mean by at most 2 N 2^-53 for N averaged entries in [0, 1]. */
+ *   from numpy's pairwise mean by at most 2 N 2^-53 for N averaged entries in [0, 1].  The 12 specs are the host's
+ *   (scda_amd.coco_eval.stat_specs) and select maxDets as the reference does: maxDets[2] for stats 1..5 and 8..11, maxDets[0] and
+ *   maxDets[1] for stats 6 and 7, and for stat 0 the entry EQUAL to 100 (_summarize's default), none -- t = -2, the stat is -1 -- when
+ *   the list holds no 100. */
 int scda_coco_det_rows_hip(const float *detections, const int *detection_counts, int B, int top_n, const uint32_t *mask_area_or_null,
                            int K, double *dt_xywh, double *dt_area, float *score, int *cat, void *stream);
 int scda_coco_box_iou_hip(const double *dt, const int *dt_counts, const double *gt, const int *gt_counts, const unsigned char *iscrowd,

@@ -32,14 +32,20 @@ def default_params():
 
 def stat_specs(iou_thrs, max_dets):
     """_summarizeDets' 12 selections as (ap, t, a, m); t = -1: every threshold, -2: the list does not hold the value (np.where finds
-    nothing and the reference reports -1); area ranges in the order all, small, medium, large"""
+    nothing and the reference reports -1); area ranges in the order all, small, medium, large.  max_dets is the sorted list.  The
+    selection is the reference's: stats 1..5 and 8..11 take maxDets[2], stats 6 and 7 maxDets[0] and maxDets[1], and stat 0 is
+    _summarize(1), whose default maxDets = 100 selects the entry EQUAL to 100 -- without one nothing is selected and the stat is -1
+    (t = -2).  With fewer than three entries the reference cannot answer (IndexError on maxDets[2] / maxDets[1]): those selections then
+    fall back to the last entry, as they always did here; stat 0 follows the reference there too."""
     def at(v):
         w = np.where(v == np.asarray(iou_thrs))[0]
         return int(w[0]) if len(w) else -2
+    max_dets = [int(m) for m in max_dets]
     last = len(max_dets) - 1
-    m0, m1 = 0, min(1, last)
-    return np.array([(1, -1, 0, last), (1, at(.5), 0, last), (1, at(.75), 0, last), (1, -1, 1, last), (1, -1, 2, last), (1, -1, 3, last),
-                     (0, -1, 0, m0), (0, -1, 0, m1), (0, -1, 0, last), (0, -1, 1, last), (0, -1, 2, last), (0, -1, 3, last)], dtype=np.int32)
+    m0, m1, m2 = 0, min(1, last), min(2, last)
+    t100, m100 = (-1, max_dets.index(100)) if 100 in max_dets else (-2, 0)
+    return np.array([(1, t100, 0, m100), (1, at(.5), 0, m2), (1, at(.75), 0, m2), (1, -1, 1, m2), (1, -1, 2, m2), (1, -1, 3, m2),
+                     (0, -1, 0, m0), (0, -1, 0, m1), (0, -1, 0, m2), (0, -1, 1, m2), (0, -1, 2, m2), (0, -1, 3, m2)], dtype=np.int32)
 
 
 class CocoEvaluator:

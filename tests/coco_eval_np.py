@@ -148,13 +148,19 @@ def accumulate(images, per_image, K, iou_thrs, rec_thrs, area_rng, max_dets):
 
 def stat_specs(iou_thrs, max_dets):
     """_summarizeDets' 12 selections as (ap, t, a, m): t = -1 every threshold, -2 a threshold the list does not hold (the reference's
-    np.where(iouThr == p.iouThrs) then selects nothing); area ranges in the order all, small, medium, large"""
+    np.where(iouThr == p.iouThrs) then selects nothing); area ranges in the order all, small, medium, large.  The maxDets entry is the
+    reference's (cocoeval.py:459-472): maxDets[2] for stats 1..5 and 8..11, maxDets[0] / maxDets[1] for stats 6 / 7, and for stat 0
+    (_summarize(1), default maxDets = 100) the entry EQUAL to 100 -- nothing, hence -1, when the list holds no 100.  Fewer than three
+    entries, where the reference raises IndexError: the missing entries fall back to the last one"""
     def at(v):
         w = np.where(v == np.asarray(iou_thrs))[0]
         return int(w[0]) if len(w) else -2
+    max_dets = [int(m) for m in max_dets]
     last = len(max_dets) - 1
-    return np.array([(1, -1, 0, last), (1, at(.5), 0, last), (1, at(.75), 0, last), (1, -1, 1, last), (1, -1, 2, last), (1, -1, 3, last),
-                     (0, -1, 0, 0), (0, -1, 0, 1), (0, -1, 0, last), (0, -1, 1, last), (0, -1, 2, last), (0, -1, 3, last)],
+    m1, m2 = min(1, last), min(2, last)
+    t100, m100 = (-1, max_dets.index(100)) if 100 in max_dets else (-2, 0)
+    return np.array([(1, t100, 0, m100), (1, at(.5), 0, m2), (1, at(.75), 0, m2), (1, -1, 1, m2), (1, -1, 2, m2), (1, -1, 3, m2),
+                     (0, -1, 0, 0), (0, -1, 0, m1), (0, -1, 0, m2), (0, -1, 1, m2), (0, -1, 2, m2), (0, -1, 3, m2)],
                     dtype=np.int32)
 
 

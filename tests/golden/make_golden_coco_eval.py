@@ -16,7 +16,10 @@ Neither the C file nor the library nor any reference program text is kept.  The 
 The sets (see main for the asserted coverage):
   rules        hand-made images, K = 4, image ids given in descending order
   random_bbox  40 images of 512 x 1024, K = 5, detections jittered from the GTs at three noise scales, 15 % crowds
-  random_segm  12 images, planes 70 x 96 (Wd = 3), ellipses and blobs, K = 3, area ranges scaled to 8^2 / 24^2"""
+  random_segm  12 images, planes 70 x 96 (Wd = 3), ellipses and blobs, K = 3, area ranges scaled to 8^2 / 24^2
+  waves, capacity, limits, limits3, sortkeys, prrounds: the structural edge sets built by tests/eval_edge_cases.py, with their own
+               s_iou_thrs, s_rec_thrs, s_max_dets and without s_iou
+An array of the older sets must come out byte-identical; main asserts it before it writes."""
 import ctypes
 import importlib
 import io
@@ -32,6 +35,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 import coco_eval_np as cnp  # noqa: E402  (parameters and the corner -> xywh rule only)
+import eval_edge_cases as edges  # noqa: E402  (the seeded builders of the edge sets)
 
 
 class RLE(ctypes.Structure):
@@ -114,8 +118,9 @@ def pack(mask, H, Wd):
     return np.packbits(full, axis=-1, bitorder='little').view(np.uint32).reshape(H, Wd)
 
 
-def run_reference(coco_mod, eval_mod, standin, images, K, area_rng, iou_type, size):
-    """images: dicts with image_id, dt_corners, dt_score, dt_cat, gt_xywh, gt_area, gt_iscrowd, gt_cat (+ dt_mask, gt_mask for segm)"""
+def run_reference(coco_mod, eval_mod, standin, images, K, area_rng, iou_type, size, params=None):
+    """images: dicts with image_id, dt_corners, dt_score, dt_cat, gt_xywh, gt_area, gt_iscrowd, gt_cat (+ dt_mask, gt_mask for segm);
+    params: iou_thrs, rec_thrs and max_dets other than Params' defaults (the edge sets)"""
     h, w = size
     gt_anns, dt_anns = [], []
     for im in images:
@@ -142,6 +147,10 @@ def run_reference(coco_mod, eval_mod, standin, images, K, area_rng, iou_type, si
         dt = gt.loadRes(dt_anns)
         E = eval_mod.COCOeval(gt, dt, iou_type)
         E.params.areaRng = [list(map(float, r)) for r in area_rng]
+        E.params.areaRngLbl = ['all', 'small', 'medium', 'large'] + ['range%d' % a for a in range(4, len(area_rng))]
+        if params is not None:
+            E.params.iouThrs, E.params.recThrs = np.asarray(params['iou_thrs']), np.asarray(params['rec_thrs'])
+            E.params.maxDets = list(params['max_dets'])
         E.evaluate()
         E.accumulate()
         E.summarize()
@@ -372,7 +381,23 @@ def main():
         sc = np.concatenate([im['dt_score'] for im in ims])
         assert len(np.unique(sc)) < len(sc)
         print("random_segm stats", np.round(r['stats'], 4), "gts", sum(len(im['gt_cat']) for im in ims), "dets", len(sc))
+        # ---- the edge sets of tests/eval_edge_cases.py (test_eval_edges_rules.py asserts the boundary each one crosses); their IoU
+        # matrices are not stored: cnp.bb_iou recomputes them
+        for name in edges.COCO_SETS:
+            case = edges.coco_case(name)
+            p = case['params']
+            assert name + '_K' not in out and list(p['max_dets']) == sorted(p['max_dets'])
+            r = run_reference(coco_mod, eval_mod, standin, case['images'], case['K'], p['area_rng'], 'bbox', (1024, 1024), p)
+            r.pop('iou')
+            store(out, name, case['images'], case['K'], p['area_rng'], dict(r))
+            out[name + '_iou_thrs'], out[name + '_rec_thrs'] = np.asarray(p['iou_thrs'], np.float64), np.asarray(p['rec_thrs'], np.float64)
+            out[name + '_max_dets'] = np.asarray(p['max_dets'], dtype=np.int32)
+            print(name, "stats", np.round(r['stats'], 4), "gts", len(out[name + '_gt_cats']), "dets", len(out[name + '_dt_cats']))
     path = os.path.join(HERE, "coco_eval_ref.npz")
+    if os.path.exists(path):                                                  # regeneration must not move an array of the older sets
+        with np.load(path) as old:
+            for k in (k for k in old.files if not any(k.startswith(s + '_') for s in edges.COCO_SETS)):
+                assert out[k].dtype == old[k].dtype and out[k].shape == old[k].shape and out[k].tobytes() == old[k].tobytes(), k
     np.savez_compressed(path, **out)
     print("wrote", path, os.path.getsize(path), "bytes")
 

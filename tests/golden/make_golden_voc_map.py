@@ -18,7 +18,9 @@ are added, cut by the per-image counts):
             s_recalled, s_rpn_gts (compute_recall summed); s_tp u8 [n], s_match i32 [n] (tests/voc_map_np.py, after its ap / max_recall
             were asserted bit-equal to the reference's and its true positives per class equal to the is_det sums)
 The sets (see main for the asserted coverage): rules (hand-made, C = 5), nan (a class with rows and no ground truth), random (40 images
-of 512 x 1024 at scale 0.5, C = 9)."""
+of 512 x 1024 at scale 0.5, C = 9); cap, keep100, match, recall: the structural edge sets built by tests/eval_edge_cases.py, each with
+s_keep_num (and, for the recall, s_recalled_each i32 [I, 2]).  An array of the older sets must come out byte-identical; main
+asserts it before it writes."""
 import importlib.util
 import os
 import sys
@@ -29,6 +31,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, HERE)
 import voc_map_np as vnp  # noqa: E402
+import eval_edge_cases as edges  # noqa: E402  (the seeded builders of the edge sets)
 
 
 class _NumpyEmptyMax:
@@ -196,9 +199,9 @@ def random_set():
     return images, [(im['name'], im['gt']) for im in images], C
 
 
-def record(name, images, records, C, cal, compute_recall):
+def record(name, images, records, C, cal, compute_recall, keep_num=100, recall_each=False):
     """run the reference and the restatement over one set -> the arrays of the fixture"""
-    rows = [r for im in images for r in text_rows(im, C)]
+    rows = [r for im in images for r in text_rows(im, C, keep_num)]
     meta = meta_lines(records)
     gts = cal.parse_gts(meta, C)
     results = cal.parse_res(rows)
@@ -228,7 +231,7 @@ def record(name, images, records, C, cal, compute_recall):
         is_det.append(flags)
     sum_gt = np.asarray(gts['num']).astype(np.int64)
     # ---- the restatement must give the reference's numbers before its per-row flags are recorded
-    mine = vnp.evaluate(images, C, sum_gt=sum_gt)
+    mine = vnp.evaluate(images, C, sum_gt=sum_gt, keep_num=keep_num)
     assert np.array_equal(mine['ap'], ap, equal_nan=True) and np.array_equal(mine['max_recall'], max_recall, equal_nan=True), (name, mine['ap'], ap)
     assert mine['ap'].tobytes() == np.asarray(ap).tobytes() or np.isnan(ap).any()
     for c in range(1, C):
@@ -243,13 +246,17 @@ def record(name, images, records, C, cal, compute_recall):
            'match': np.concatenate([e['match'] for e in mine['per_image']]).astype(np.int32)}
     if 'props' in images[0]:
         rc = ng = 0
+        each = []
         for im in images:
             r, g = compute_recall(im['props'][:, 1:5], im['rgts'])
             rc, ng = rc + int(r), ng + int(g)
+            each.append((int(r), int(g)))
         assert (mine['rpn_recalled'], mine['rpn_gts']) == (rc, ng), (mine['rpn_recalled'], rc)
         out.update({'props': np.concatenate([im['props'] for im in images]), 'prop_counts': np.asarray([len(im['props']) for im in images], dtype=np.int32),
                     'rgts': np.concatenate([im['rgts'] for im in images]), 'rgt_counts': np.asarray([len(im['rgts']) for im in images], dtype=np.int32),
                     'recalled': np.int64(rc), 'rpn_gts': np.int64(ng)})
+        if recall_each:                                                       # compute_recall's answer image by image too
+            out['recalled_each'] = np.asarray(each, dtype=np.int32).reshape(-1, 2)
     return {name + '_' + k: v for k, v in out.items()}, mine
 
 
@@ -305,7 +312,19 @@ def main():
     assert 2048 < len(out['random_res']) and 0 < out['random_recalled'] < out['random_rpn_gts']
     sc = out['random_det'][:, 5]
     assert len(np.unique(sc)) < len(sc) and out['random_prop_counts'][5] == 0
+    # ---- the edge sets of tests/eval_edge_cases.py (test_eval_edges_rules.py asserts the boundary each one crosses)
+    for name in edges.MAP_SETS:
+        images, records, C = edges.map_case(name)
+        assert name + '_C' not in out
+        z, mine = record(name, images, records, C, cal, compute_recall, keep_num=edges.MAP_CAPS[name]['keep_num'], recall_each=True)
+        z[name + '_keep_num'] = np.int64(edges.MAP_CAPS[name]['keep_num'])
+        out.update(z)
+        print(name, "rows", len(z[name + '_res']), "mAP", z[name + '_mAP'])
     path = os.path.join(HERE, "voc_map_ref.npz")
+    if os.path.exists(path):                                                  # regeneration must not move an array of the older sets
+        with np.load(path) as old:
+            for k in (k for k in old.files if not any(k.startswith(s + '_') for s in edges.MAP_SETS)):
+                assert out[k].dtype == old[k].dtype and out[k].shape == old[k].shape and out[k].tobytes() == old[k].tobytes(), k
     np.savez_compressed(path, **out)
     print("wrote", path, os.path.getsize(path), "bytes;", "random mAP", out['random_mAP'], "rules ap", out['rules_ap'])
 
