@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from scda_amd import native as N
+from scda_amd.eval_base import StreamingEvaluator
 
 MAX_PER_IMAGE = 1024
 
@@ -48,7 +49,7 @@ def stat_specs(iou_thrs, max_dets):
                      (0, -1, 0, m0), (0, -1, 0, m1), (0, -1, 0, m2), (0, -1, 1, m2), (0, -1, 2, m2), (0, -1, 3, m2)], dtype=np.int32)
 
 
-class CocoEvaluator:
+class CocoEvaluator(StreamingEvaluator):
     """Fixed-capacity streaming COCOeval.  add() stores each image's rows (score, category, rank and the matched / ignored masks of every
     detection slot) on the device; accumulate() sorts and scans all rows collected so far; summarize() returns the 12 stats.
 
@@ -74,12 +75,8 @@ class CocoEvaluator:
             raise ValueError("CocoEvaluator: 1 <= num_categories <= 255, max_images >= 1, 1 <= max_dets / max_gts per image <= 1024")
         if not (1 <= self.T <= 16 and 4 <= self.A <= 8 and 1 <= self.M <= 4 and 1 <= self.R <= 128):
             raise ValueError("CocoEvaluator: at most 16 IoU thresholds, 4..8 area ranges, 4 maxDets, 128 recall thresholds")
-        dev = torch.device('cuda') if device is None else torch.device(device)
-        if dev.type != 'cuda':
-            raise N.ScdaNativeError("CocoEvaluator needs a HIP device; there is no CPU path")
-        if dev.index is None:                   # 'cuda' -> the current device, so that tensors on it compare equal
-            dev = torch.device('cuda', torch.cuda.current_device())
-        self.device = dev
+        self._init_stream(device)
+        dev = self.device
         I, D, K, A, T = self.I, self.D, self.K, self.A, self.T
         z = lambda *s, dtype: torch.zeros(*s, dtype=dtype, device=dev)        # noqa: E731
         self.d_iou_thrs, self.d_rec_thrs = N.upload(self.iou_thrs, dev), N.upload(self.rec_thrs, dev)
@@ -101,21 +98,12 @@ class CocoEvaluator:
         self.ws = torch.empty(max(N.coco_accumulate_workspace_bytes(I, D, K, A), 16), dtype=torch.uint8, device=dev)
         self._iou = None                        # [B, G, D] of the largest batch seen
         self._miou = None                       # 'segm': scda_mask_iou_hip's workspace and raw intersections
-        self.n_images = 0
-        self._accumulated = -1
 
     def reset(self):
         self.npig.zero_(); self.seen.zero_()
         if self.debug_match is not None:
             self.debug_match.fill_(-1)
-        self.n_images, self._accumulated = 0, -1
-
-    def _dev(self, t, name, dtype, shape):
-        if not torch.is_tensor(t) or t.device != self.device or t.dtype != dtype or not t.is_contiguous():
-            t = torch.as_tensor(np.asarray(t.cpu() if torch.is_tensor(t) else t)).to(dtype).to(self.device).contiguous()   # (allocates)
-        if tuple(t.shape) != tuple(shape):
-            raise ValueError("CocoEvaluator.add: %s must be %s, got %s" % (name, tuple(shape), tuple(t.shape)))
-        return t
+        self._reset_stream()
 
     @torch.no_grad()
     def add(self, image_ids, detections, detection_counts, gt_boxes, gt_areas, gt_iscrowd, gt_categories, gt_counts,
@@ -128,10 +116,9 @@ class CocoEvaluator:
         (h, w) or B of them on the HOST -- the image inside the planes (default: the whole plane).  Capacity violations raise before
         anything is launched; the counts themselves live on the device and are clamped there."""
         B = int(detections.shape[0])
-        if detections.dim() != 3 or detections.shape[1] != self.D or detections.shape[2] != 7:
+        if len(detections.shape) != 3 or detections.shape[1] != self.D or detections.shape[2] != 7:
             raise ValueError("CocoEvaluator.add: detections must be [B, %d, 7] (max_dets_per_image = %d)" % (self.D, self.D))
-        if self.n_images + B > self.I:
-            raise ValueError("CocoEvaluator.add: %d images exceed max_images = %d" % (self.n_images + B, self.I))
+        s0, s1 = self._slots(B)
         if tuple(gt_boxes.shape[1:]) != (self.G, 4):
             raise ValueError("CocoEvaluator.add: gt_boxes must be [B, %d, 4] (max_gts_per_image = %d)" % (self.G, self.G))
         det = self._dev(detections, "detections", torch.float32, (B, self.D, 7))
@@ -159,7 +146,6 @@ class CocoEvaluator:
                 raise ValueError("CocoEvaluator.add: sizes must be one or B (h, w) inside the %d x %d planes" % (H, 32 * Wd))
         if self._iou is None or self._iou.shape[0] < B:
             self._iou = torch.zeros(B, self.G, self.D, dtype=torch.float64, device=self.device)       # (first batch of this size only)
-        s0, s1 = self.n_images, self.n_images + B
         self.image_ids[s0:s1].copy_(ids)
         N.coco_det_rows(det, dc, self.K, self.xywh[s0:s1], self.area[s0:s1], self.score[s0:s1], self.cat[s0:s1],
                         mask_area=det_areas if segm else None)
@@ -185,8 +171,7 @@ class CocoEvaluator:
     def accumulate(self):
         """-> {'precision' [T, R, K, A, M], 'recall' [T, K, A, M], 'scores' [T, R, K, A, M]}: float64 device tensors of the evaluator
         (overwritten by the next call), COCOeval.eval's arrays over every image added so far"""
-        if self.n_images == 0:
-            raise ValueError("CocoEvaluator.accumulate: no image was added")
+        self._require_images()
         N.coco_accumulate(self.image_ids, self.n_images, self.cat, self.rank, self.score, self.bits, self.npig, self.seen,
                           self.d_rec_thrs, self.d_max_dets, self.max_dets[-1], self.T, self.ws, self.precision, self.recall, self.scores)
         self._accumulated = self.n_images
@@ -195,7 +180,6 @@ class CocoEvaluator:
     @torch.no_grad()
     def summarize(self):
         """-> numpy float64 [12]: COCOeval.stats (AP, AP50, AP75, APs, APm, APl, AR1, AR10, AR100, ARs, ARm, ARl); the one host wait"""
-        if self._accumulated != self.n_images:
-            self.accumulate()
+        self._ensure_accumulated()
         N.coco_summarize(self.precision, self.recall, (self.T, self.R, self.K, self.A, self.M), self.d_specs, self.stats)
         return self.stats.cpu().numpy()

@@ -8,10 +8,11 @@
 //   box_iou_kernel      per (image, gt, dt) pair: bbIou
 //   match_kernel        per (image, category): ranks, the GT orders, evaluateImg's greedy matching, one lane per (area range, threshold)
 //   sort_*_kernel       the stable LSD radix sort of radix_sort.h, 8 bits per pass, over the keys of SortKey
-//   gather_kernel       the rows in sorted order (score, rank, match bits), category segments
+//   gather_kernel       the rows in sorted order (score, rank, match bits); segment_bounds_kernel: the category segments
 //   pr_kernel           per (category, area range, maxDets): tp / fp scans, precision envelope, the recall thresholds
 //   stats_kernel        the 12 numbers of _summarizeDets
-#include "common.h"
+// The block scan, the envelope step, wave_compact, segment_bounds_kernel and the workspace allocator are those of eval_prims.h.
+#include "eval_prims.h"
 #include "radix_sort.h"
 
 namespace {
@@ -59,19 +60,6 @@ __global__ __launch_bounds__(256) void box_iou_kernel(const double *__restrict__
         o = in / u;
     }
     iou[(size_t)b * D * G + i] = o;
-}
-
-// stable compaction by one wave: the indices i < n with pred(i), in order, appended to list at *cnt (wave-uniform)
-template <class Pred>
-__device__ inline int wave_compact(int n, int lane, uint16_t *list, int cnt, Pred pred) {
-    for (int base = 0; base < n; base += 64) {
-        const int i = base + lane;
-        const bool f = i < n && pred(i);
-        const unsigned long long m = __ballot(f);
-        if (f) list[cnt + __popcll(m & ((1ull << lane) - 1ull))] = (uint16_t)i;
-        cnt += __popcll(m);
-    }
-    return cnt;
 }
 
 struct MatchArgs {
@@ -218,8 +206,6 @@ __global__ __launch_bounds__(kMatchThreads) void match_kernel(MatchArgs p) {
 }
 
 // ------------------------------------------------------------------------------------------------ the sort keys (radix_sort.h)
-using radix::sort_pass;
-
 struct SortKey {
     int kind;                                   // 0: image id, 1: score (descending), 2: category (0 = the row takes no part)
     int shift;
@@ -266,14 +252,11 @@ __global__ __launch_bounds__(256) void gather_kernel(const uint32_t *__restrict_
     for (int a = 0; a < A; ++a) s_bits[(size_t)a * n + i] = part ? bits[(size_t)e * A + a] : 0u;
 }
 
-// seg [2, K + 1]: first row and row count of every category's segment (zeroed before)
-__global__ __launch_bounds__(256) void segment_kernel(const int *__restrict__ s_cat, int n, int K, int *__restrict__ seg) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int c = s_cat[i];
-    if (i == 0 || s_cat[i - 1] != c) seg[c] = i;
-    if (i == n - 1 || s_cat[i + 1] != c) seg[K + 1 + c] = i + 1;         // the END here; the count is taken by the reader
-}
+// segment_bounds_kernel's key: the category of a sorted row.  seg [2, K + 1]
+struct CatKey {
+    const int *s_cat;
+    __device__ int operator()(int i) const { return s_cat[i]; }
+};
 
 __global__ __launch_bounds__(256) void fill_kernel(double *p, size_t n, double v) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[i] = v;
@@ -289,11 +272,19 @@ struct PrArgs {
     double *precision, *recall, *scores;
 };
 
+// pr_kernel's counts, scanned as one value behind one pair of barriers: tp in the low, fp in the high 32 bits of c; in = the rows with
+// rank < maxDets.  12 bytes, so that the four wave partials take the LDS the two arrays took
+struct __attribute__((packed, aligned(4))) PrCount {
+    unsigned long long c;
+    uint32_t in;
+    __device__ PrCount operator+(const PrCount &o) const { return {c + o.c, in + o.in}; }
+};
+__device__ inline PrCount lanes_up(PrCount v, int d) { return {__shfl_up(v.c, d, 64), __shfl_up(v.in, d, 64)}; }
+
 // grid (K * A * M), 256 threads.  The rows are visited from the LAST to the first, so the scans in thread order are suffix scans
 __global__ __launch_bounds__(256) void pr_kernel(PrArgs p) {
     __shared__ int cs[kMaxRec];
-    __shared__ unsigned long long w_cnt[4];
-    __shared__ uint32_t w_in[4];
+    __shared__ PrCount w_cnt[4];
     __shared__ double w_max[4];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int m = blockIdx.x % p.M, a = (blockIdx.x / p.M) % p.A, k = blockIdx.x / (p.M * p.A);
@@ -333,15 +324,14 @@ __global__ __launch_bounds__(256) void pr_kernel(PrArgs p) {
 #pragma unroll
         for (int s = 32; s > 0; s >>= 1) { tot += __shfl_xor(tot, s, 64); nin += __shfl_xor(nin, s, 64); }
         __syncthreads();                        // cs is written; the previous round's use of w_* is over
-        if (lane == 0) { w_cnt[wv] = tot; w_in[wv] = nin; }
+        if (lane == 0) w_cnt[wv] = {tot, nin};
         __syncthreads();
-        tot = w_cnt[0] + w_cnt[1] + w_cnt[2] + w_cnt[3];
-        nin = w_in[0] + w_in[1] + w_in[2] + w_in[3];
+        tot = w_cnt[0].c + w_cnt[1].c + w_cnt[2].c + w_cnt[3].c;
+        nin = w_cnt[0].in + w_cnt[1].in + w_cnt[2].in + w_cnt[3].in;
         const uint32_t tp_tot = (uint32_t)tot, fp_tot = (uint32_t)(tot >> 32);
         if (tid == 0) p.recall[o_rec] = nin ? (double)tp_tot / (double)np : 0.0;
         // ---- from the last row backwards
-        unsigned long long c_cnt = 0;
-        uint32_t c_in = 0;
+        PrCount c_cnt = {0ull, 0u};
         double c_max = -1.0;
         for (int base = 0; base < n; base += 256) {
             const int j = base + tid, i = n - 1 - j;
@@ -353,44 +343,16 @@ __global__ __launch_bounds__(256) void pr_kernel(PrArgs p) {
                 tp = in && !ig && mt;
                 fp = in && !ig && !mt;
             }
-            unsigned long long sc = tp ? 1ull : (fp ? (1ull << 32) : 0ull);
-            uint32_t si = in ? 1u : 0u;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const unsigned long long oc = __shfl_up(sc, d, 64);
-                const uint32_t oi = __shfl_up(si, d, 64);
-                if (lane >= d) { sc += oc; si += oi; }
-            }
-            __syncthreads();
-            if (lane == 63) { w_cnt[wv] = sc; w_in[wv] = si; }
-            __syncthreads();
-            unsigned long long all_c = 0; uint32_t all_i = 0;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                if (q < wv) { sc += w_cnt[q]; si += w_in[q]; }
-                all_c += w_cnt[q]; all_i += w_in[q];
-            }
-            sc += c_cnt; si += c_in;            // inclusive suffix counts of the row
+            const PrCount one = {tp ? 1ull : (fp ? (1ull << 32) : 0ull), in ? 1u : 0u};
+            PrCount all_c;
+            const PrCount s = block_scan256(one, w_cnt, Add(), c_cnt, &all_c) + c_cnt;      // inclusive suffix counts of the row
+            const unsigned long long sc = s.c;
+            const uint32_t si = s.in;
             // the row's inclusive prefix counts = totals - the suffix behind it
             const uint32_t tpc = tp_tot - ((uint32_t)sc - (tp ? 1u : 0u)), fpc = fp_tot - ((uint32_t)(sc >> 32) - (fp ? 1u : 0u));
             const uint32_t inc = nin - (si - (in ? 1u : 0u));
             const double tpd = (double)tpc, fpd = (double)fpc;
-            double pm = in ? tpd / (fpd + tpd + 2.220446049250313e-16) : -1.0;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const double o = __shfl_up(pm, d, 64);
-                if (lane >= d) pm = fmax(pm, o);
-            }
-            __syncthreads();
-            if (lane == 63) w_max[wv] = pm;
-            __syncthreads();
-            double all_m = c_max;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                if (q < wv) pm = fmax(pm, w_max[q]);
-                all_m = fmax(all_m, w_max[q]);
-            }
-            pm = fmax(pm, c_max);
+            const double pm = envelope_step(in ? tpd / (fpd + tpd + 2.220446049250313e-16) : -1.0, w_max, &c_max);
             if (in) {
                 // searchsorted(rc, thr, 'left'): the c-th true positive for the thresholds whose count is c, the first row for count 0
                 for (int pass = 0; pass < 2; ++pass) {
@@ -405,7 +367,7 @@ __global__ __launch_bounds__(256) void pr_kernel(PrArgs p) {
                     }
                 }
             }
-            c_cnt += all_c; c_in += all_i; c_max = all_m;
+            c_cnt = all_c;
         }
         __syncthreads();
     }
@@ -438,35 +400,29 @@ __global__ __launch_bounds__(256) void stats_kernel(const double *__restrict__ p
     }
 }
 
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-struct AccLayout { size_t perm_a, perm_b, img_a, img_b, hist, seg, s_score, s_rank, s_cat, s_bits, total; int tiles; };
+struct AccLayout { size_t perm_a, perm_b, img_a, img_b, hist, seg, s_score, s_rank, s_cat, s_bits, total; };
 
 AccLayout acc_layout(int n_images, int D, int K, int A) {
     AccLayout l;
-    const size_t n = (size_t)n_images * D;
-    l.tiles = (int)((n + radix::kSortTile - 1) / radix::kSortTile);
-    size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t at = o; o += align256(bytes); return at; };
-    l.perm_a = take(n * 4); l.perm_b = take(n * 4);
-    l.img_a = take((size_t)n_images * 4); l.img_b = take((size_t)n_images * 4);
-    l.hist = take((size_t)l.tiles * 256 * 4);
-    l.seg = take((size_t)2 * (K + 1) * 4);
-    l.s_score = take(n * 4); l.s_rank = take(n * 4); l.s_cat = take(n * 4);
-    l.s_bits = take(n * 4 * A);
-    l.total = o;
+    const size_t n = (size_t)n_images * D, tiles = (n + radix::kSortTile - 1) / radix::kSortTile;
+    Bump ws;
+    l.perm_a = ws.take(n * 4); l.perm_b = ws.take(n * 4);
+    l.img_a = ws.take((size_t)n_images * 4); l.img_b = ws.take((size_t)n_images * 4);
+    l.hist = ws.take(tiles * 256 * 4);
+    l.seg = ws.take((size_t)2 * (K + 1) * 4);
+    l.s_score = ws.take(n * 4); l.s_rank = ws.take(n * 4); l.s_cat = ws.take(n * 4);
+    l.s_bits = ws.take(n * 4 * A);
+    l.total = ws.total();
     return l;
 }
 
 }  // namespace
 
-#define CE_CHECK(cond, name) if (!(cond)) { set_error(name ": bad arguments"); return SCDA_EINVAL; }
-
 SCDA_API int scda_coco_det_rows_hip(const float *detections, const int *detection_counts, int B, int top_n,
                                     const uint32_t *mask_area_or_null, int K, double *dt_xywh, double *dt_area, float *score, int *cat,
                                     void *stream) {
-    CE_CHECK(detections && detection_counts && dt_xywh && dt_area && score && cat && B > 0 && top_n > 0 && K > 0 &&
-             (long long)B * top_n < 0x7fffffffLL, "scda_coco_det_rows_hip")
+    SCDA_CHECK_ARGS(detections && detection_counts && dt_xywh && dt_area && score && cat && B > 0 && top_n > 0 && K > 0 &&
+                    (long long)B * top_n < 0x7fffffffLL, "scda_coco_det_rows_hip")
     hipLaunchKernelGGL(det_rows_kernel, dim3(ew_grid((long long)B * top_n)), dim3(256), 0, as_stream(stream), detections,
                        detection_counts, B, top_n, mask_area_or_null, K, dt_xywh, dt_area, score, cat);
     return launch_status("det_rows_kernel");
@@ -474,8 +430,8 @@ SCDA_API int scda_coco_det_rows_hip(const float *detections, const int *detectio
 
 SCDA_API int scda_coco_box_iou_hip(const double *dt, const int *dt_counts, const double *gt, const int *gt_counts,
                                    const unsigned char *iscrowd, int B, int D, int G, double *iou, void *stream) {
-    CE_CHECK(dt && dt_counts && gt && gt_counts && iscrowd && iou && B > 0 && B <= 65535 && D > 0 && G > 0 && D <= kMaxPer &&
-             G <= kMaxPer, "scda_coco_box_iou_hip")
+    SCDA_CHECK_ARGS(dt && dt_counts && gt && gt_counts && iscrowd && iou && B > 0 && B <= 65535 && D > 0 && G > 0 && D <= kMaxPer &&
+                    G <= kMaxPer, "scda_coco_box_iou_hip")
     hipLaunchKernelGGL(box_iou_kernel, dim3(cdiv((long long)D * G, 256), B), dim3(256), 0, as_stream(stream), dt, dt_counts, gt,
                        gt_counts, iscrowd, D, G, iou);
     return launch_status("box_iou_kernel");
@@ -485,10 +441,10 @@ SCDA_API int scda_coco_match_hip(const double *iou, int B, int D, int G, const i
                                  const double *dt_area, const int *gt_counts, const int *gt_cat, const double *gt_area,
                                  const unsigned char *gt_iscrowd, int K, const double *iou_thrs, int T, const double *area_rng, int A,
                                  int max_det, int *rank, uint32_t *bits, int *npig, int *seen, int *dbg_match_or_null, void *stream) {
-    CE_CHECK(iou && dt_counts && dt_cat && score && dt_area && gt_counts && gt_cat && gt_area && gt_iscrowd && iou_thrs && area_rng &&
-             rank && bits && npig && seen, "scda_coco_match_hip")
-    CE_CHECK(B > 0 && B <= 65535 && D > 0 && D <= kMaxPer && G > 0 && G <= kMaxPer && K > 0 && K <= 65535 && T > 0 && T <= kMaxT &&
-             A > 0 && A <= kMaxA && max_det > 0, "scda_coco_match_hip (limits: D, G <= 1024, T <= 16, A <= 8)")
+    SCDA_CHECK_ARGS(iou && dt_counts && dt_cat && score && dt_area && gt_counts && gt_cat && gt_area && gt_iscrowd && iou_thrs &&
+                    area_rng && rank && bits && npig && seen, "scda_coco_match_hip")
+    SCDA_CHECK_ARGS(B > 0 && B <= 65535 && D > 0 && D <= kMaxPer && G > 0 && G <= kMaxPer && K > 0 && K <= 65535 && T > 0 && T <= kMaxT &&
+                    A > 0 && A <= kMaxA && max_det > 0, "scda_coco_match_hip (limits: D, G <= 1024, T <= 16, A <= 8)")
     const MatchArgs args = {iou, dt_counts, dt_cat, score, dt_area, gt_counts, gt_cat, gt_area, gt_iscrowd, iou_thrs, area_rng,
                             D, G, K, T, A, max_det, rank, bits, npig, seen, dbg_match_or_null};
     hipLaunchKernelGGL(match_kernel, dim3(K, B), dim3(kMatchThreads), 0, as_stream(stream), args);
@@ -504,11 +460,11 @@ SCDA_API int scda_coco_accumulate_hip(const int *image_ids, int n_images, int D,
                                       const uint32_t *bits, const int *npig, const int *seen, int K, int T, int A,
                                       const double *rec_thrs, int R, const int *max_dets, int M, int max_det_last, void *ws,
                                       double *precision, double *recall, double *scores, void *stream) {
-    CE_CHECK(image_ids && cat && rank && score && bits && npig && seen && rec_thrs && max_dets && ws && precision && recall && scores &&
-             (uintptr_t)ws % 16 == 0, "scda_coco_accumulate_hip")
-    CE_CHECK(n_images > 0 && D > 0 && D <= kMaxPer && (long long)n_images * D < 0x7fffffffLL && K > 0 && K <= 255 && T > 0 &&
-             T <= kMaxT && A > 0 && A <= kMaxA && R > 0 && R <= kMaxRec && M > 0 && M <= kMaxM && max_det_last > 0,
-             "scda_coco_accumulate_hip (limits: K <= 255, T <= 16, A <= 8, M <= 4, R <= 128)")
+    SCDA_CHECK_ARGS(image_ids && cat && rank && score && bits && npig && seen && rec_thrs && max_dets && ws && precision && recall &&
+                    scores && (uintptr_t)ws % 16 == 0, "scda_coco_accumulate_hip")
+    SCDA_CHECK_ARGS(n_images > 0 && D > 0 && D <= kMaxPer && (long long)n_images * D < 0x7fffffffLL && K > 0 && K <= 255 && T > 0 &&
+                    T <= kMaxT && A > 0 && A <= kMaxA && R > 0 && R <= kMaxRec && M > 0 && M <= kMaxM && max_det_last > 0,
+                    "scda_coco_accumulate_hip (limits: K <= 255, T <= 16, A <= 8, M <= 4, R <= 128)")
     const AccLayout l = acc_layout(n_images, D, K, A);
     char *w8 = (char *)ws;
     uint32_t *perm_a = (uint32_t *)(w8 + l.perm_a), *perm_b = (uint32_t *)(w8 + l.perm_b);
@@ -522,24 +478,16 @@ SCDA_API int scda_coco_accumulate_hip(const int *image_ids, int n_images, int D,
     // their rank order, so stable passes over the score (descending) and the category finish the reference's order
     SortKey key = {0, 0, image_ids, score, cat, rank, max_det_last};
     hipLaunchKernelGGL(iota_kernel, dim3(cdiv(n_images, 256)), dim3(256), 0, st, img_a, n_images);
-    for (int pass = 0; pass < 4; ++pass) {
-        key.shift = 8 * pass;
-        sort_pass(img_a, img_b, n_images, key, hist, st);
-        uint32_t *t = img_a; img_a = img_b; img_b = t;
-    }
+    img_a = radix::sort_u32(img_a, img_b, n_images, key, hist, st);
     hipLaunchKernelGGL(rows_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, (const uint32_t *)img_a, D, perm_a, n);
     key.kind = 1;
-    for (int pass = 0; pass < 4; ++pass) {
-        key.shift = 8 * pass;
-        sort_pass(perm_a, perm_b, n, key, hist, st);
-        uint32_t *t = perm_a; perm_a = perm_b; perm_b = t;
-    }
+    perm_a = radix::sort_u32(perm_a, perm_b, n, key, hist, st);
     key.kind = 2; key.shift = 0;
-    sort_pass(perm_a, perm_b, n, key, hist, st);
+    radix::sort_pass(perm_a, perm_b, n, key, hist, st);
     hipLaunchKernelGGL(gather_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, (const uint32_t *)perm_b, n, score, cat, rank, bits, A,
                        max_det_last, s_score, s_rank, s_cat, s_bits);
     if (hipMemsetAsync(seg, 0, (size_t)2 * (K + 1) * 4, st) != hipSuccess) return launch_status("scda_coco_accumulate_hip (memset)");
-    hipLaunchKernelGGL(segment_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, (const int *)s_cat, n, K, seg);
+    hipLaunchKernelGGL(segment_bounds_kernel<CatKey>, dim3(cdiv(n, 256)), dim3(256), 0, st, n, CatKey{s_cat}, K + 1, seg);
     const size_t np_ = (size_t)T * R * K * A * M, nr_ = (size_t)T * K * A * M;
     hipLaunchKernelGGL(fill_kernel, dim3(ew_grid((long long)np_)), dim3(256), 0, st, precision, np_, -1.0);
     hipLaunchKernelGGL(fill_kernel, dim3(ew_grid((long long)np_)), dim3(256), 0, st, scores, np_, -1.0);
@@ -551,8 +499,8 @@ SCDA_API int scda_coco_accumulate_hip(const int *image_ids, int n_images, int D,
 
 SCDA_API int scda_coco_summarize_hip(const double *precision, const double *recall, int T, int R, int K, int A, int M, const int *spec,
                                      int n_stats, double *stats, void *stream) {
-    CE_CHECK(precision && recall && spec && stats && T > 0 && R > 0 && K > 0 && A > 0 && M > 0 && n_stats > 0 && n_stats <= 64,
-             "scda_coco_summarize_hip")
+    SCDA_CHECK_ARGS(precision && recall && spec && stats && T > 0 && R > 0 && K > 0 && A > 0 && M > 0 && n_stats > 0 && n_stats <= 64,
+                    "scda_coco_summarize_hip")
     hipLaunchKernelGGL(stats_kernel, dim3(n_stats), dim3(256), 0, as_stream(stream), precision, recall, T, R, K, A, M, spec, stats);
     return launch_status("stats_kernel");
 }

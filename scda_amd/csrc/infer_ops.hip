@@ -13,7 +13,7 @@
 // include/scda_ops.h: the RPN's exp of the float32 size deltas is the correctly rounded float32 exp here, numpy's own SIMD routine there.
 #include <math.h>
 
-#include "common.h"
+#include "eval_prims.h"
 
 namespace scda {
 
@@ -316,8 +316,6 @@ struct BoxWs {
 
 using namespace scda;
 
-#define INFER_CHECK(cond, name) if (!(cond)) { set_error(name ": bad arguments"); return SCDA_EINVAL; }
-
 SCDA_API size_t scda_rpn_topk_workspace_bytes(int B, int KA, int top_n) {
     const int n = topk_n(KA, top_n);
     return n > kSortCap ? (size_t)B * n * sizeof(unsigned long long) : 0;
@@ -325,9 +323,9 @@ SCDA_API size_t scda_rpn_topk_workspace_bytes(int B, int KA, int top_n) {
 
 SCDA_API int scda_rpn_topk_hip(const float *prob, int B, int A, int fh, int fw, int top_n, int *order, void *ws, void *stream) {
     const long long KA = (long long)A * fh * fw;
-    INFER_CHECK(prob && order && B > 0 && A > 0 && fh > 0 && fw > 0 && KA < 0x7fffffffLL, "scda_rpn_topk_hip")
+    SCDA_CHECK_ARGS(prob && order && B > 0 && A > 0 && fh > 0 && fw > 0 && KA < 0x7fffffffLL, "scda_rpn_topk_hip")
     const int n = topk_n((int)KA, top_n);
-    INFER_CHECK(n <= kSortCap || ws, "scda_rpn_topk_hip")
+    SCDA_CHECK_ARGS(n <= kSortCap || ws, "scda_rpn_topk_hip")
     hipLaunchKernelGGL(rpn_topk_kernel, dim3(B), dim3(kSortThreads), 0, as_stream(stream), prob, A, fh * fw, n,
                        (unsigned long long *)ws, order);
     return launch_status("rpn_topk_kernel");
@@ -336,8 +334,8 @@ SCDA_API int scda_rpn_topk_hip(const float *prob, int B, int A, int fh, int fw, 
 SCDA_API int scda_rpn_decode_batched_hip(const int *order, int n, const double *anchors64, const float *loc, const float *prob, int B,
                                          int A, int fh, int fw, const float *image_info, int info_stride, double min_size,
                                          float *props5, unsigned char *ok, void *stream) {
-    INFER_CHECK(order && anchors64 && loc && prob && image_info && props5 && ok && n > 0 && B > 0 && B <= 65535 && A > 0 && fh > 0 &&
-                fw > 0 && info_stride >= 2, "scda_rpn_decode_batched_hip")
+    SCDA_CHECK_ARGS(order && anchors64 && loc && prob && image_info && props5 && ok && n > 0 && B > 0 && B <= 65535 && A > 0 && fh > 0 &&
+                    fw > 0 && info_stride >= 2, "scda_rpn_decode_batched_hip")
     hipLaunchKernelGGL(rpn_decode_kernel, dim3(cdiv(n, 256), B), dim3(256), 0, as_stream(stream), order, n, anchors64, loc, prob, A,
                        fh * fw, image_info, info_stride, min_size, props5, ok);
     return launch_status("rpn_decode_kernel");
@@ -351,8 +349,8 @@ SCDA_API size_t scda_rpn_proposals_workspace_bytes(int B, int A, int fh, int fw,
 SCDA_API int scda_rpn_proposals_hip(const float *prob, const float *loc, const double *anchors64, int B, int A, int fh, int fw,
                                     const float *image_info, int info_stride, int pre_nms_top_n, double min_size, float nms_thresh,
                                     int post_nms_top_n, void *ws, float *rois5, float *props6, int *counts, void *stream) {
-    INFER_CHECK(prob && loc && anchors64 && image_info && ws && rois5 && props6 && counts && B > 0 && B <= 65535 && A > 0 && fh > 0 &&
-                fw > 0 && (long long)A * fh * fw < 0x7fffffffLL && info_stride >= 2 && post_nms_top_n > 0, "scda_rpn_proposals_hip")
+    SCDA_CHECK_ARGS(prob && loc && anchors64 && image_info && ws && rois5 && props6 && counts && B > 0 && B <= 65535 && A > 0 && fh > 0 &&
+                    fw > 0 && (long long)A * fh * fw < 0x7fffffffLL && info_stride >= 2 && post_nms_top_n > 0, "scda_rpn_proposals_hip")
     const int KA = A * fh * fw, n = topk_n(KA, pre_nms_top_n), P = post_nms_top_n;
     RpnWs w(ws, B, KA, n);
     hipStream_t st = as_stream(stream);

@@ -7,9 +7,10 @@
 //   map_rows_kernel     per image: the keep_num best live rows (rank under the stable score sort), clip, divide, truncate   (R1)
 //   map_match_kernel    per (class, image), one wave: detections in kept order, lanes over the ground truths, first-maximum argmax   (R2)
 //   map_recall_kernel   per image: one wave per ground-truth row over the live proposals                                   (R4)
-//   map_perm_kernel     the rows in (image, kept order); then radix_sort.h by score (descending) and by class
+//   map_perm_kernel     the rows in (image, kept order); then radix_sort.h by score (descending) and by class, segment_bounds_kernel
 //   map_pr_kernel       per class: cumulative tp, precision envelope, the AP sum left to right by one lane                  (R3)
-#include "common.h"
+// The block scan, the envelope step, wave_compact, segment_bounds_kernel and the workspace allocator are those of eval_prims.h.
+#include "eval_prims.h"
 #include "radix_sort.h"
 
 namespace {
@@ -77,14 +78,7 @@ __global__ __launch_bounds__(64) void map_match_kernel(MatchArgs p) {
     const int *gt = p.gt + (size_t)b * p.G * 5;
     const int *cls = p.cls + (size_t)b * p.D, *rank = p.rank + (size_t)b * p.D, *kept = p.kept + (size_t)b * p.D;
     // ---- the class's ground truths in meta order; its kept detections in kept order
-    int Gc = 0;
-    for (int base = 0; base < ng; base += 64) {
-        const int i = base + lane;
-        const bool f = i < ng && gt[i * 5 + 4] == c;
-        const unsigned long long m = __ballot(f);
-        if (f) s_gl[Gc + __popcll(m & ((1ull << lane) - 1ull))] = (uint16_t)i;
-        Gc += __popcll(m);
-    }
+    const int Gc = wave_compact(ng, lane, s_gl, 0, [&](int i) { return gt[i * 5 + 4] == c; });
     if (lane == 0 && Gc) atomicAdd(p.gt_num + c, Gc);
     for (int i = lane; i < p.D; i += 64) s_byrank[i] = 0xffffu;
     for (int i = lane; i < kMaxPer / 32; i += 64) s_claim[i] = 0u;
@@ -94,15 +88,8 @@ __global__ __launch_bounds__(64) void map_match_kernel(MatchArgs p) {
         if (r >= 0 && r < p.D) s_byrank[r] = (uint16_t)d;
     }
     __syncthreads();
-    int Dc = 0;
-    for (int base = 0; base < p.D; base += 64) {
-        const int i = base + lane;
-        const int d = i < p.D ? s_byrank[i] : 0xffff;
-        const bool f = d != 0xffff && kept[d] != 0 && cls[d] == c;
-        const unsigned long long m = __ballot(f);
-        if (f) s_dl[Dc + __popcll(m & ((1ull << lane) - 1ull))] = (uint16_t)d;
-        Dc += __popcll(m);
-    }
+    auto mine = [&](int i) { const int d = s_byrank[i]; return d != 0xffff && kept[d] != 0 && cls[d] == c; };
+    const int Dc = wave_compact(p.D, lane, s_dl, 0, mine, [&](int i) { return s_byrank[i]; });
     __syncthreads();
     // ---- calIoU and the claim, one detection after the other
     for (int k = 0; k < Dc; ++k) {
@@ -205,16 +192,12 @@ struct MapKey {
     }
 };
 
-// seg [2, kMaxClasses]: first row and END of every class's segment of the sorted rows (zeroed before)
-__global__ __launch_bounds__(256) void map_segment_kernel(const uint32_t *__restrict__ perm, int n, const int *__restrict__ cls,
-                                                          const int *__restrict__ kept, int *__restrict__ seg) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    auto key = [&](int j) { const uint32_t e = perm[j]; return kept[e] ? cls[e] : 0; };
-    const int c = key(i);
-    if (i == 0 || key(i - 1) != c) seg[c] = i;
-    if (i == n - 1 || key(i + 1) != c) seg[kMaxClasses + c] = i + 1;
-}
+// segment_bounds_kernel's key: the class of a sorted row (0 = not kept).  seg [2, kMaxClasses]
+struct ClassKey {
+    const uint32_t *perm;
+    const int *cls, *kept;
+    __device__ int operator()(int i) const { const uint32_t e = perm[i]; return kept[e] ? cls[e] : 0; }
+};
 
 struct PrArgs {
     const uint32_t *perm;
@@ -229,7 +212,7 @@ struct PrArgs {
 __global__ __launch_bounds__(256) void map_pr_kernel(PrArgs p) {
     __shared__ uint32_t wave_sums[4];
     __shared__ double w_max[4];
-    const int c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int c = blockIdx.x, tid = threadIdx.x;
     const int start = c ? p.seg[c] : 0, end = c ? p.seg[kMaxClasses + c] : 0;
     const int n = end > start ? end - start : 0;
     if (n == 0) {
@@ -246,9 +229,9 @@ __global__ __launch_bounds__(256) void map_pr_kernel(PrArgs p) {
         const int v = base + tid;
         const uint32_t f = v < n ? (uint32_t)p.tp[perm[v]] : 0u;
         uint32_t all;
-        const uint32_t ex = radix::block_excl_scan256(f, wave_sums, &all);
-        if (v < n) tpc[v] = (int)(carry + ex + f);
-        carry += all;
+        const uint32_t inc = block_scan256(f, wave_sums, Add(), carry, &all);
+        if (v < n) tpc[v] = (int)(carry + inc);
+        carry = all;
         __syncthreads();
     }
     __syncthreads();
@@ -263,23 +246,8 @@ __global__ __launch_bounds__(256) void map_pr_kernel(PrArgs p) {
             rec = t / sg;
             prev = v > 0 ? (double)tpc[v - 1] / sg : 0.0;
         }
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const double o = __shfl_up(pm, d, 64);
-            if (lane >= d) pm = fmax(pm, o);
-        }
-        __syncthreads();
-        if (lane == 63) w_max[wv] = pm;
-        __syncthreads();
-        double all_m = c_max;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            if (q < wv) pm = fmax(pm, w_max[q]);
-            all_m = fmax(all_m, w_max[q]);
-        }
-        pm = fmax(pm, c_max);
+        pm = envelope_step(pm, w_max, &c_max);
         if (j < n) term[v] = v == 0 ? rec * pm : (rec - prev) * pm;
-        c_max = all_m;
     }
     __syncthreads();
     // ---- the sum left to right, np.max(rec) (a NaN stays)
@@ -296,36 +264,30 @@ __global__ __launch_bounds__(256) void map_pr_kernel(PrArgs p) {
     }
 }
 
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 struct AccLayout { size_t perm_a, perm_b, hist, seg, tpc, term, total; };
 
 AccLayout acc_layout(int n_images, int D) {
     AccLayout l;
-    const size_t n = (size_t)n_images * D;
-    const size_t tiles = (n + radix::kSortTile - 1) / radix::kSortTile;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t at = o; o += align256(bytes); return at; };
-    l.perm_a = take(n * 4); l.perm_b = take(n * 4);
-    l.hist = take(tiles * 256 * 4);
-    l.seg = take((size_t)2 * kMaxClasses * 4);
-    l.tpc = take(n * 4);
-    l.term = take(n * 8);
-    l.total = o;
+    const size_t n = (size_t)n_images * D, tiles = (n + radix::kSortTile - 1) / radix::kSortTile;
+    Bump ws;
+    l.perm_a = ws.take(n * 4); l.perm_b = ws.take(n * 4);
+    l.hist = ws.take(tiles * 256 * 4);
+    l.seg = ws.take((size_t)2 * kMaxClasses * 4);
+    l.tpc = ws.take(n * 4);
+    l.term = ws.take(n * 8);
+    l.total = ws.total();
     return l;
 }
 
 }  // namespace
 
-#define ME_CHECK(cond, name) if (!(cond)) { set_error(name ": bad arguments"); return SCDA_EINVAL; }
-
 SCDA_API int scda_map_rows_hip(const float *detections, const int *detection_counts, int B, int D, const float *image_info, int info_w,
                                int scale_column, int num_classes, int keep_num, int *box, float *score, int *cls, int *rank, int *kept,
                                int *tp, int *dbg_match_or_null, int G, int *dbg_claimed_or_null, void *stream) {
-    ME_CHECK(detections && detection_counts && image_info && box && score && cls && rank && kept && tp, "scda_map_rows_hip")
-    ME_CHECK(B > 0 && B <= 65535 && D > 0 && D <= kMaxPer && info_w >= 2 && scale_column >= 0 && scale_column < info_w &&
-             num_classes >= 2 && num_classes <= kMaxClasses && keep_num > 0 && keep_num <= D && G > 0 && G <= kMaxPer,
-             "scda_map_rows_hip (limits: D, G <= 1024, 2 <= num_classes <= 256, 1 <= keep_num <= D)")
+    SCDA_CHECK_ARGS(detections && detection_counts && image_info && box && score && cls && rank && kept && tp, "scda_map_rows_hip")
+    SCDA_CHECK_ARGS(B > 0 && B <= 65535 && D > 0 && D <= kMaxPer && info_w >= 2 && scale_column >= 0 && scale_column < info_w &&
+                    num_classes >= 2 && num_classes <= kMaxClasses && keep_num > 0 && keep_num <= D && G > 0 && G <= kMaxPer,
+                    "scda_map_rows_hip (limits: D, G <= 1024, 2 <= num_classes <= 256, 1 <= keep_num <= D)")
     hipLaunchKernelGGL(map_rows_kernel, dim3(B), dim3(256), 0, as_stream(stream), detections, detection_counts, D, image_info, info_w,
                        scale_column, num_classes, keep_num, box, score, cls, rank, kept, tp, dbg_match_or_null, G, dbg_claimed_or_null);
     return launch_status("map_rows_kernel");
@@ -334,9 +296,9 @@ SCDA_API int scda_map_rows_hip(const float *detections, const int *detection_cou
 SCDA_API int scda_map_match_hip(const int *box, const int *cls, const int *rank, const int *kept, int B, int D, const int *gt_boxes,
                                 const int *gt_counts, int G, int num_classes, double iou_thr, int *tp, int *gt_num,
                                 int *dbg_match_or_null, int *dbg_claimed_or_null, void *stream) {
-    ME_CHECK(box && cls && rank && kept && gt_boxes && gt_counts && tp && gt_num, "scda_map_match_hip")
-    ME_CHECK(B > 0 && B <= 65535 && D > 0 && D <= kMaxPer && G > 0 && G <= kMaxPer && num_classes >= 2 && num_classes <= kMaxClasses,
-             "scda_map_match_hip (limits: D, G <= 1024, 2 <= num_classes <= 256)")
+    SCDA_CHECK_ARGS(box && cls && rank && kept && gt_boxes && gt_counts && tp && gt_num, "scda_map_match_hip")
+    SCDA_CHECK_ARGS(B > 0 && B <= 65535 && D > 0 && D <= kMaxPer && G > 0 && G <= kMaxPer && num_classes >= 2 && num_classes <= kMaxClasses,
+                    "scda_map_match_hip (limits: D, G <= 1024, 2 <= num_classes <= 256)")
     const MatchArgs args = {box, cls, rank, kept, gt_boxes, gt_counts, D, G, iou_thr, tp, gt_num, dbg_match_or_null, dbg_claimed_or_null};
     hipLaunchKernelGGL(map_match_kernel, dim3(num_classes - 1, B), dim3(64), 0, as_stream(stream), args);
     return launch_status("map_match_kernel");
@@ -344,9 +306,9 @@ SCDA_API int scda_map_match_hip(const int *box, const int *cls, const int *rank,
 
 SCDA_API int scda_map_recall_hip(const float *proposals, const int *proposal_counts, int B, int P, int prop_w, const float *gts,
                                  const int *gt_counts, int Gr, int gt_w, int *counters, void *stream) {
-    ME_CHECK(proposals && proposal_counts && gts && gt_counts && counters, "scda_map_recall_hip")
-    ME_CHECK(B > 0 && B <= 65535 && P > 0 && prop_w >= 5 && Gr > 0 && gt_w >= 4 && (long long)B * P * prop_w < 0x7fffffffLL &&
-             (long long)B * Gr * gt_w < 0x7fffffffLL, "scda_map_recall_hip (proposal rows >= 5 wide, ground-truth rows >= 4 wide)")
+    SCDA_CHECK_ARGS(proposals && proposal_counts && gts && gt_counts && counters, "scda_map_recall_hip")
+    SCDA_CHECK_ARGS(B > 0 && B <= 65535 && P > 0 && prop_w >= 5 && Gr > 0 && gt_w >= 4 && (long long)B * P * prop_w < 0x7fffffffLL &&
+                    (long long)B * Gr * gt_w < 0x7fffffffLL, "scda_map_recall_hip (proposal rows >= 5 wide, ground-truth rows >= 4 wide)")
     hipLaunchKernelGGL(map_recall_kernel, dim3(B), dim3(256), 0, as_stream(stream), proposals, proposal_counts, P, prop_w, gts, gt_counts,
                        Gr, gt_w, counters);
     return launch_status("map_recall_kernel");
@@ -360,10 +322,10 @@ SCDA_API size_t scda_map_accumulate_workspace_bytes(int n_images, int D) {
 SCDA_API int scda_map_accumulate_hip(int n_images, int D, const float *score, const int *cls, const int *rank, const int *kept,
                                      const int *tp, const int *sum_gt, int num_classes, void *ws, double *ap, double *max_recall,
                                      int *rows, void *stream) {
-    ME_CHECK(score && cls && rank && kept && tp && sum_gt && ws && ap && max_recall && rows && (uintptr_t)ws % 16 == 0,
-             "scda_map_accumulate_hip")
-    ME_CHECK(n_images > 0 && D > 0 && D <= kMaxPer && (long long)n_images * D < 0x7fffffffLL && num_classes >= 2 &&
-             num_classes <= kMaxClasses, "scda_map_accumulate_hip (limits: D <= 1024, 2 <= num_classes <= 256)")
+    SCDA_CHECK_ARGS(score && cls && rank && kept && tp && sum_gt && ws && ap && max_recall && rows && (uintptr_t)ws % 16 == 0,
+                    "scda_map_accumulate_hip")
+    SCDA_CHECK_ARGS(n_images > 0 && D > 0 && D <= kMaxPer && (long long)n_images * D < 0x7fffffffLL && num_classes >= 2 &&
+                    num_classes <= kMaxClasses, "scda_map_accumulate_hip (limits: D <= 1024, 2 <= num_classes <= 256)")
     const AccLayout l = acc_layout(n_images, D);
     char *w8 = (char *)ws;
     uint32_t *perm_a = (uint32_t *)(w8 + l.perm_a), *perm_b = (uint32_t *)(w8 + l.perm_b), *hist = (uint32_t *)(w8 + l.hist);
@@ -376,15 +338,12 @@ SCDA_API int scda_map_accumulate_hip(int n_images, int D, const float *score, co
     if (hipMemsetAsync(perm_a, 0, (size_t)n * 4, st) != hipSuccess) return launch_status("scda_map_accumulate_hip (memset)");
     hipLaunchKernelGGL(map_perm_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, rank, D, perm_a, n);
     MapKey key = {1, 0, score, cls, kept};
-    for (int pass = 0; pass < 4; ++pass) {
-        key.shift = 8 * pass;
-        radix::sort_pass(perm_a, perm_b, n, key, hist, st);
-        uint32_t *t = perm_a; perm_a = perm_b; perm_b = t;
-    }
+    perm_a = radix::sort_u32(perm_a, perm_b, n, key, hist, st);
     key.kind = 2; key.shift = 0;
     radix::sort_pass(perm_a, perm_b, n, key, hist, st);
     if (hipMemsetAsync(seg, 0, (size_t)2 * kMaxClasses * 4, st) != hipSuccess) return launch_status("scda_map_accumulate_hip (memset)");
-    hipLaunchKernelGGL(map_segment_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, (const uint32_t *)perm_b, n, cls, kept, seg);
+    hipLaunchKernelGGL(segment_bounds_kernel<ClassKey>, dim3(cdiv(n, 256)), dim3(256), 0, st, n, ClassKey{perm_b, cls, kept}, kMaxClasses,
+                       seg);
     const PrArgs args = {perm_b, tp, seg, sum_gt, tpc, term, ap, max_recall, rows};
     hipLaunchKernelGGL(map_pr_kernel, dim3(num_classes), dim3(256), 0, st, args);
     return launch_status("map accumulate kernels");

@@ -6,7 +6,7 @@
 // left-to-right sum and the sample is (float) of the left-to-right double sum of (double)pixel * weight.  Every operation below is one
 // IEEE operation per source operator (compiled with -ffp-contract=off), which makes the result Pillow's bit for bit; the rule is
 // stated in include/scda_ops.h and restated in numpy by tests/test_mask_infer_rules.py.
-#include "common.h"
+#include "eval_prims.h"
 #include "mask_resample.h"      // bicubic, axis_ksize, axis_taps, trunc_ok
 
 namespace {
@@ -165,12 +165,10 @@ __global__ void mask_select_kernel(const float *__restrict__ logits, long long s
 
 }  // namespace
 
-#define MASK_CHECK(cond, name) if (!(cond)) { set_error(name ": bad arguments"); return SCDA_EINVAL; }
-
 SCDA_API int scda_det_rois_hip(const float *detections, const int *detection_counts, int B, int top_n, float *rois5, int *cls,
                                void *stream) {
-    MASK_CHECK(detections && detection_counts && rois5 && cls && B > 0 && top_n > 0 && (long long)B * top_n < 0x7fffffffLL,
-               "scda_det_rois_hip")
+    SCDA_CHECK_ARGS(detections && detection_counts && rois5 && cls && B > 0 && top_n > 0 && (long long)B * top_n < 0x7fffffffLL,
+                    "scda_det_rois_hip")
     hipLaunchKernelGGL(det_rois_kernel, dim3(cdiv((long long)B * top_n, 256)), dim3(256), 0, as_stream(stream), detections,
                        detection_counts, B, top_n, rois5, cls);
     return launch_status("det_rois_kernel");
@@ -178,8 +176,8 @@ SCDA_API int scda_det_rois_hip(const float *detections, const int *detection_cou
 
 SCDA_API int scda_mask_select_hip(const float *logits, long long stride_r, long long stride_c, long long stride_h, long long stride_w,
                                   const int *cls, int R, int C, int ph, int pw, int sigmoid, float *out, void *stream) {
-    MASK_CHECK(logits && cls && out && R > 0 && C > 0 && ph > 0 && pw > 0 && stride_r >= 0 && stride_c >= 0 && stride_h >= 0 &&
-               stride_w >= 0, "scda_mask_select_hip")
+    SCDA_CHECK_ARGS(logits && cls && out && R > 0 && C > 0 && ph > 0 && pw > 0 && stride_r >= 0 && stride_c >= 0 && stride_h >= 0 &&
+                    stride_w >= 0, "scda_mask_select_hip")
     hipLaunchKernelGGL(mask_select_kernel, dim3(ew_grid((long long)R * ph * pw)), dim3(256), 0, as_stream(stream), logits, stride_r,
                        stride_c, stride_h, stride_w, cls, R, C, ph, pw, sigmoid, out);
     return launch_status("mask_select_kernel");
@@ -187,8 +185,8 @@ SCDA_API int scda_mask_select_hip(const float *logits, long long stride_r, long 
 
 SCDA_API int scda_mask_paste_hip(const float *rois, int roi_stride, const int *cls_or_null, const float *planes, int R, int ph, int pw,
                                  int H, int W, int packed, float threshold, void *out, void *stream) {
-    MASK_CHECK(rois && planes && out && R > 0 && R <= 65535 && roi_stride >= 5 && ph > 0 && pw > 0 && ph <= kMaxIn && pw <= kMaxIn &&
-               H > 0 && W > 0, "scda_mask_paste_hip")
+    SCDA_CHECK_ARGS(rois && planes && out && R > 0 && R <= 65535 && roi_stride >= 5 && ph > 0 && pw > 0 && ph <= kMaxIn && pw <= kMaxIn &&
+                    H > 0 && W > 0, "scda_mask_paste_hip")
     const int Wd = (W + 31) / 32;
     const dim3 grid(cdiv(W, kStrip), R);
     if (packed) {

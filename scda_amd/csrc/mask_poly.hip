@@ -9,18 +9,18 @@
 //
 //   (memset)              the toggle planes and the areas
 //   poly_toggle_kernel    one wave per polygon edge, lanes over its points: the point and its predecessor in closed form, one atomicXor
-//   rle_toggle_kernel     one workgroup per RLE: prefix sums of the counts, one atomicXor per run end
+//   rle_toggle_kernel     one workgroup per RLE: prefix sums of the counts (block_scan256 of eval_prims.h), one atomicXor per run end
 //   parity_scan_kernel    one workgroup per shape: prefix parity over the linear pixel sequence, in place
 //   plane_write_kernel    per 32 x 32 block of an output plane: gathers the block's columns from every shape of the plane, ORs them,
 //                         transposes to row-major words, writes every word of the plane and adds the popcount to the area
 #include <limits.h>
 
-#include "common.h"
+#include "eval_prims.h"
 
 namespace {
 using namespace scda;
 
-constexpr int kThreads = 256;
+constexpr int kThreads = 256;                   // block_scan256 (eval_prims.h) is written for it
 constexpr int kMaxCoord = 65535;
 
 // the image size inside plane n; false for a plane index or a size out of range (such shapes are skipped: nothing is written out of bounds)
@@ -141,7 +141,7 @@ __global__ __launch_bounds__(kThreads) void rle_toggle_kernel(const uint32_t *__
                                                               const int *__restrict__ rle_plane, const int *__restrict__ sizes, int N,
                                                               int H, int Wd, size_t TW, uint32_t *__restrict__ tog) {
     __shared__ unsigned long long wave_sums[kThreads / kWave];
-    const int q = blockIdx.x, t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    const int q = blockIdx.x, t = threadIdx.x;
     const int a = rle_first[q], b = rle_first[q + 1];
     int h, w;
     if (a < 0 || b > C || a > b || !plane_size(sizes, N, H, Wd, rle_plane[q], &h, &w)) return;
@@ -151,26 +151,12 @@ __global__ __launch_bounds__(kThreads) void rle_toggle_kernel(const uint32_t *__
     unsigned long long base = 0;
     for (int i0 = 0; i0 < m; i0 += kThreads) {
         const int i = i0 + t;
-        unsigned long long inc = i < m ? counts[a + i] : 0ull;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const unsigned long long o = __shfl_up(inc, d, 64);
-            if (lane >= d) inc += o;
-        }
-        __syncthreads();                                                    // the previous round's wave_sums are read
-        if (lane == 63) wave_sums[wv] = inc;
-        __syncthreads();
-        unsigned long long before = 0, all = 0;
-#pragma unroll
-        for (int s = 0; s < kThreads / kWave; ++s) {
-            if (s < wv) before += wave_sums[s];
-            all += wave_sums[s];
-        }
+        unsigned long long all;
         // run i ends at the running sum; the pixels behind the last run stay 0 (a last run of zeros toggles nothing); a sum beyond
         // h * w (refused by the host layer, the reference writes past its buffer there) is dropped
-        const unsigned long long pos = base + before + inc;
+        const unsigned long long pos = base + block_scan256<unsigned long long>(i < m ? counts[a + i] : 0ull, wave_sums, Add(), base, &all);
         if (i < m && pos <= hw && (i < m - 1 || !(m & 1))) atomicXor(&T[pos >> 5], 1u << (pos & 31));
-        base += all;
+        base = all;
     }
 }
 
@@ -286,8 +272,6 @@ bool plane_ok(int N, int H, int Wd) {
 
 }  // namespace
 
-#define POLY_CHECK(cond, name) if (!(cond)) { set_error(name ": bad arguments"); return SCDA_EINVAL; }
-
 SCDA_API size_t scda_mask_frpoly_workspace_bytes(int P, int Q, int H, int Wd) {
     if (P < 0 || Q < 0 || !plane_ok(1, H, Wd)) return 0;
     const size_t bytes = ((size_t)P + Q) * toggle_words(H, Wd) * sizeof(uint32_t);
@@ -297,10 +281,10 @@ SCDA_API size_t scda_mask_frpoly_workspace_bytes(int P, int Q, int H, int Wd) {
 SCDA_API int scda_mask_frpoly_hip(const double *xy, int V, const int *poly_first, const int *poly_plane, int P, const uint32_t *rle_counts,
                                   int C, const int *rle_first, const int *rle_plane, int Q, const int *sizes, int N, int H, int Wd,
                                   void *ws, uint32_t *bits, uint32_t *area_or_null, void *stream) {
-    POLY_CHECK(sizes && bits && ws && (uintptr_t)ws % 16 == 0 && plane_ok(N, H, Wd) && V >= 0 && P >= 0 && C >= 0 && Q >= 0 &&
-               (long long)P + Q < 0x7fffffffLL, "scda_mask_frpoly_hip")
-    POLY_CHECK(P == 0 ? V == 0 : (poly_first && poly_plane && (xy || V == 0)), "scda_mask_frpoly_hip (polygons)")
-    POLY_CHECK(Q == 0 ? C == 0 : (rle_first && rle_plane && (rle_counts || C == 0)), "scda_mask_frpoly_hip (run lengths)")
+    SCDA_CHECK_ARGS(sizes && bits && ws && (uintptr_t)ws % 16 == 0 && plane_ok(N, H, Wd) && V >= 0 && P >= 0 && C >= 0 && Q >= 0 &&
+                    (long long)P + Q < 0x7fffffffLL, "scda_mask_frpoly_hip")
+    SCDA_CHECK_ARGS(P == 0 ? V == 0 : (poly_first && poly_plane && (xy || V == 0)), "scda_mask_frpoly_hip (polygons)")
+    SCDA_CHECK_ARGS(Q == 0 ? C == 0 : (rle_first && rle_plane && (rle_counts || C == 0)), "scda_mask_frpoly_hip (run lengths)")
     const size_t TW = toggle_words(H, Wd);
     const int nrb = (H + 31) / 32;
     uint32_t *tog = (uint32_t *)ws;

@@ -6,7 +6,7 @@
 // reach (the paste's two passes, mask_ops.hip), resizes them horizontally and then vertically.  The arithmetic is the paste's: the
 // coefficients of mask_resample.h, every sample (float) of the left-to-right double sum of (double)pixel * weight, one IEEE operation per
 // source operator (-ffp-contract=off).  The rule is stated in include/scda_ops.h and restated in numpy by tests/mask_orig_np.py.
-#include "common.h"
+#include "eval_prims.h"
 #include "mask_resample.h"
 
 namespace {
@@ -224,16 +224,14 @@ __global__ __launch_bounds__(kThreads) void mask_rescale_kernel(const float *__r
 
 }  // namespace
 
-#define RESCALE_CHECK(cond, name) if (!(cond)) { set_error(name ": bad arguments"); return SCDA_EINVAL; }
-
 SCDA_API int scda_mask_rescale_max_ratio(void) { return kRatio; }
 
 SCDA_API int scda_mask_rescale_hip(const float *rois, int roi_stride, const int *cls_or_null, const float *planes, int R, int ph, int pw,
                                    int H, int W, const float *image_info, int info_stride, int masks_per_image, int Ho, int Wo,
                                    int packed, float threshold, void *out, float *foot_rois, int *status, void *stream) {
-    RESCALE_CHECK(rois && planes && image_info && out && foot_rois && status && R > 0 && R <= 65535 && roi_stride >= 5 && ph > 0 &&
-                  pw > 0 && ph <= kMaxIn && pw <= kMaxIn && H > 0 && W > 0 && info_stride >= 5 && masks_per_image >= 1 && Ho > 0 && Wo > 0,
-                  "scda_mask_rescale_hip")
+    SCDA_CHECK_ARGS(rois && planes && image_info && out && foot_rois && status && R > 0 && R <= 65535 && roi_stride >= 5 && ph > 0 &&
+                    pw > 0 && ph <= kMaxIn && pw <= kMaxIn && H > 0 && W > 0 && info_stride >= 5 && masks_per_image >= 1 && Ho > 0 && Wo > 0,
+                    "scda_mask_rescale_hip")
     const int Wdo = (Wo + 31) / 32;
     const dim3 grid(Wdo, R);
     if (packed)

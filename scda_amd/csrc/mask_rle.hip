@@ -13,12 +13,12 @@
 //   rle_emit_kernel    per block: transition positions into the workspace at their run index                      [reads the bits again]
 //   rle_string_kernel  per mask : counts = differences of positions, the 6-bit string (length, scan, bytes)
 //   mask_iou_kernel    per pair : popcount(dt & gt) over the common columns, the box gate, the double division
-#include "common.h"
+#include "eval_prims.h"
 
 namespace {
 using namespace scda;
 
-constexpr int kThreads = 256;
+constexpr int kThreads = 256;                   // block_scan256 (eval_prims.h) is written for it
 constexpr int kPart = 8;                        // uint32 per block partial: area, xs, xe, ys, ye (+ 3 unused: two 16-byte stores)
 
 // the image size of mask r and the word columns [wa, wb) that have to be scanned
@@ -151,28 +151,6 @@ __global__ __launch_bounds__(kThreads) void rle_count_kernel(const uint32_t *__r
     pp[1] = make_uint4(ye, 0u, 0u, 0u);
 }
 
-// exclusive scan of one value per thread over the workgroup (256 threads = 4 waves); *total = the sum
-__device__ inline uint32_t block_excl_scan(uint32_t v, uint32_t *wave_sums, uint32_t *total) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    uint32_t inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t o = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += o;
-    }
-    __syncthreads();                                                    // the previous use of wave_sums is over
-    if (lane == 63) wave_sums[wv] = inc;
-    __syncthreads();
-    uint32_t before = 0, all = 0;
-#pragma unroll
-    for (int q = 0; q < kThreads / 64; ++q) {
-        if (q < wv) before += wave_sums[q];
-        all += wave_sums[q];
-    }
-    *total = all;
-    return before + inc - v;
-}
-
 // grid (R), 256 threads.  With cnt16: in place, cnt16[r, rb, c] becomes the number of transitions of column c above block rb, colbase
 // [R, Wd * 32] every column's first transition index, n_runs = transitions + 1.  Always: area, bbox from the partials.
 __global__ __launch_bounds__(kThreads) void rle_scan_kernel(int H, int Wd, int nrb, Sizes sz, uint16_t *__restrict__ cnt16,
@@ -229,9 +207,9 @@ __global__ __launch_bounds__(kThreads) void rle_scan_kernel(int H, int Wd, int n
             }
         }
         uint32_t total;
-        const uint32_t ex = block_excl_scan(tot, wave_sums, &total);
+        const uint32_t ex = block_scan256(tot, wave_sums, Add(), base, &total) - tot;
         if (c < 32 * g.wb) colbase[(size_t)r * Wd * 32 + c] = base + ex;
-        base += total;
+        base = total;
     }
     if (t == 0) n_runs[r] = (int)base + 1;
 }
@@ -320,9 +298,9 @@ __global__ __launch_bounds__(kThreads) void rle_string_kernel(int H, int Wd, Siz
             len = rle_chars(x, nullptr);
         }
         uint32_t total;
-        const uint32_t off = base + block_excl_scan((uint32_t)len, wave_sums, &total);
+        const uint32_t off = base + block_scan256((uint32_t)len, wave_sums, Add(), base, &total) - (uint32_t)len;
         if (k < n && off + (uint32_t)len <= (uint32_t)cap_bytes) rle_chars(x, chars + (size_t)r * cap_bytes + off);
-        base += total;
+        base = total;
     }
     if (t == 0) n_bytes[r] = (int)base;
 }
@@ -370,19 +348,31 @@ __global__ __launch_bounds__(kThreads) void mask_iou_kernel(const uint32_t *__re
     inter[(size_t)gi * M + d] = n;
 }
 
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 struct Layout { size_t cnt16, part, colbase, pos, total; int nrb; };
 
 Layout layout(int R, int H, int Wd, int cap_runs) {
     Layout l;
     l.nrb = (H + 31) / 32;
     const size_t blocks = (size_t)R * l.nrb * Wd;
-    l.cnt16 = 0;
-    l.part = align256(blocks * 32 * sizeof(uint16_t));
-    l.colbase = l.part + align256(blocks * kPart * sizeof(uint32_t));
-    l.pos = l.colbase + align256((size_t)R * Wd * 32 * sizeof(uint32_t));
-    l.total = l.pos + align256((size_t)R * (cap_runs > 0 ? cap_runs : 0) * sizeof(uint32_t));
+    Bump ws;
+    l.cnt16 = ws.take(blocks * 32 * sizeof(uint16_t));
+    l.part = ws.take(blocks * kPart * sizeof(uint32_t));
+    l.colbase = ws.take((size_t)R * Wd * 32 * sizeof(uint32_t));
+    l.pos = ws.take((size_t)R * (cap_runs > 0 ? cap_runs : 0) * sizeof(uint32_t));
+    l.total = ws.total();
+    return l;
+}
+
+// scda_mask_iou_hip's workspace: the partials of the M + N planes, then area [M + N] and bbox [M + N, 4]
+struct IouLayout { size_t part, area, total; int nrb; };
+
+IouLayout iou_layout(int planes, int H, int Wd) {
+    IouLayout l;
+    l.nrb = (H + 31) / 32;
+    Bump ws;
+    l.part = ws.take((size_t)planes * l.nrb * Wd * kPart * sizeof(uint32_t));
+    l.area = ws.take((size_t)planes * 5 * sizeof(uint32_t));
+    l.total = ws.total();
     return l;
 }
 
@@ -398,8 +388,6 @@ bool plane_ok(int R, int H, int Wd) {
 
 }  // namespace
 
-#define RLE_CHECK(cond, name) if (!(cond)) { set_error(name ": bad arguments"); return SCDA_EINVAL; }
-
 SCDA_API int scda_mask_rle_max_chars(int h, int w) {
     if (h <= 0 || w <= 0) return 0;
     return (bitlength((unsigned long long)h * (unsigned long long)w) + 1 + 4) / 5;
@@ -414,13 +402,13 @@ SCDA_API int scda_mask_rle_hip(const uint32_t *bits, int R, int H, int Wd, const
                                int h_all, int w_all, const float *rois_or_null, int roi_stride, int cap_runs, int cap_bytes, void *ws,
                                int *n_runs, uint32_t *counts, int *n_bytes, unsigned char *chars, uint32_t *area, uint32_t *bbox,
                                void *stream) {
-    RLE_CHECK(bits && ws && n_runs && counts && n_bytes && chars && area && bbox && plane_ok(R, H, Wd) && cap_runs >= 1 &&
-              (uintptr_t)ws % 16 == 0, "scda_mask_rle_hip")
-    RLE_CHECK(image_info ? (info_stride >= 2 && masks_per_image >= 1) : (h_all >= 1 && h_all <= H && w_all >= 1 && w_all <= Wd * 32),
-              "scda_mask_rle_hip (sizes)")
-    RLE_CHECK(!rois_or_null || roi_stride >= 5, "scda_mask_rle_hip (rois)")
-    RLE_CHECK((long long)cap_bytes >= (long long)cap_runs * scda_mask_rle_max_chars(H, Wd * 32) &&
-              (long long)cap_runs * R < 0x7fffffffLL, "scda_mask_rle_hip (cap_bytes < cap_runs * scda_mask_rle_max_chars(H, 32 Wd))")
+    SCDA_CHECK_ARGS(bits && ws && n_runs && counts && n_bytes && chars && area && bbox && plane_ok(R, H, Wd) && cap_runs >= 1 &&
+                    (uintptr_t)ws % 16 == 0, "scda_mask_rle_hip")
+    SCDA_CHECK_ARGS(image_info ? (info_stride >= 2 && masks_per_image >= 1) : (h_all >= 1 && h_all <= H && w_all >= 1 && w_all <= Wd * 32),
+                    "scda_mask_rle_hip (sizes)")
+    SCDA_CHECK_ARGS(!rois_or_null || roi_stride >= 5, "scda_mask_rle_hip (rois)")
+    SCDA_CHECK_ARGS((long long)cap_bytes >= (long long)cap_runs * scda_mask_rle_max_chars(H, Wd * 32) &&
+                    (long long)cap_runs * R < 0x7fffffffLL, "scda_mask_rle_hip (cap_bytes < cap_runs * scda_mask_rle_max_chars(H, 32 Wd))")
     const Layout l = layout(R, H, Wd, cap_runs);
     char *w8 = (char *)ws;
     uint16_t *cnt16 = (uint16_t *)(w8 + l.cnt16);
@@ -440,17 +428,16 @@ SCDA_API int scda_mask_rle_hip(const uint32_t *bits, int R, int H, int Wd, const
 
 SCDA_API size_t scda_mask_iou_workspace_bytes(int M, int N, int H, int Wd) {
     if (M <= 0 || N <= 0 || !plane_ok(M + N, H, Wd)) return 0;
-    const int nrb = (H + 31) / 32;
-    return align256((size_t)(M + N) * nrb * Wd * kPart * sizeof(uint32_t)) + align256((size_t)(M + N) * 5 * sizeof(uint32_t));
+    return iou_layout(M + N, H, Wd).total;
 }
 
 SCDA_API int scda_mask_iou_hip(const uint32_t *dt_bits, int M, const uint32_t *gt_bits, int N, int H, int Wd, int h, int w,
                                const unsigned char *iscrowd_or_null, void *ws, double *iou, uint32_t *inter, void *stream) {
-    RLE_CHECK(dt_bits && gt_bits && ws && iou && inter && M > 0 && N > 0 && M <= 65535 && N <= 65535 && plane_ok(M + N, H, Wd) &&
-              h >= 1 && h <= H && w >= 1 && w <= Wd * 32 && (uintptr_t)ws % 16 == 0, "scda_mask_iou_hip")
-    const int nrb = (H + 31) / 32;
-    uint32_t *part = (uint32_t *)ws;
-    uint32_t *area = (uint32_t *)((char *)ws + align256((size_t)(M + N) * nrb * Wd * kPart * sizeof(uint32_t)));
+    SCDA_CHECK_ARGS(dt_bits && gt_bits && ws && iou && inter && M > 0 && N > 0 && M <= 65535 && N <= 65535 && plane_ok(M + N, H, Wd) &&
+                    h >= 1 && h <= H && w >= 1 && w <= Wd * 32 && (uintptr_t)ws % 16 == 0, "scda_mask_iou_hip")
+    const IouLayout l = iou_layout(M + N, H, Wd);
+    const int nrb = l.nrb;
+    uint32_t *part = (uint32_t *)((char *)ws + l.part), *area = (uint32_t *)((char *)ws + l.area);
     uint32_t *bbox = area + (M + N);
     const Sizes sz = {nullptr, 0, 1, h, w, nullptr, 0};
     hipStream_t st = as_stream(stream);

@@ -1,9 +1,10 @@
 // radix_sort.h -- the stable LSD radix sort of the evaluators (coco_eval.hip, map_eval.hip): 8 bits per pass over a permutation of
-// row indices; per-tile histograms, one scan, a stable scatter (wave match by ballots).  A pass is templated on the key: any struct
-// passed by value with `__device__ uint32_t digit(uint32_t row) const`, the row's 8-bit digit of this pass.  The only atomics are
-// integer LDS histogram counters, so a pass gives the same bytes every time.
+// row indices; per-tile histograms, one scan (block_scan256 of eval_prims.h), a stable scatter (wave match by ballots).  A pass is
+// templated on the key: any struct passed by value with `__device__ uint32_t digit(uint32_t row) const`, the row's 8-bit digit of this
+// pass, taken at the key's `shift`; sort_u32 runs the four passes of a 32-bit key.  The only atomics are integer LDS histogram
+// counters, so a pass gives the same bytes every time.
 #pragma once
-#include "common.h"
+#include "eval_prims.h"
 
 namespace scda {
 namespace radix {
@@ -31,28 +32,6 @@ __global__ __launch_bounds__(64) void sort_hist_kernel(const uint32_t *__restric
     for (int q = lane; q < 256; q += 64) hist[(size_t)blockIdx.x * 256 + q] = h[q];
 }
 
-// exclusive scan of one value per thread over 256 threads
-__device__ inline uint32_t block_excl_scan256(uint32_t v, uint32_t *wave_sums, uint32_t *total) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    uint32_t inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t o = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += o;
-    }
-    __syncthreads();
-    if (lane == 63) wave_sums[wv] = inc;
-    __syncthreads();
-    uint32_t before = 0, all = 0;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        if (q < wv) before += wave_sums[q];
-        all += wave_sums[q];
-    }
-    *total = all;
-    return before + inc - v;
-}
-
 // one block of 256 threads: hist [tiles, 256] -> each (tile, digit)'s first output index, digits major
 static __global__ __launch_bounds__(256) void sort_scan_kernel(uint32_t *__restrict__ hist, int tiles) {
     __shared__ uint32_t wave_sums[4];
@@ -60,7 +39,7 @@ static __global__ __launch_bounds__(256) void sort_scan_kernel(uint32_t *__restr
     uint32_t tot = 0;
     for (int b = 0; b < tiles; ++b) tot += hist[(size_t)b * 256 + d];
     uint32_t all;
-    uint32_t run = block_excl_scan256(tot, wave_sums, &all);
+    uint32_t run = block_scan256(tot, wave_sums, Add(), 0u, &all) - tot;
     for (int b = 0; b < tiles; ++b) {
         const uint32_t v = hist[(size_t)b * 256 + d];
         hist[(size_t)b * 256 + d] = run;
@@ -105,6 +84,18 @@ inline void sort_pass(const uint32_t *src, uint32_t *dst, int n, const Key &key,
     hipLaunchKernelGGL(sort_hist_kernel<Key>, dim3(tiles), dim3(64), 0, st, src, n, key, hist);
     hipLaunchKernelGGL(sort_scan_kernel, dim3(1), dim3(256), 0, st, hist, tiles);
     hipLaunchKernelGGL(sort_scatter_kernel<Key>, dim3(tiles), dim3(64), 0, st, src, dst, n, key, (const uint32_t *)hist);
+}
+
+// the four stable passes over a 32-bit key (key.shift = 0, 8, 16, 24), between perm_a and perm_b; returns the buffer that holds the
+// result (an even number of passes: perm_a again, and perm_b is free for the next pass)
+template <class Key>
+inline uint32_t *sort_u32(uint32_t *perm_a, uint32_t *perm_b, int n, Key key, uint32_t *hist, hipStream_t st) {
+    for (int pass = 0; pass < 4; ++pass) {
+        key.shift = 8 * pass;
+        sort_pass(perm_a, perm_b, n, key, hist, st);
+        uint32_t *t = perm_a; perm_a = perm_b; perm_b = t;
+    }
+    return perm_a;
 }
 
 }  // namespace radix

@@ -19,12 +19,13 @@ import numpy as np
 import torch
 
 from scda_amd import native as N
+from scda_amd.eval_base import StreamingEvaluator
 
 MAX_PER_IMAGE = 1024
 MAX_CLASSES = 256
 
 
-class MapEvaluator:
+class MapEvaluator(StreamingEvaluator):
     """Fixed-capacity streaming cal_mAP.  add() stores each image's rows (int32 box, score, class, kept flag, rank, true-positive flag)
     on the device; accumulate() sorts and scans all rows collected so far; summarize() brings 2 * num_classes doubles and the integer
     counters to the host.
@@ -44,12 +45,8 @@ class MapEvaluator:
             raise ValueError("MapEvaluator: 2 <= num_classes <= 256, max_images >= 1, 1 <= max_dets / max_gts per image <= 1024")
         if not 1 <= self.keep_num <= self.D:
             raise ValueError("MapEvaluator: 1 <= keep_num <= max_dets_per_image (%d), got %d" % (self.D, self.keep_num))
-        dev = torch.device('cuda') if device is None else torch.device(device)
-        if dev.type != 'cuda':
-            raise N.ScdaNativeError("MapEvaluator needs a HIP device; there is no CPU path")
-        if dev.index is None:
-            dev = torch.device('cuda', torch.cuda.current_device())
-        self.device = dev
+        self._init_stream(device)
+        dev = self.device
         I, D, C = self.I, self.D, self.C
         z = lambda *s, dtype: torch.zeros(*s, dtype=dtype, device=dev)        # noqa: E731
         self.d_sum_gt = None
@@ -69,19 +66,10 @@ class MapEvaluator:
         self._i32 = z(2 * C + 2, dtype=torch.int32)
         self.rows, self.gt_num, self.rpn = self._i32[:C], self._i32[C:2 * C], self._i32[2 * C:]
         self.ws = torch.empty(max(N.map_accumulate_workspace_bytes(I, D), 16), dtype=torch.uint8, device=dev)
-        self.n_images = 0
-        self._accumulated = -1
 
     def reset(self):
         self._i32.zero_()
-        self.n_images, self._accumulated = 0, -1
-
-    def _dev(self, t, name, dtype, shape):
-        if not torch.is_tensor(t) or t.device != self.device or t.dtype != dtype or not t.is_contiguous():
-            t = N.upload(np.ascontiguousarray(t.cpu().numpy() if torch.is_tensor(t) else t), self.device, dtype).contiguous()   # (allocates)
-        if shape is not None and tuple(t.shape) != tuple(shape):
-            raise ValueError("MapEvaluator.add: %s must be %s, got %s" % (name, tuple(shape), tuple(t.shape)))
-        return t
+        self._reset_stream()
 
     @torch.no_grad()
     def add(self, detections, detection_counts, image_info, gt_boxes, gt_counts, proposals=None, proposal_counts=None, recall_gts=None,
@@ -96,8 +84,7 @@ class MapEvaluator:
         if not hasattr(detections, 'shape') or len(detections.shape) != 3 or detections.shape[1] != self.D or detections.shape[2] != 7:
             raise ValueError("MapEvaluator.add: detections must be [B, %d, 7] (max_dets_per_image = %d)" % (self.D, self.D))
         B = int(detections.shape[0])
-        if self.n_images + B > self.I:
-            raise ValueError("MapEvaluator.add: %d images exceed max_images = %d" % (self.n_images + B, self.I))
+        s0, s1 = self._slots(B)
         if len(gt_boxes.shape) != 3 or tuple(gt_boxes.shape[1:]) != (self.G, 5):
             raise ValueError("MapEvaluator.add: gt_boxes must be [B, %d, 5] (max_gts_per_image = %d)" % (self.G, self.G))
         if len(image_info.shape) != 2 or image_info.shape[0] != B or image_info.shape[1] < 2 or \
@@ -122,7 +109,6 @@ class MapEvaluator:
             if recall_gt_counts is None:
                 recall_gt_counts = np.full(B, rg.shape[1], np.int32)
             rc = self._dev(recall_gt_counts, "recall_gt_counts", torch.int32, (B,))
-        s0, s1 = self.n_images, self.n_images + B
         dbg_m = None if self.debug_match is None else self.debug_match[s0:s1]
         dbg_c = None if self.debug_claimed is None else self.debug_claimed[s0:s1]
         N.map_rows(det, dc, info, scale_column, self.C, self.keep_num, self.box[s0:s1], self.score[s0:s1], self.cls[s0:s1],
@@ -137,8 +123,7 @@ class MapEvaluator:
     def accumulate(self):
         """-> {'ap' [C], 'max_recall' [C] float64, 'rows' [C] int32}: device tensors of the evaluator (overwritten by the next call),
         cal_mAP's arrays over every image added so far"""
-        if self.n_images == 0:
-            raise ValueError("MapEvaluator.accumulate: no image was added")
+        self._require_images()
         N.map_accumulate(self.n_images, self.score, self.cls, self.rank, self.kept, self.tp,
                          self.gt_num if self.d_sum_gt is None else self.d_sum_gt, self.ws, self._f64[0], self._f64[1], self.rows)
         self._accumulated = self.n_images
@@ -148,8 +133,7 @@ class MapEvaluator:
     def summarize(self):
         """-> {'ap', 'max_recall' float64 [C], 'mAP' = np.mean(ap[1:]), 'mean_max_recall', 'rows' [C], 'sum_gt' [C], 'rpn_recalled',
         'rpn_gts', 'rpn_recall' (nan without recall rows)}; the one host wait.  The means are numpy's over the doubles that crossed."""
-        if self._accumulated != self.n_images:
-            self.accumulate()
+        self._ensure_accumulated()
         f = self._f64.cpu().numpy()
         i = self._i32.cpu().numpy()
         C = self.C

@@ -712,6 +712,13 @@ def mask_frpoly(xy, poly_first, poly_plane, rle_counts, rle_first, rle_plane, si
 
 
 # ------------------------------------------------- COCO AP (COCOeval) -------
+def _req_all(what, specs):
+    for t, name, dt, n in specs:
+        _req(t, name, dt)
+        if t.numel() < n:
+            raise ValueError(f"{what}: {name} holds {t.numel()} elements, {n} needed")
+
+
 def coco_det_rows(detections, detection_counts, K, xywh, area, score, cat, mask_area=None):
     """detections float32 [B, top_n, 7] + detection_counts int32 [B] -> the caller's xywh float64 [B, top_n, 4], area float64, score
     float32, cat int32 [B, top_n] (include/scda_ops.h: scda_coco_det_rows_hip).  mask_area int32 [B, top_n]: the RLE area, for 'segm'."""
@@ -762,16 +769,14 @@ def coco_match(iou, dt_counts, dt_cat, score, dt_area, gt_counts, gt_cat, gt_are
     B, D = dt_cat.shape
     G = gt_cat.shape[1]
     T, A = iou_thrs.numel(), area_rng.shape[0]
-    for t, name, dt, n in ((iou, "iou", torch.float64, B * G * D), (dt_counts, "dt_counts", torch.int32, B), (dt_cat, "dt_cat", torch.int32, B * D),
-                           (score, "score", torch.float32, B * D), (dt_area, "dt_area", torch.float64, B * D),
-                           (gt_counts, "gt_counts", torch.int32, B), (gt_cat, "gt_cat", torch.int32, B * G),
-                           (gt_area, "gt_area", torch.float64, B * G), (gt_iscrowd, "gt_iscrowd", torch.uint8, B * G),
-                           (iou_thrs, "iou_thrs", torch.float64, T), (area_rng, "area_rng", torch.float64, 2 * A),
-                           (rank, "rank", torch.int32, B * D), (bits, "bits", torch.int32, B * D * A), (npig, "npig", torch.int32, K * A),
-                           (seen, "seen", torch.int32, K)) + (((dbg_match, "dbg_match", torch.int32, B * D * A * T),) if dbg_match is not None else ()):
-        _req(t, name, dt)
-        if t.numel() < n:
-            raise ValueError(f"coco_match: {name} holds {t.numel()} elements, {n} needed")
+    _req_all("coco_match", ((iou, "iou", torch.float64, B * G * D), (dt_counts, "dt_counts", torch.int32, B),
+                            (dt_cat, "dt_cat", torch.int32, B * D), (score, "score", torch.float32, B * D),
+                            (dt_area, "dt_area", torch.float64, B * D), (gt_counts, "gt_counts", torch.int32, B),
+                            (gt_cat, "gt_cat", torch.int32, B * G), (gt_area, "gt_area", torch.float64, B * G),
+                            (gt_iscrowd, "gt_iscrowd", torch.uint8, B * G), (iou_thrs, "iou_thrs", torch.float64, T),
+                            (area_rng, "area_rng", torch.float64, 2 * A), (rank, "rank", torch.int32, B * D),
+                            (bits, "bits", torch.int32, B * D * A), (npig, "npig", torch.int32, K * A), (seen, "seen", torch.int32, K))
+             + (((dbg_match, "dbg_match", torch.int32, B * D * A * T),) if dbg_match is not None else ()))
     _check(lib().scda_coco_match_hip(_p(iou), B, D, G, _p(dt_counts), _p(dt_cat), _p(score), _p(dt_area), _p(gt_counts), _p(gt_cat),
                                      _p(gt_area), _p(gt_iscrowd), int(K), _p(iou_thrs), T, _p(area_rng), A, int(max_det), _p(rank),
                                      _p(bits), _p(npig), _p(seen), _p(dbg_match), _stream()), "scda_coco_match_hip")
@@ -787,15 +792,13 @@ def coco_accumulate(image_ids, n_images, cat, rank, score, bits, npig, seen, rec
     D = cat.shape[1]
     K, A = npig.shape
     R, M = rec_thrs.numel(), max_dets.numel()
-    for t, name, dt, n in ((image_ids, "image_ids", torch.int32, n_images), (cat, "cat", torch.int32, n_images * D),
-                           (rank, "rank", torch.int32, n_images * D), (score, "score", torch.float32, n_images * D),
-                           (bits, "bits", torch.int32, n_images * D * A), (npig, "npig", torch.int32, K * A), (seen, "seen", torch.int32, K),
-                           (rec_thrs, "rec_thrs", torch.float64, R), (max_dets, "max_dets", torch.int32, M),
-                           (precision, "precision", torch.float64, T * R * K * A * M), (recall, "recall", torch.float64, T * K * A * M),
-                           (scores, "scores", torch.float64, T * R * K * A * M), (ws, "ws", torch.uint8, 1)):
-        _req(t, name, dt)
-        if t.numel() < n:
-            raise ValueError(f"coco_accumulate: {name} holds {t.numel()} elements, {n} needed")
+    _req_all("coco_accumulate", ((image_ids, "image_ids", torch.int32, n_images), (cat, "cat", torch.int32, n_images * D),
+                                 (rank, "rank", torch.int32, n_images * D), (score, "score", torch.float32, n_images * D),
+                                 (bits, "bits", torch.int32, n_images * D * A), (npig, "npig", torch.int32, K * A),
+                                 (seen, "seen", torch.int32, K), (rec_thrs, "rec_thrs", torch.float64, R),
+                                 (max_dets, "max_dets", torch.int32, M), (precision, "precision", torch.float64, T * R * K * A * M),
+                                 (recall, "recall", torch.float64, T * K * A * M), (scores, "scores", torch.float64, T * R * K * A * M),
+                                 (ws, "ws", torch.uint8, 1)))
     need = coco_accumulate_workspace_bytes(n_images, D, K, A)
     if need == 0 or ws.numel() < need:
         raise ValueError("coco_accumulate: workspace too small or sizes out of range")
@@ -818,13 +821,6 @@ def coco_summarize(precision, recall, shape, spec, stats):
 
 
 # ------------------------------------------------- Cityscapes mAP (cal_mAP) --
-def _req_all(what, specs):
-    for t, name, dt, n in specs:
-        _req(t, name, dt)
-        if t.numel() < n:
-            raise ValueError(f"{what}: {name} holds {t.numel()} elements, {n} needed")
-
-
 def map_rows(detections, detection_counts, image_info, scale_column, num_classes, keep_num, box, score, cls, rank, kept, tp,
              dbg_match=None, dbg_claimed=None, G=1):
     """validate()'s rows of B images (include/scda_ops.h: scda_map_rows_hip, rule R1).  detections float32 [B, D, 7], detection_counts

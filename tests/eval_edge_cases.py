@@ -1,6 +1,6 @@
 """Seeded builders of the evaluators' structural edge cases: inputs whose shapes come from the constants of scda_amd/csrc/coco_eval.hip,
-map_eval.hip and radix_sort.h (wave and block rounds, the LDS stage, the 32-detection flush, the capacities, the parameter limits, the
-sort keys, the 256-row scan rounds), not from what data looks like.  tests/golden/make_golden_coco_eval.py and make_golden_voc_map.py
+map_eval.hip, radix_sort.h and the primitives they share in eval_prims.h (wave and block rounds, the LDS stage, the 32-detection flush,
+the capacities, the parameter limits, the sort keys, the 256-row scan rounds), not from what data looks like.  tests/golden/make_golden_coco_eval.py and make_golden_voc_map.py
 record the reference's outputs for them next to the older sets; tests/test_eval_edges_rules.py asserts that every case still crosses
 the boundary it was built for and tests/test_eval_edges_gpu.py runs the kernels over them.  Boxes sit on an integer grid (the recorded
 arrays compress, and equal IoUs are exact).  Nothing here depends on a GPU."""

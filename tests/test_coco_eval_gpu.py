@@ -134,6 +134,29 @@ def test_order_and_batching_of_the_images_do_not_matter(cuda, name):
             assert r[key].tobytes() == base[key].tobytes(), key
 
 
+def test_converted_inputs_give_the_bytes_of_device_inputs(cuda):
+    """add() takes device tensors of the stated types as they are and converts anything else (eval_base.StreamingEvaluator._dev, through
+    native.upload): host numpy arrays, device tensors of another dtype (each wide enough to hold the values exactly) and non-contiguous
+    ones give the arrays of the all-device run byte for byte"""
+    from scda_amd.coco_eval import CocoEvaluator
+    images, K, params = cnp.load_set(fixture(), 'rules')
+    D, G = CAPS['rules']
+    base = _default_run('rules', cuda)
+    args, _ = _batch(images, list(range(len(images))), D, G, cuda)
+    ids, det, dc, gb, ga, gi, gk, gc = args
+    wide = lambda t: torch.stack([t, t], -1)[..., 0]        # noqa: E731  (a non-contiguous view with the same values)
+    assert not wide(gb).is_contiguous()
+    variants = {'host numpy': [a.cpu().numpy() for a in args],
+                'other dtypes': [ids.long(), det.double(), dc.long(), wide(gb), wide(ga), gi.int(), gk.long(), gc.long()]}
+    for what, given in variants.items():
+        ev = CocoEvaluator(K, 'bbox', max_images=len(images), max_dets_per_image=D, max_gts_per_image=G, device=cuda,
+                           params={'area_rng': params['area_rng']})
+        ev.add(*given)
+        got = ev.accumulate()
+        for key in ('precision', 'recall', 'scores'):
+            assert got[key].cpu().numpy().tobytes() == base[key].tobytes(), (what, key)
+
+
 def test_segm_ious_come_from_mask_iou_on_packed_planes(cuda):
     from scda_amd import native as N
     z = fixture()

@@ -1,8 +1,8 @@
 """The structural edge sets of the two evaluators (tests/eval_edge_cases.py) on the CPU: the numpy statements (coco_eval_np.evaluate,
 voc_map_np.evaluate / recall) against the arrays the reference's own code recorded for them in tests/golden/coco_eval_ref.npz and
 voc_map_ref.npz, bit for bit, and -- from the inputs -- that every set still crosses the boundary of scda_amd/csrc/coco_eval.hip,
-map_eval.hip or radix_sort.h it was built for, so that a case that stops crossing it fails here and does not pass quietly on the GPU.
-The constants named below are the kernels'.  No GPU."""
+map_eval.hip, radix_sort.h or eval_prims.h (block_scan256, wave_compact) it was built for, so that a case that stops crossing it fails
+here and does not pass quietly on the GPU.  The constants named below are the kernels'.  No GPU."""
 import hashlib
 
 import numpy as np
