@@ -550,6 +550,46 @@ size_t scda_map_accumulate_workspace_bytes(int n_images, int D);
 int scda_map_accumulate_hip(int n_images, int D, const float *score, const int *cls, const int *rank, const int *kept, const int *tp,
                             const int *sum_gt, int num_classes, void *ws, double *ap, double *max_recall, int *rows, void *stream);
 
+/* ---- Merging sharded evaluators (scda_amd/csrc/eval_merge.hip; StreamingEvaluator.absorb / merge of scda_amd/eval_base.py) -------------
+ * Data-parallel validation: every rank fills an evaluator of its own over its shard; the ranks' rows are gathered as [W, cap, ...]
+ * (W shards of cap image slots each) and merged into one evaluator, so that scda_map_accumulate_hip / scda_coco_accumulate_hip run
+ * unchanged on the merged rows.  What the reference does there: each rank writes results.txt.rank<r>, rank 0 concatenates them with
+ * `cat results.txt.rank*` (the shell's order: by the decimal rank STRING, so 0, 1, 10, 2, ... with 11 ranks) and scores the whole;
+ * images a DistributedSampler repeats as padding are not removed.  Integer work only; two runs give the same bytes.  No call waits for
+ * the host or allocates.  tests/sharded_map_np.py restates the rules in numpy; tests/golden/sharded_map_ref.npz holds what the
+ * reference's own cal_mAP gives for the concatenated rank files.  flags i32 [4] on the device, zeroed by the caller before the first
+ * merge: [0] = 1 the merged images exceeded max_images, [1] = 1 a duplicate that is not covered, [2] the number of duplicates,
+ * [3] the number of merged images when the counts live on the device.
+ *
+ * M1, scda_eval_place_rows_hip: one row array, as 32-bit words: src [W, cap, row_words] -> dst [max_images, row_words].  order_host
+ *   int [W] (host): a permutation of the shards; the merged images are, for k = 0..W-1, the images 0..counts[order[k]]-1 of shard
+ *   order[k], and they are written to the slots start, start + 1, ...  Either counts_host_or_null int [W] (host) or
+ *   counts_dev_or_null i32 [W] (device) is given.  Host counts: a count outside 0..cap or start + total > max_images is refused with
+ *   SCDA_EINVAL before anything is launched; only the total's slots are written.  Device counts: each is clamped to 0..cap; a total
+ *   beyond max_images - start sets flags[0] = 1 and the images beyond are dropped; EVERY slot start..max_images-1 is written, the
+ *   ones behind the total with an empty row -- fill 0: zeros, 1: word w = w (a rank that is a permutation of the slots), 2: all bits
+ *   set (the id -1) -- so that the caller can take max_images as its image count without knowing the total; flags[3] = start + total.
+ * M2, scda_eval_sum_counters_hip: dst[j] += sum over the W shards of src[w, j], src i32 [W, n] (gt_num and the recall counters of
+ *   scda_map_match_hip / scda_map_recall_hip, npig and seen of scda_coco_match_hip).  A duplicated image's ground truths are therefore
+ *   counted once per copy.
+ * M3, scda_eval_mark_duplicates_hip: image_ids i32 [n] in merged order.  A stable LSD radix sort (csrc/radix_sort.h, 4 passes) of the
+ *   positions by id; a position whose predecessor in that order has the same id >= 0 is a duplicate, and first[position] = the first
+ *   position of that id (the head of its run: block_scan256 with the maximum over 256 positions a round, one block); first = -1 for
+ *   every other position.  Ids < 0 mean "no identity" and are never duplicates.  flags[2] = the number of duplicates (overwritten);
+ *   with raise_on_duplicate != 0 any duplicate sets flags[1] = 1 (COCO: the reference would re-evaluate the image with both copies'
+ *   detections, which the stored rows cannot reproduce).  ws: scda_eval_mark_duplicates_workspace_bytes(n) bytes, 16-byte aligned.
+ * M4, scda_map_merge_duplicates_hip: cal_mAP with a repeated image: the later copy's rows sort behind the equal-scored rows of the
+ *   first copy (the sort is stable, R3), find their best ground truth claimed already or below the threshold, and are false positives.
+ *   For every image with first >= 0: tp = 0 for all its rows (kept stays); its box, score (by bits), cls, rank and kept are compared
+ *   with the first copy's over all D slots, and any difference sets flags[1] = 1 -- the rule is exact only for equal copies. */
+int scda_eval_place_rows_hip(const void *src, int W, int cap, int row_words, const int *order_host, const int *counts_host_or_null,
+                             const int *counts_dev_or_null, int start, int max_images, int fill, void *dst, int *flags, void *stream);
+int scda_eval_sum_counters_hip(const int *src, int W, int n, int *dst, void *stream);
+size_t scda_eval_mark_duplicates_workspace_bytes(int n);
+int scda_eval_mark_duplicates_hip(const int *image_ids, int n, void *ws, int *first, int *flags, int raise_on_duplicate, void *stream);
+int scda_map_merge_duplicates_hip(const int *first, int n, int D, const int *box, const float *score, const int *cls, const int *rank,
+                                  const int *kept, int *tp, int *flags, void *stream);
+
 /* ------------------------------------------------- convolution / GEMM ---- */
 /* The reference reaches these through torch.nn (cuDNN / cuBLAS): nn.Conv2d in
  * models/faster_rcnn/vgg_adver_expansion_cluster.py:101-114 (VGG body),

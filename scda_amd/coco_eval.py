@@ -9,6 +9,13 @@ NOT covered: keypoints / OKS, useCats = 0 (proposal AR), the text / JSON round t
 (scda_amd.coco_gt.GroundTruth builds them, masks included, from annotation dicts).  Detections and ground truth must be in the SAME coordinates -- dividing the
 network-input detections by resize_scale (or scaling the ground truth) stays with the caller.  Image ids must be distinct.
 
+Data-parallel validation: every rank fills an evaluator over its shard and one collective merge() leaves every rank holding all rows
+and the summed npig / seen (eval_base.StreamingEvaluator.merge, rules M1..M3 of include/scda_ops.h); accumulate() orders the rows by
+(image id, slot), so the order of the ranks has no effect.  The shards must be UNPADDED, e.g. Subset(ds, range(rank, n, world)): the
+reference would evaluate an image a DistributedSampler repeats once more with both copies' detections cut at maxDets, which the stored
+rows cannot reproduce (the ground truth is not kept) -- a repeated image id after the merge makes summarize() raise ValueError.  Only
+the rows accumulate() reads are merged (not xywh, area or the debug array).
+
     ev = CocoEvaluator(num_categories=80, iou_type='bbox', max_images=5000, max_dets_per_image=100, max_gts_per_image=64, device=dev)
     for images, info, ids, gt in loader:                      # nothing below waits for the host
         out = predictor(images, info)
@@ -18,7 +25,7 @@ import numpy as np
 import torch
 
 from scda_amd import native as N
-from scda_amd.eval_base import StreamingEvaluator
+from scda_amd.eval_base import StreamingEvaluator, merge_order  # noqa: F401
 
 MAX_PER_IMAGE = 1024
 
@@ -57,6 +64,10 @@ class CocoEvaluator(StreamingEvaluator):
     Gcap of the ground-truth tensors (<= 1024).  params: overrides of default_params() (e.g. scaled area ranges); the limits are 16
     thresholds, 8 area ranges (the summary uses the first four as all / small / medium / large), 4 maxDets, 128 recall thresholds.
     debug=True keeps the matched GT row of every (detection, area range, threshold) in .debug_match [max_images, D, A, T]."""
+
+    MERGE_ROWS = (('image_ids', 'minus_one'), ('score', 'zero'), ('cat', 'zero'), ('rank', 'zero'), ('bits', 'zero'))
+    MERGE_COUNTERS = ('npig', 'seen')
+    MERGE_RAISES_ON_DUPLICATE = True
 
     def __init__(self, num_categories, iou_type='bbox', max_images=5000, max_dets_per_image=100, max_gts_per_image=64, device=None,
                  params=None, debug=False):
@@ -98,6 +109,10 @@ class CocoEvaluator(StreamingEvaluator):
         self.ws = torch.empty(max(N.coco_accumulate_workspace_bytes(I, D, K, A), 16), dtype=torch.uint8, device=dev)
         self._iou = None                        # [B, G, D] of the largest batch seen
         self._miou = None                       # 'segm': scda_mask_iou_hip's workspace and raw intersections
+
+    def _merge_signature(self):
+        return (self.iou_type, self.K, self.I, self.D, self.G, self.iou_thrs.tobytes(), self.rec_thrs.tobytes(), tuple(self.max_dets),
+                self.area_rng.tobytes())
 
     def reset(self):
         self.npig.zero_(); self.seen.zero_()
@@ -182,4 +197,6 @@ class CocoEvaluator(StreamingEvaluator):
         """-> numpy float64 [12]: COCOeval.stats (AP, AP50, AP75, APs, APm, APl, AR1, AR10, AR100, ARs, ARm, ARl); the one host wait"""
         self._ensure_accumulated()
         N.coco_summarize(self.precision, self.recall, (self.T, self.R, self.K, self.A, self.M), self.d_specs, self.stats)
-        return self.stats.cpu().numpy()
+        stats = self.stats.cpu().numpy()
+        self._check_merge_flags()
+        return stats

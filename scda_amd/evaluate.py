@@ -145,7 +145,7 @@ def write_segm_results(writer, image_info, image_ids, out, category_of=None, inp
     return fallbacks
 
 
-def coco_stats(loader, predictor, evaluator, device=None):
+def coco_stats(loader, predictor, evaluator, device=None, distributed=False, group=None):
     """Drives a scda_amd.infer.Predictor over a loader into a scda_amd.coco_eval.CocoEvaluator and returns COCOeval's 12 stats (numpy
     float64).  Loader items are dicts: 'image' [B, 3, H, W], 'image_info' [B, >= 2], 'image_ids' int32 [B], and the ground truth as
     CocoEvaluator.add takes it -- 'gt_boxes' float64 [B, Gcap, 4] (x, y, w, h), 'gt_areas', 'gt_iscrowd', 'gt_categories', 'gt_counts',
@@ -164,7 +164,11 @@ def coco_stats(loader, predictor, evaluator, device=None):
     'sizes' = every image's (origin_h, origin_w) -- the item's 'sizes' if it has them, else image_info[:, 3:5] --, and the GroundTruth
     of 'annotations' is built at the planes of mask_bits_orig.  COCO's own annotations then need no rescaling, for 'bbox' and 'segm'
     alike.  The orig_status of every pass is kept on the device and read after the last one: ValueError, in place of stats that empty
-    masks would have entered silently, if any image was beyond the device limits (it names the image ids)."""
+    masks would have entered silently, if any image was beyond the device limits (it names the image ids).
+
+    distributed=True, with torch.distributed initialised: the loader is this rank's UNPADDED shard (e.g. Subset(ds, range(rank, n,
+    world)); a repeated image id raises ValueError) and CocoEvaluator.merge(group) runs before the summary, so every rank returns the
+    same stats.  The orig_status check stays this rank's own.  The default returns this rank's own result."""
     segm = evaluator.iou_type == 'segm'
     if segm and not (predictor.masks and predictor.rle):
         raise ValueError("coco_stats: a 'segm' evaluator needs Predictor(masks=True, rle=True)")
@@ -198,6 +202,7 @@ def coco_stats(loader, predictor, evaluator, device=None):
             if segm:
                 kw = {'mask_bits': bits, 'det_areas': out[5]['area'], 'gt_mask_bits': gt[5], 'sizes': sizes}
             evaluator.add(item['image_ids'], det, out[3], *gt[:5], **kw)
+    _merge_if_distributed(evaluator, distributed, group)
     stats = evaluator.summarize()
     flagged = [(int(i), int(v)) for ids, st in statuses for i, v in zip(_np(ids).reshape(-1), _np(st).reshape(-1)) if v]
     if flagged:
@@ -232,16 +237,27 @@ def meta_ground_truth(val_meta_file, num_classes):
     return gts
 
 
-def map_stats(loader, predictor, evaluator, ground_truth, scale_column=-1, device=None):
+def _merge_if_distributed(evaluator, distributed, group):
+    if distributed and dist.is_available() and dist.is_initialized():
+        evaluator.merge(group=group)
+
+
+def map_stats(loader, predictor, evaluator, ground_truth, scale_column=-1, device=None, distributed=False, group=None):
     """Drives a scda_amd.infer.Predictor over validate()'s loader into a scda_amd.map_eval.MapEvaluator and returns its summary: what
     Cal_MAP computes from validate()'s rows (ap, max_recall, mAP) plus validate()'s RPN recall, without the text files and with one
     wait for the host, the last one.  Loader items are validate()'s tuples: item[0] image [b, 3, h, w], item[1] image_info [b, >= 3],
     item[2] gts [b, G, 5] (for the recall, every row counted as the reference counts them), item[-1] filenames.  ground_truth:
     meta_ground_truth(...); each file's pure name is looked up there, an image missing there gets zero ground truths.  scale_column:
-    the image_info column the boxes are divided by (-1; 2 is the reference's dataset == 'coco' choice).  validate() is not involved."""
+    the image_info column the boxes are divided by (-1; 2 is the reference's dataset == 'coco' choice).  validate() is not involved.
+
+    Every image is added with an id: the position of its pure name in the meta file, -1 for an image the meta does not have (such an
+    image is never taken for a copy of another).  distributed=True, with torch.distributed initialised: the loader is this rank's
+    shard (a DistributedSampler, padding included), and MapEvaluator.merge(group) runs before the summary, so every rank returns the
+    SAME dict -- what the reference computes from the concatenated rank files.  The default returns this rank's own result."""
     from scda_amd import native
     device = evaluator.device if device is None else device
     G = evaluator.G
+    position = {name: k for k, name in enumerate(n for n in ground_truth if n != 'num')}
     with torch.no_grad():
         for item in loader:
             img, img_info, gt_boxes, filenames = item[0], item[1], item[2], item[-1]
@@ -250,14 +266,18 @@ def map_stats(loader, predictor, evaluator, ground_truth, scale_column=-1, devic
             on_device = torch.is_tensor(img_info) and img_info.is_cuda and img_info.dtype == torch.float32 and img_info.is_contiguous()
             info = img_info if on_device else predictor.image_info          # the Predictor's own upload of a host image_info
             boxes, counts = np.zeros((B, G, 5), dtype=np.int32), np.zeros(B, dtype=np.int32)
+            ids = np.full(B, -1, dtype=np.int32)
             for b in range(B):
-                rows = ground_truth.get(filenames[b].rsplit('/', 1)[-1].rsplit('.', 1)[0])
-                if rows is None:
+                pure = filenames[b].rsplit('/', 1)[-1].rsplit('.', 1)[0]
+                rows = ground_truth.get(pure)
+                if rows is None or pure == 'num':
                     continue
+                ids[b] = position[pure]
                 if len(rows) > G:
                     raise ValueError("map_stats: %s has %d ground truths, max_gts_per_image = %d" % (filenames[b], len(rows), G))
                 boxes[b, :len(rows)], counts[b] = rows, len(rows)
             evaluator.add(out[2], out[3], info, native.upload(boxes, device), native.upload(counts, device), proposals=out[0],
                           proposal_counts=out[1], recall_gts=native.upload(_np(gt_boxes).astype(np.float32), device),
-                          scale_column=scale_column)
+                          scale_column=scale_column, image_ids=native.upload(ids, device))
+    _merge_if_distributed(evaluator, distributed, group)
     return evaluator.summarize()

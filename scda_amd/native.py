@@ -892,6 +892,75 @@ def map_accumulate(n_images, score, cls, rank, kept, tp, sum_gt, ws, ap, max_rec
                                          _p(max_recall), _p(rows), _stream()), "scda_map_accumulate_hip")
 
 
+# ------------------------------------------------- merging sharded evaluators --
+EVAL_FILL = {"zero": 0, "slot": 1, "minus_one": 2}
+MAX_SHARDS = 256
+
+
+def eval_place_rows(src, order, counts, start, dst, flags, fill="zero"):
+    """One row array of W gathered shards into an evaluator's rows (include/scda_ops.h: scda_eval_place_rows_hip, rule M1).  src
+    [W, cap, ...] and dst [max_images, ...] of one 4- or 8-byte dtype and one row shape; order: a permutation of range(W) on the host;
+    counts: W host integers, or an int32 [W] device tensor (then every slot from `start` on is written, `fill` behind the total);
+    flags int32 [4]."""
+    if not (src.is_cuda and dst.is_cuda and src.is_contiguous() and dst.is_contiguous()) or src.dtype != dst.dtype or \
+            src.element_size() not in (4, 8) or src.dim() < 2 or tuple(src.shape[2:]) != tuple(dst.shape[1:]):
+        raise ValueError("eval_place_rows: src [W, cap, ...] and dst [max_images, ...] contiguous device tensors of one 4- or 8-byte dtype")
+    _req(flags, "flags", torch.int32)
+    W, cap = int(src.shape[0]), int(src.shape[1])
+    words = (src[0, 0].numel() if src.dim() > 2 else 1) * src.element_size() // 4
+    if W > MAX_SHARDS or len(order) != W or flags.numel() < 4:
+        raise ValueError("eval_place_rows: at most %d shards, one order entry per shard, flags [4]" % MAX_SHARDS)
+    order_c = (ctypes.c_int * W)(*[int(o) for o in order])
+    on_device = torch.is_tensor(counts)
+    if on_device:
+        _req(counts, "counts", torch.int32)
+        if counts.numel() != W:
+            raise ValueError("eval_place_rows: counts must hold one entry per shard")
+    else:
+        counts_c = (ctypes.c_int * W)(*[int(c) for c in counts])
+    _check(lib().scda_eval_place_rows_hip(_p(src), W, cap, words, order_c, None if on_device else counts_c, _p(counts) if on_device else None,
+                                          int(start), int(dst.shape[0]), EVAL_FILL[fill], _p(dst), _p(flags), _stream()),
+           "scda_eval_place_rows_hip")
+
+
+def eval_sum_counters(src, dst):
+    """dst int32 [n] += the sum over the shards of src int32 [W, n] (scda_eval_sum_counters_hip, rule M2)"""
+    W = int(src.shape[0])
+    n = dst.numel()
+    _req_all("eval_sum_counters", ((src, "src", torch.int32, W * n), (dst, "dst", torch.int32, n)))
+    if src.numel() != W * n:
+        raise ValueError("eval_sum_counters: src must be [W, %d]" % n)
+    _check(lib().scda_eval_sum_counters_hip(_p(src), W, n, _p(dst), _stream()), "scda_eval_sum_counters_hip")
+
+
+def eval_mark_duplicates_workspace_bytes(n):
+    return int(lib().scda_eval_mark_duplicates_workspace_bytes(n))
+
+
+def eval_mark_duplicates(image_ids, n, ws, first, flags, raise_on_duplicate=False):
+    """first int32 [n] = the first merged position of a repeated image id >= 0, else -1; flags[2] = the number of duplicates
+    (scda_eval_mark_duplicates_hip, rule M3)"""
+    _req_all("eval_mark_duplicates", ((image_ids, "image_ids", torch.int32, n), (first, "first", torch.int32, n),
+                                      (flags, "flags", torch.int32, 4), (ws, "ws", torch.uint8, 1)))
+    need = eval_mark_duplicates_workspace_bytes(n)
+    if need == 0 or ws.numel() < need:
+        raise ValueError("eval_mark_duplicates: workspace too small or n out of range")
+    _check(lib().scda_eval_mark_duplicates_hip(_p(image_ids), int(n), _p(ws), _p(first), _p(flags), 1 if raise_on_duplicate else 0,
+                                               _stream()), "scda_eval_mark_duplicates_hip")
+
+
+def map_merge_duplicates(first, n, box, score, cls, rank, kept, tp, flags):
+    """cal_mAP's treatment of a repeated image: tp = 0 for the rows of every later copy; flags[1] = 1 if a copy's rows differ from the
+    first copy's (scda_map_merge_duplicates_hip, rule M4)"""
+    D = cls.shape[1]
+    _req_all("map_merge_duplicates", ((first, "first", torch.int32, n), (box, "box", torch.int32, n * D * 4),
+                                      (score, "score", torch.float32, n * D), (cls, "cls", torch.int32, n * D),
+                                      (rank, "rank", torch.int32, n * D), (kept, "kept", torch.int32, n * D), (tp, "tp", torch.int32, n * D),
+                                      (flags, "flags", torch.int32, 4)))
+    _check(lib().scda_map_merge_duplicates_hip(_p(first), int(n), D, _p(box), _p(score), _p(cls), _p(rank), _p(kept), _p(tp), _p(flags),
+                                               _stream()), "scda_map_merge_duplicates_hip")
+
+
 # ------------------------------------------------- convolution / GEMM -------
 _WS = {}
 
