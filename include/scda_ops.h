@@ -435,7 +435,8 @@ int scda_mask_frpoly_hip(const double *xy, int V, const int *poly_first, const i
  * the rules in numpy; tests/golden/coco_eval_ref.npz holds what the reference's own code gives.  Thresholds, area ranges and maxDets
  * are DEVICE arrays filled by the host (np.linspace values as Params.setDetParams computes them); the limits are T <= 16 thresholds,
  * A <= 8 area ranges, M <= 4 maxDets, R <= 128 recall thresholds, K <= 255 categories (indices 1..K), D, G <= 1024 detection slots /
- * ground truths per image.  Not covered: keypoints / OKS, useCats = 0, the JSON round trip, annotation loading (annToMask: see above).  No call waits for
+ * ground truths per image.  Keypoints (OKS) and useCats = 0 (proposal AR) are stated behind the detection rules below.  Not covered:
+ * the keypoint head, useCats = 0 for keypoints, the JSON round trip, annotation loading (annToMask: see above).  No call waits for
  * the host or allocates.
  *
  * scda_coco_det_rows_hip: detections [B, top_n, 7] = (b, x1, y1, x2, y2, score, class) + detection_counts i32 [B] (scda_box_predict_hip's
@@ -480,7 +481,56 @@ int scda_mask_frpoly_hip(const double *xy, int V, const int *poly_first, const i
  *   from numpy's pairwise mean by at most 2 N 2^-53 for N averaged entries in [0, 1].  The 12 specs are the host's
  *   (scda_amd.coco_eval.stat_specs) and select maxDets as the reference does: maxDets[2] for stats 1..5 and 8..11, maxDets[0] and
  *   maxDets[1] for stats 6 and 7, and for stat 0 the entry EQUAL to 100 (_summarize's default), none -- t = -2, the stat is -1 -- when
- *   the list holds no 100. */
+ *   the list holds no 100.
+ *
+ * Keypoints (iouType 'keypoints', computeOks of cocoeval.py:193-234, Params.setKpParams, _summarizeKps): the same match, accumulate
+ * and summarize kernels over an OKS block in place of the IoU block.  Kp <= 32 keypoints (only Kp = 17 with the reference's sigmas is
+ * pinned to the reference), A >= 3 area ranges (all, medium, large).
+ * scda_coco_kp_rows_hip: the rows of scda_coco_det_rows_hip for keypoint results.  detections [B, top_n, 7] supply score and class (the
+ *   corners are not read); keypoints f32 [B, top_n, Kp, 3] = (x, y, anything), each value cast to double.  As loadRes (coco.py:350-357):
+ *   x0, x1 = min, max over ALL Kp x values, visible or not, y likewise; dt_xywh = (x0, y0, x1 - x0, y1 - y0), dt_area = (x1 - x0) *
+ *   (y1 - y0).  Slots at or past the image's count get zero rows and cat 0 whatever their keypoints hold.
+ * scda_coco_oks_hip: computeOks for B images -> oks f64 [B, G * D], o[g * D + d] per image, the layout of scda_coco_box_iou_hip, written
+ *   for d < dt_counts[b], g < gt_counts[b] (nothing else is touched).  dt_keypoints f32 [B, D, Kp, 3]; gt_keypoints f64 [B, G, Kp, 3] =
+ *   (x, y, v); gt_boxes f64 [B, G, 4] xywh; gt_areas f64 [B, G]; vars f64 [Kp] = (sigmas * 2) ** 2 as numpy computes it.  Per pair, in
+ *   double, each line single IEEE operations left to right, nothing contracted:
+ *     k1 = the number of vg > 0;
+ *     k1 > 0: dx = xd - xg, dy = yd - yg for every keypoint; else x0 = bb.x - bb.w, x1 = bb.x + bb.w * 2, y0 = bb.y - bb.h,
+ *       y1 = bb.y + bb.h * 2; dx = fmax(0, x0 - xd) + fmax(0, xd - x1), dy likewise;
+ *     e = (dx * dx + dy * dy) / vars / (area_gt + 2.220446049250313e-16) / 2;
+ *     oks = (the sum of exp(-e) over the keypoints with vg > 0 when k1 > 0, else over all Kp, in ascending keypoint order) / (k1 > 0 ?
+ *       k1 : Kp).
+ *   e is the reference's bit for bit; exp is not (numpy's and the device's are each faithful to about 1 ulp, and np.sum adds in another
+ *   order): at most 17 terms in [0, 1] keep the difference below 1e-14.  One thread per pair, one workgroup per (image, GT, 256
+ *   detection slots); the GT's values and vars are staged in LDS once.  computeOks also cuts the detections at maxDets[-1] behind the
+ *   score sort and returns [] when either side is empty: both are what scda_coco_match_hip does already (ranks >= max_det take no part;
+ *   without GTs nothing matches), so every pair of the image is written here.
+ *   With gt_ignore_or_null u8 [B, G] (then gt_iscrowd u8 and gt_num_keypoints i32 [B, G] are required): gt_ignore[b, g] = iscrowd ||
+ *   num_keypoints == 0 for g < gt_counts[b] -- the annotation's OWN num_keypoints field (cocoeval.py:108-112), while k1 above counts
+ *   v > 0; the two may disagree in a malformed file and both are kept as the reference keeps them.
+ * scda_coco_match_ign_hip: scda_coco_match_hip (the same kernel) with the GT's ignore flag given apart from its iscrowd.
+ *   gt_ignore_or_null u8 [B, G]: _ignore = gt_ignore || area outside the range, while "matched already and no crowd" still reads the
+ *   raw iscrowd (cocoeval.py:262, 281).  A null pointer means iscrowd: the results of scda_coco_match_hip, byte for byte.
+ * The ten specs of _summarizeKps go through scda_coco_summarize_hip (scda_amd.coco_eval.kps_stat_specs): AP, AP50, AP75, APm, APl, AR,
+ *   AR50, AR75, ARm, ARl, area indices 0 / 1 / 2, all at the maxDets entry EQUAL to 20 -- none (t = -2, the stat is -1) when the list
+ *   holds no 20.
+ *
+ * Category-agnostic evaluation (useCats = 0, cocoeval.py:99-101, 143, 169-171, 245-247; utils/coco_eval.py:56-58 switches it on for
+ * proposals with maxDets [1, 100, 1000]): K = 1 in every result array; per image the detections are the concatenation of the
+ * categories' lists in ascending category id, each in the order given, and the GTs likewise.  So score ties are broken by (category
+ * ascending, given order) and the GT order -- which decides "the later GT wins at equal IoU" and the order among ignored GTs -- is
+ * (category ascending, given order).
+ * scda_coco_regroup_hip: that order, made physical BEHIND the IoU (computed in the given order, so 'segm' needs no plane moved) and
+ *   BEFORE scda_coco_match_hip, which then runs unchanged with K = 1.  Per image one workgroup: a stable counting sort (LDS histogram,
+ *   block scan) of the slots d < dt_counts[b] with 1 <= in_cat <= K and of the GT rows g < gt_counts[b] with 1 <= gt_cat <= K ->
+ *   perm_dets i32 [B, D] / perm_gts i32 [B, G]: the given slot / row at each regrouped place, -1 behind the live ones.  The rows
+ *   (dt_xywh, dt_area, score; out_gt_area, out_gt_iscrowd) are gathered into that order, cat / out_gt_cat = 1 for the live places and 0
+ *   (zero rows) behind; out_iou[g * D + d] = in_iou[perm_gts[g] * D + perm_dets[d]] for the live places.  Inputs and outputs must be
+ *   different buffers.  K <= 255, D, G <= 1024.
+ * scda_coco_prop_rows_hip: the rows of scda_coco_det_rows_hip from proposals f32 [B, P, 6] = (b, x1, y1, x2, y2, score)
+ *   (scda_rpn_proposals_batched_hip's) with cat = 1 below the image's count.  xyxy_as_xywh != 0 takes (x2, y2) as (w, h): the reference's
+ *   'proposal' run hands [x1, y1, x2, y2] to COCO as if it were xywh (utils/coco_eval.py:33-36), a defect reproduced only on request.
+ * Still not covered: the keypoint head itself, the JSON round trip, useCats = 0 for keypoints (computeOks then finds no GT). */
 int scda_coco_det_rows_hip(const float *detections, const int *detection_counts, int B, int top_n, const uint32_t *mask_area_or_null,
                            int K, double *dt_xywh, double *dt_area, float *score, int *cat, void *stream);
 int scda_coco_box_iou_hip(const double *dt, const int *dt_counts, const double *gt, const int *gt_counts, const unsigned char *iscrowd,
@@ -489,6 +539,24 @@ int scda_coco_match_hip(const double *iou, int B, int D, int G, const int *dt_co
                         const double *dt_area, const int *gt_counts, const int *gt_cat, const double *gt_area,
                         const unsigned char *gt_iscrowd, int K, const double *iou_thrs, int T, const double *area_rng, int A, int max_det,
                         int *rank, uint32_t *bits, int *npig, int *seen, int *dbg_match_or_null, void *stream);
+int scda_coco_match_ign_hip(const double *iou, int B, int D, int G, const int *dt_counts, const int *dt_cat, const float *score,
+                            const double *dt_area, const int *gt_counts, const int *gt_cat, const double *gt_area,
+                            const unsigned char *gt_iscrowd, const unsigned char *gt_ignore_or_null, int K, const double *iou_thrs, int T,
+                            const double *area_rng, int A, int max_det, int *rank, uint32_t *bits, int *npig, int *seen,
+                            int *dbg_match_or_null, void *stream);
+int scda_coco_kp_rows_hip(const float *detections, const int *detection_counts, int B, int top_n, const float *keypoints, int Kp, int K,
+                          double *dt_xywh, double *dt_area, float *score, int *cat, void *stream);
+int scda_coco_oks_hip(const float *dt_keypoints, const int *dt_counts, const double *gt_keypoints, const double *gt_boxes,
+                      const double *gt_areas, const int *gt_counts, const double *vars, int Kp, const unsigned char *gt_iscrowd_or_null,
+                      const int *gt_num_keypoints_or_null, int B, int D, int G, double *oks, unsigned char *gt_ignore_or_null,
+                      void *stream);
+int scda_coco_prop_rows_hip(const float *proposals, const int *proposal_counts, int B, int P, int xyxy_as_xywh, double *dt_xywh,
+                            double *dt_area, float *score, int *cat, void *stream);
+int scda_coco_regroup_hip(int B, int D, int G, int K, const int *dt_counts, const double *in_xywh, const double *in_area,
+                          const float *in_score, const int *in_cat, const int *gt_counts, const int *gt_cat, const double *gt_area,
+                          const unsigned char *gt_iscrowd, const double *in_iou, double *dt_xywh, double *dt_area, float *score, int *cat,
+                          double *out_gt_area, unsigned char *out_gt_iscrowd, int *out_gt_cat, double *out_iou, int *perm_dets,
+                          int *perm_gts, void *stream);
 size_t scda_coco_accumulate_workspace_bytes(int n_images, int D, int K, int A);
 int scda_coco_accumulate_hip(const int *image_ids, int n_images, int D, const int *cat, const int *rank, const float *score,
                              const uint32_t *bits, const int *npig, const int *seen, int K, int T, int A, const double *rec_thrs, int R,

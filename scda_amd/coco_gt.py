@@ -7,7 +7,8 @@ flatten_annotations() is the host half (numpy): it lays the annotations of a bat
 every limit the kernels rely on.  GroundTruth owns the device buffers and makes the call.
 
 NOT covered: boxes as segmentations (frBbox / rleFrBbox -- a polygon list whose first entry has four values is what the reference reads
-as boxes; it is refused here), keypoints, the resize of ground-truth masks for training (datasets/coco_dataset.py:200)."""
+as boxes; it is refused here), the resize of ground-truth masks for training (datasets/coco_dataset.py:200).  Keypoint annotations are
+carried as they stand (flatten_annotations(keypoints=True)) for CocoEvaluator(K, 'keypoints', num_keypoints=Kp); GroundTruth.load does not take them."""
 import numpy as np
 import torch
 
@@ -49,7 +50,7 @@ def _check_plane(H, Wd, n_planes):
                          % (n_planes, H, Wd))
 
 
-def flatten_annotations(per_image_anns, sizes, gcap, plane=None):
+def flatten_annotations(per_image_anns, sizes, gcap, plane=None, keypoints=False, num_keypoints=None):
     """per_image_anns: per image a list of COCO annotation dicts -- 'segmentation' (a list of polygons [x0, y0, x1, y1, ...],
     {'size': [h, w], 'counts': list} or {'size': [h, w], 'counts': str | bytes}), 'bbox' [x, y, w, h], 'area', 'iscrowd', 'category_id';
     sizes: one (h, w) or one per image; gcap: the ground-truth slots per image.  Annotation g of image b becomes plane b * gcap + g.
@@ -62,7 +63,13 @@ def flatten_annotations(per_image_anns, sizes, gcap, plane=None):
     no polygon is an empty mask.  ValueError -- before anything reaches the device -- for: more than gcap annotations in an image; sizes
     below 1 or, with plane = (H, Wd), outside the planes, and planes beyond the kernel's limits; a coordinate that is not finite or
     beyond +-65535; an RLE whose 'size' is not the image's or whose counts sum to more than h * w (the reference writes past its buffer
-    there); a polygon list whose first entry has four values or fewer (the reference reads those as boxes, or refuses them)."""
+    there); a polygon list whose first entry has four values or fewer (the reference reads those as boxes, or refuses them).
+
+    keypoints=True: the dict also holds gt_keypoints float64 [B, gcap, Kp, 3] (x, y, v) and gt_num_keypoints int32 [B, gcap] -- the
+    annotations' 'keypoints' (3 Kp values, the same Kp in every annotation) and 'num_keypoints' fields, each as it stands (the
+    evaluator reads both, as the reference does); an annotation without either, or with another length, raises ValueError.  Kp is
+    num_keypoints if given (every annotation must then hold 3 * num_keypoints values), else that of the first annotation -- a batch
+    without any annotation then raises, so a loader that may meet one passes num_keypoints."""
     B = len(per_image_anns)
     gcap = int(gcap)
     sz = np.asarray(sizes, dtype=np.int64).reshape(-1, 2)
@@ -84,6 +91,11 @@ def flatten_annotations(per_image_anns, sizes, gcap, plane=None):
     gt_iscrowd = np.zeros((B, gcap), np.uint8)
     gt_categories = np.zeros((B, gcap), np.int32)
     gt_counts = np.zeros(B, np.int32)
+    gt_keypoints, gt_num_keypoints = None, np.zeros((B, gcap), np.int32)
+    if num_keypoints is not None:
+        if not keypoints or int(num_keypoints) < 1:
+            raise ValueError("flatten_annotations: num_keypoints (>= 1) goes with keypoints=True")
+        gt_keypoints = np.zeros((B, gcap, int(num_keypoints), 3), np.float64)
     for b, anns in enumerate(per_image_anns):
         if len(anns) > gcap:
             raise ValueError("flatten_annotations: image %d has %d annotations, gcap = %d" % (b, len(anns), gcap))
@@ -92,6 +104,19 @@ def flatten_annotations(per_image_anns, sizes, gcap, plane=None):
         for g, ann in enumerate(anns):
             gt_boxes[b, g] = ann['bbox']
             gt_areas[b, g], gt_iscrowd[b, g], gt_categories[b, g] = ann['area'], ann.get('iscrowd', 0), ann['category_id']
+            if keypoints:
+                if 'keypoints' not in ann or 'num_keypoints' not in ann:
+                    raise ValueError("flatten_annotations: image %d annotation %d has no 'keypoints' / 'num_keypoints'" % (b, g))
+                kp = np.asarray(ann['keypoints'], dtype=np.float64).reshape(-1)
+                if gt_keypoints is None:
+                    if len(kp) == 0 or len(kp) % 3:
+                        raise ValueError("flatten_annotations: image %d annotation %d: 'keypoints' must hold 3 Kp values" % (b, g))
+                    gt_keypoints = np.zeros((B, gcap, len(kp) // 3, 3), np.float64)
+                if len(kp) != gt_keypoints.shape[2] * 3:
+                    raise ValueError("flatten_annotations: image %d annotation %d: %d keypoint values, %d in the first annotation"
+                                     % (b, g, len(kp), gt_keypoints.shape[2] * 3))
+                gt_keypoints[b, g] = kp.reshape(-1, 3)
+                gt_num_keypoints[b, g] = ann['num_keypoints']
             segm = ann['segmentation']
             n = b * gcap + g
             if isinstance(segm, (list, tuple)):
@@ -122,12 +147,17 @@ def flatten_annotations(per_image_anns, sizes, gcap, plane=None):
                 rle_first.append(rle_first[-1] + len(c))
                 rle_plane.append(n)
     i32 = lambda a: np.asarray(a, dtype=np.int32)                             # noqa: E731
-    return {'xy': np.concatenate(xy).reshape(-1, 2) if xy else np.zeros((0, 2), np.float64),
+    flat = {'xy': np.concatenate(xy).reshape(-1, 2) if xy else np.zeros((0, 2), np.float64),
             'poly_first': i32(poly_first), 'poly_plane': i32(poly_plane),
             'rle_counts': np.concatenate(counts) if counts else np.zeros(0, np.uint32),
             'rle_first': i32(rle_first), 'rle_plane': i32(rle_plane),
             'sizes': np.repeat(sz, gcap, axis=0).astype(np.int32),
             'gt_boxes': gt_boxes, 'gt_areas': gt_areas, 'gt_iscrowd': gt_iscrowd, 'gt_categories': gt_categories, 'gt_counts': gt_counts}
+    if keypoints:
+        if gt_keypoints is None:
+            raise ValueError("flatten_annotations: keypoints=True takes Kp from the first annotation and there is none; pass num_keypoints")
+        flat['gt_keypoints'], flat['gt_num_keypoints'] = gt_keypoints, gt_num_keypoints
+    return flat
 
 
 class GroundTruth:

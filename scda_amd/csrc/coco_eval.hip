@@ -1,16 +1,23 @@
 // coco_eval.hip -- COCO AP on the device (gfx950): the detection evaluator of datasets/pycocotools/cocoeval.py (COCOeval.evaluate,
-// accumulate, summarize for iouType 'bbox' / 'segm', useCats = 1) and bbIou of datasets/pycocotools/common/maskApi.c.  The rules are
-// stated in include/scda_ops.h and restated in numpy by tests/coco_eval_np.py.  Everything is integer work plus single IEEE double
-// operations in the reference's order (built with -ffp-contract=off), so the arrays are the reference's bit for bit; the only atomics
-// are integer adds (the non-ignored GT counts) and integer LDS histogram counters, so two runs give the same bytes.
+// accumulate, summarize for iouType 'bbox' / 'segm' / 'keypoints', and useCats = 0 for the first two) and bbIou of
+// datasets/pycocotools/common/maskApi.c.  The rules are stated in include/scda_ops.h and restated in numpy by tests/coco_eval_np.py and
+// tests/coco_kps_np.py.  Everything is integer work plus single IEEE double operations in the reference's order (built with
+// -ffp-contract=off), so the arrays are the reference's bit for bit -- but for the exp() of the OKS, whose last bit belongs to the
+// implementation --; the only atomics are integer adds (the non-ignored GT counts) and integer LDS histogram counters, so two runs give
+// the same bytes.
 //
 //   det_rows_kernel     per detection slot: xywh and area in double from the float32 corners, score, category (0 = padding)
 //   box_iou_kernel      per (image, gt, dt) pair: bbIou
+//   kp_rows_kernel      per detection slot of a keypoint run: the box and area of its keypoints' extent, score, category
+//   oks_kernel          per (image, gt, dt) pair: computeOks' object keypoint similarity; per GT the keypoint ignore flag
+//   prop_rows_kernel    per proposal slot: det_rows_kernel's rows from the RPN proposals, category 1
+//   regroup_kernel      useCats = 0, per image: the rows in (category, given) order by a stable counting sort, every live category 1;
+//                       regroup_iou_kernel: the image's IoU block in that order
 //   match_kernel        per (image, category): ranks, the GT orders, evaluateImg's greedy matching, one lane per (area range, threshold)
 //   sort_*_kernel       the stable LSD radix sort of radix_sort.h, 8 bits per pass, over the keys of SortKey
 //   gather_kernel       the rows in sorted order (score, rank, match bits); segment_bounds_kernel: the category segments
 //   pr_kernel           per (category, area range, maxDets): tp / fp scans, precision envelope, the recall thresholds
-//   stats_kernel        the 12 numbers of _summarizeDets
+//   stats_kernel        the 12 numbers of _summarizeDets, the 10 of _summarizeKps
 // The block scan, the envelope step, wave_compact, segment_bounds_kernel and the workspace allocator are those of eval_prims.h.
 #include "eval_prims.h"
 #include "radix_sort.h"
@@ -62,6 +69,189 @@ __global__ __launch_bounds__(256) void box_iou_kernel(const double *__restrict__
     iou[(size_t)b * D * G + i] = o;
 }
 
+// grid-stride over B * top_n slots.  kp [B, top_n, Kp, 3] float32 (x, y, anything): loadRes' box of a keypoint result (coco.py:350-357),
+// the extent of ALL Kp points; slots at or past the image's count are written as zero rows, whatever their keypoints hold
+__global__ __launch_bounds__(256) void kp_rows_kernel(const float *__restrict__ det, const int *__restrict__ counts, int B, int top_n,
+                                                      const float *__restrict__ kp, int Kp, int K, double *__restrict__ xywh,
+                                                      double *__restrict__ area, float *__restrict__ score, int *__restrict__ cat) {
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < B * top_n; i += gridDim.x * blockDim.x) {
+        const int b = i / top_n, d = i - b * top_n;
+        const float *r = det + (size_t)i * 7, *q = kp + (size_t)i * Kp * 3;
+        const bool live = d < counts[b];
+        double x0 = 0.0, y0 = 0.0, w = 0.0, h = 0.0;
+        if (live) {
+            double x1 = x0 = (double)q[0], y1 = y0 = (double)q[1];
+            for (int j = 1; j < Kp; ++j) {
+                const double x = (double)q[3 * j], y = (double)q[3 * j + 1];
+                x0 = fmin(x0, x); x1 = fmax(x1, x); y0 = fmin(y0, y); y1 = fmax(y1, y);
+            }
+            w = x1 - x0; h = y1 - y0;
+        }
+        const float c = r[6];
+        xywh[(size_t)i * 4 + 0] = x0; xywh[(size_t)i * 4 + 1] = y0; xywh[(size_t)i * 4 + 2] = w; xywh[(size_t)i * 4 + 3] = h;
+        area[i] = w * h;
+        score[i] = live ? r[5] : 0.0f;
+        cat[i] = (live && c >= 1.0f && c <= (float)K) ? (int)c : 0;
+    }
+}
+
+constexpr int kMaxKp = 32;
+
+// grid (cdiv(D, 256), G, B), 256 threads: one GT against 256 detection slots, one thread per pair; the GT's keypoints, box, area and
+// the variances are staged once.  o[b][g * D + d], d < dt_counts[b], g < gt_counts[b] (the rest is not written); the first block of a
+// GT also writes ignore[b][g] = iscrowd || num_keypoints == 0
+__global__ __launch_bounds__(256) void oks_kernel(const float *__restrict__ dt_kp, const int *__restrict__ dt_counts,
+                                                  const double *__restrict__ gt_kp, const double *__restrict__ gt_box,
+                                                  const double *__restrict__ gt_area, const int *__restrict__ gt_counts,
+                                                  const double *__restrict__ vars, const unsigned char *__restrict__ iscrowd,
+                                                  const int *__restrict__ gt_num_kp, int D, int G, int Kp, double *__restrict__ oks,
+                                                  unsigned char *__restrict__ ignore) {
+    __shared__ double s_g[kMaxKp][3], s_var[kMaxKp];
+    const int b = blockIdx.z, g = blockIdx.y, tid = threadIdx.x, d = blockIdx.x * 256 + tid;
+    if (g >= min(gt_counts[b], G)) return;      // block-uniform
+    if (ignore && blockIdx.x == 0 && tid == 0)
+        ignore[(size_t)b * G + g] = (iscrowd[(size_t)b * G + g] != 0 || gt_num_kp[(size_t)b * G + g] == 0) ? 1 : 0;
+    const int nd = min(dt_counts[b], D);
+    if (blockIdx.x * 256 >= nd) return;         // block-uniform
+    const double *gk = gt_kp + ((size_t)b * G + g) * Kp * 3;
+    for (int i = tid; i < Kp * 3; i += 256) s_g[i / 3][i % 3] = gk[i];
+    for (int i = tid; i < Kp; i += 256) s_var[i] = vars[i];
+    __syncthreads();
+    if (d >= nd) return;
+    int k1 = 0;
+    for (int i = 0; i < Kp; ++i) k1 += s_g[i][2] > 0.0 ? 1 : 0;
+    const double *bb = gt_box + ((size_t)b * G + g) * 4;
+    const double den = gt_area[(size_t)b * G + g] + 2.220446049250313e-16;
+    const double x0 = bb[0] - bb[2], x1 = bb[0] + bb[2] * 2.0, y0 = bb[1] - bb[3], y1 = bb[1] + bb[3] * 2.0;
+    const float *q = dt_kp + ((size_t)b * D + d) * Kp * 3;
+    double sum = 0.0;
+    for (int i = 0; i < Kp; ++i) {
+        if (k1 > 0 && !(s_g[i][2] > 0.0)) continue;
+        const double xd = (double)q[3 * i], yd = (double)q[3 * i + 1];
+        double dx, dy;
+        if (k1 > 0) {
+            dx = xd - s_g[i][0];
+            dy = yd - s_g[i][1];
+        } else {
+            dx = fmax(0.0, x0 - xd) + fmax(0.0, xd - x1);
+            dy = fmax(0.0, y0 - yd) + fmax(0.0, yd - y1);
+        }
+        const double e = (dx * dx + dy * dy) / s_var[i] / den / 2.0;
+        sum += exp(-e);
+    }
+    oks[(size_t)b * D * G + (size_t)g * D + d] = sum / (double)(k1 > 0 ? k1 : Kp);
+}
+
+// grid-stride over B * P slots.  prop [B, P, 6] = (b, x1, y1, x2, y2, score): the rows det_rows_kernel writes, category 1 for the slots
+// below the image's count.  as_xywh: (x2, y2) taken as (w, h), as utils/coco_eval.py:33-36 hands proposals to COCO
+__global__ __launch_bounds__(256) void prop_rows_kernel(const float *__restrict__ prop, const int *__restrict__ counts, int B, int P,
+                                                        int as_xywh, double *__restrict__ xywh, double *__restrict__ area,
+                                                        float *__restrict__ score, int *__restrict__ cat) {
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < B * P; i += gridDim.x * blockDim.x) {
+        const int b = i / P, d = i - b * P;
+        const float *r = prop + (size_t)i * 6;
+        const double x = (double)r[1], y = (double)r[2];
+        const double w = as_xywh ? (double)r[3] : (double)r[3] - x, h = as_xywh ? (double)r[4] : (double)r[4] - y;
+        const bool live = d < counts[b];
+        xywh[(size_t)i * 4 + 0] = x; xywh[(size_t)i * 4 + 1] = y; xywh[(size_t)i * 4 + 2] = w; xywh[(size_t)i * 4 + 3] = h;
+        area[i] = w * h;
+        score[i] = live ? r[5] : 0.0f;
+        cat[i] = live ? 1 : 0;
+    }
+}
+
+// The stable counting sort of useCats = 0 by one block of 256 threads: perm[0 .. live) = the indices i < n with 1 <= key[i] <= kmax (<= 255) in
+// (key ascending, index ascending) order, perm[live .. cap) = -1; -> live.  hist, base: 256 ints, keys: 256 ints, part: 4 ints of LDS
+__device__ inline int block_sort_by_category(const int *__restrict__ key, int n, int kmax, int cap, int *__restrict__ perm, int *hist, int *base,
+                                             int *keys, int *part) {
+    const int tid = threadIdx.x;
+    hist[tid] = 0;
+    __syncthreads();
+    for (int i = tid; i < n; i += 256) {
+        const int c = key[i];
+        if (c >= 1 && c <= kmax) atomicAdd(hist + c, 1);
+    }
+    __syncthreads();
+    const int v = hist[tid];
+    int live;
+    base[tid] = block_scan256(v, part, Add(), 0, &live) - v;
+    __syncthreads();
+    for (int r = 0; r < n; r += 256) {
+        const int i = r + tid;
+        int c = i < n ? key[i] : 0;
+        c = (c >= 1 && c <= kmax) ? c : 0;
+        keys[tid] = c;
+        __syncthreads();
+        if (c) {
+            int before = 0;
+            for (int j = 0; j < tid; ++j) before += keys[j] == c ? 1 : 0;
+            perm[base[c] + before] = i;
+        }
+        __syncthreads();
+        if (c) atomicAdd(base + c, 1);
+        __syncthreads();
+    }
+    for (int i = live + tid; i < cap; i += 256) perm[i] = -1;
+    return live;
+}
+
+struct RegroupArgs {
+    const int *dt_counts, *gt_counts;           // [B]
+    const double *in_xywh, *in_area;            // [B, D, 4], [B, D]: the rows in the order given
+    const float *in_score;
+    const int *in_cat;
+    const int *gt_cat;                          // [B, G]
+    const double *gt_area;
+    const unsigned char *gt_iscrowd;
+    int D, G, K;
+    double *xywh, *area;                        // the regrouped rows
+    float *score;
+    int *cat;
+    double *out_gt_area;                        // [B, G]
+    unsigned char *out_gt_iscrowd;
+    int *out_gt_cat;
+    int *perm_d, *perm_g;                       // [B, D], [B, G]: the slot / row given that stands at each regrouped place, -1 behind
+};
+
+// grid (B), 256 threads: the two permutations of image b and its rows in that order, category 1 for the live ones
+__global__ __launch_bounds__(256) void regroup_kernel(RegroupArgs p) {
+    __shared__ int s_hist[256], s_base[256], s_keys[256], s_part[4];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int nd = min(p.dt_counts[b], p.D), ng = min(p.gt_counts[b], p.G);
+    int *pd = p.perm_d + (size_t)b * p.D, *pg = p.perm_g + (size_t)b * p.G;
+    block_sort_by_category(p.in_cat + (size_t)b * p.D, nd, p.K, p.D, pd, s_hist, s_base, s_keys, s_part);
+    __syncthreads();
+    block_sort_by_category(p.gt_cat + (size_t)b * p.G, ng, p.K, p.G, pg, s_hist, s_base, s_keys, s_part);
+    __syncthreads();                            // the block's own global writes are visible to it behind the barrier
+    for (int j = tid; j < p.D; j += 256) {
+        const int s = pd[j];
+        const size_t o = (size_t)b * p.D + j, i = (size_t)b * p.D + (s >= 0 ? s : 0);
+        for (int q = 0; q < 4; ++q) p.xywh[o * 4 + q] = s >= 0 ? p.in_xywh[i * 4 + q] : 0.0;
+        p.area[o] = s >= 0 ? p.in_area[i] : 0.0;
+        p.score[o] = s >= 0 ? p.in_score[i] : 0.0f;
+        p.cat[o] = s >= 0 ? 1 : 0;
+    }
+    for (int j = tid; j < p.G; j += 256) {
+        const int s = pg[j];
+        const size_t o = (size_t)b * p.G + j, i = (size_t)b * p.G + (s >= 0 ? s : 0);
+        p.out_gt_area[o] = s >= 0 ? p.gt_area[i] : 0.0;
+        p.out_gt_iscrowd[o] = s >= 0 ? p.gt_iscrowd[i] : (unsigned char)0;
+        p.out_gt_cat[o] = s >= 0 ? 1 : 0;
+    }
+}
+
+// grid (cdiv(D * G, 256), B), behind regroup_kernel: out[g * D + d] = in[perm_g[g] * D + perm_d[d]] for the live places (the rest is
+// not written)
+__global__ __launch_bounds__(256) void regroup_iou_kernel(const double *__restrict__ in, const int *__restrict__ perm_d,
+                                                          const int *__restrict__ perm_g, int D, int G, double *__restrict__ out) {
+    const int b = blockIdx.y, i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= D * G) return;
+    const int g = i / D, d = i - g * D;
+    const int sg = perm_g[(size_t)b * G + g], sd = perm_d[(size_t)b * D + d];
+    if (sg < 0 || sd < 0) return;
+    out[(size_t)b * D * G + i] = in[(size_t)b * D * G + (size_t)sg * D + sd];
+}
+
 struct MatchArgs {
     const double *iou;                          // [B, G * D]
     const int *dt_counts, *dt_cat;              // [B], [B, D]
@@ -70,6 +260,7 @@ struct MatchArgs {
     const int *gt_counts, *gt_cat;              // [B], [B, G]
     const double *gt_area;                      // [B, G]
     const unsigned char *gt_iscrowd;            // [B, G]
+    const unsigned char *gt_ignore;             // [B, G] or null: the GT's own ignore flag where it is not its iscrowd (keypoints)
     const double *iou_thrs, *area_rng;          // [T], [A, 2]
     int D, G, K, T, A, max_det;
     int *rank;                                  // [B, D]
@@ -91,6 +282,7 @@ __global__ __launch_bounds__(kMatchThreads) void match_kernel(MatchArgs p) {
     const int nd = min(p.dt_counts[b], p.D), ng = min(p.gt_counts[b], p.G);
     const int *dcat = p.dt_cat + (size_t)b * p.D, *gcat = p.gt_cat + (size_t)b * p.G;
     const unsigned char *crowd = p.gt_iscrowd + (size_t)b * p.G;
+    const unsigned char *gign = p.gt_ignore ? p.gt_ignore + (size_t)b * p.G : crowd;
     // ---- this category's detections and ground truths, in the order given
     if (wv == 0) {
         const int c = wave_compact(nd, lane, s_dl, 0, [&](int i) { return dcat[i] == k + 1; });
@@ -113,11 +305,11 @@ __global__ __launch_bounds__(kMatchThreads) void match_kernel(MatchArgs p) {
         s_sorted[r] = s_dl[i];
         p.rank[(size_t)b * p.D + s_dl[i]] = r;
     }
-    // ---- per area range: _ignore = iscrowd || area < lo || area > hi; non-ignored first, otherwise as given
+    // ---- per area range: _ignore = ignore (iscrowd unless given) || area < lo || area > hi; non-ignored first, otherwise as given
     for (int a = wv; a < p.A; a += kMatchThreads / 64) {
         const double lo = p.area_rng[2 * a], hi = p.area_rng[2 * a + 1];
         const double *ga = p.gt_area + (size_t)b * p.G;
-        auto ign = [&](int i) { const int g = s_gl[i]; return crowd[g] != 0 || ga[g] < lo || ga[g] > hi; };
+        auto ign = [&](int i) { const int g = s_gl[i]; return gign[g] != 0 || ga[g] < lo || ga[g] > hi; };
         const int n0 = wave_compact(Gc, lane, s_go[a], 0, [&](int i) { return !ign(i); });
         wave_compact(Gc, lane, s_go[a], n0, [&](int i) { return ign(i); });
         if (lane == 0) {
@@ -437,18 +629,92 @@ SCDA_API int scda_coco_box_iou_hip(const double *dt, const int *dt_counts, const
     return launch_status("box_iou_kernel");
 }
 
+namespace {
+int launch_match(const char *name, const double *iou, int B, int D, int G, const int *dt_counts, const int *dt_cat, const float *score,
+                 const double *dt_area, const int *gt_counts, const int *gt_cat, const double *gt_area, const unsigned char *gt_iscrowd,
+                 const unsigned char *gt_ignore, int K, const double *iou_thrs, int T, const double *area_rng, int A, int max_det, int *rank,
+                 uint32_t *bits, int *npig, int *seen, int *dbg, void *stream) {
+    // the two checks and messages scda_coco_match_hip always had: the pointers, then the limits
+    if (!(iou && dt_counts && dt_cat && score && dt_area && gt_counts && gt_cat && gt_area && gt_iscrowd && iou_thrs && area_rng && rank &&
+          bits && npig && seen)) {
+        set_error("%s: bad arguments", name);
+        return SCDA_EINVAL;
+    }
+    if (!(B > 0 && B <= 65535 && D > 0 && D <= kMaxPer && G > 0 && G <= kMaxPer && K > 0 && K <= 65535 && T > 0 && T <= kMaxT && A > 0 &&
+          A <= kMaxA && max_det > 0)) {
+        set_error("%s (limits: D, G <= 1024, T <= 16, A <= 8): bad arguments", name);
+        return SCDA_EINVAL;
+    }
+    const MatchArgs args = {iou, dt_counts, dt_cat, score, dt_area, gt_counts, gt_cat, gt_area, gt_iscrowd, gt_ignore, iou_thrs, area_rng,
+                            D, G, K, T, A, max_det, rank, bits, npig, seen, dbg};
+    hipLaunchKernelGGL(match_kernel, dim3(K, B), dim3(kMatchThreads), 0, as_stream(stream), args);
+    return launch_status("match_kernel");
+}
+}  // namespace
+
 SCDA_API int scda_coco_match_hip(const double *iou, int B, int D, int G, const int *dt_counts, const int *dt_cat, const float *score,
                                  const double *dt_area, const int *gt_counts, const int *gt_cat, const double *gt_area,
                                  const unsigned char *gt_iscrowd, int K, const double *iou_thrs, int T, const double *area_rng, int A,
                                  int max_det, int *rank, uint32_t *bits, int *npig, int *seen, int *dbg_match_or_null, void *stream) {
-    SCDA_CHECK_ARGS(iou && dt_counts && dt_cat && score && dt_area && gt_counts && gt_cat && gt_area && gt_iscrowd && iou_thrs &&
-                    area_rng && rank && bits && npig && seen, "scda_coco_match_hip")
-    SCDA_CHECK_ARGS(B > 0 && B <= 65535 && D > 0 && D <= kMaxPer && G > 0 && G <= kMaxPer && K > 0 && K <= 65535 && T > 0 && T <= kMaxT &&
-                    A > 0 && A <= kMaxA && max_det > 0, "scda_coco_match_hip (limits: D, G <= 1024, T <= 16, A <= 8)")
-    const MatchArgs args = {iou, dt_counts, dt_cat, score, dt_area, gt_counts, gt_cat, gt_area, gt_iscrowd, iou_thrs, area_rng,
-                            D, G, K, T, A, max_det, rank, bits, npig, seen, dbg_match_or_null};
-    hipLaunchKernelGGL(match_kernel, dim3(K, B), dim3(kMatchThreads), 0, as_stream(stream), args);
-    return launch_status("match_kernel");
+    return launch_match("scda_coco_match_hip", iou, B, D, G, dt_counts, dt_cat, score, dt_area, gt_counts, gt_cat, gt_area, gt_iscrowd,
+                        nullptr, K, iou_thrs, T, area_rng, A, max_det, rank, bits, npig, seen, dbg_match_or_null, stream);
+}
+
+SCDA_API int scda_coco_match_ign_hip(const double *iou, int B, int D, int G, const int *dt_counts, const int *dt_cat, const float *score,
+                                     const double *dt_area, const int *gt_counts, const int *gt_cat, const double *gt_area,
+                                     const unsigned char *gt_iscrowd, const unsigned char *gt_ignore_or_null, int K,
+                                     const double *iou_thrs, int T, const double *area_rng, int A, int max_det, int *rank, uint32_t *bits,
+                                     int *npig, int *seen, int *dbg_match_or_null, void *stream) {
+    return launch_match("scda_coco_match_ign_hip", iou, B, D, G, dt_counts, dt_cat, score, dt_area, gt_counts, gt_cat, gt_area, gt_iscrowd,
+                        gt_ignore_or_null, K, iou_thrs, T, area_rng, A, max_det, rank, bits, npig, seen, dbg_match_or_null, stream);
+}
+
+SCDA_API int scda_coco_kp_rows_hip(const float *detections, const int *detection_counts, int B, int top_n, const float *keypoints, int Kp,
+                                   int K, double *dt_xywh, double *dt_area, float *score, int *cat, void *stream) {
+    SCDA_CHECK_ARGS(detections && detection_counts && keypoints && dt_xywh && dt_area && score && cat && B > 0 && top_n > 0 && K > 0 &&
+                    Kp > 0 && Kp <= kMaxKp && (long long)B * top_n < 0x7fffffffLL, "scda_coco_kp_rows_hip")
+    hipLaunchKernelGGL(kp_rows_kernel, dim3(ew_grid((long long)B * top_n)), dim3(256), 0, as_stream(stream), detections,
+                       detection_counts, B, top_n, keypoints, Kp, K, dt_xywh, dt_area, score, cat);
+    return launch_status("kp_rows_kernel");
+}
+
+SCDA_API int scda_coco_oks_hip(const float *dt_keypoints, const int *dt_counts, const double *gt_keypoints, const double *gt_boxes,
+                               const double *gt_areas, const int *gt_counts, const double *vars, int Kp,
+                               const unsigned char *gt_iscrowd_or_null, const int *gt_num_keypoints_or_null, int B, int D, int G,
+                               double *oks, unsigned char *gt_ignore_or_null, void *stream) {
+    SCDA_CHECK_ARGS(dt_keypoints && dt_counts && gt_keypoints && gt_boxes && gt_areas && gt_counts && vars && oks && Kp > 0 &&
+                    Kp <= kMaxKp && B > 0 && B <= 65535 && D > 0 && G > 0 && D <= kMaxPer && G <= kMaxPer &&
+                    (!gt_ignore_or_null || (gt_iscrowd_or_null && gt_num_keypoints_or_null)), "scda_coco_oks_hip")
+    hipLaunchKernelGGL(oks_kernel, dim3(cdiv(D, 256), G, B), dim3(256), 0, as_stream(stream), dt_keypoints, dt_counts, gt_keypoints,
+                       gt_boxes, gt_areas, gt_counts, vars, gt_iscrowd_or_null, gt_num_keypoints_or_null, D, G, Kp, oks,
+                       gt_ignore_or_null);
+    return launch_status("oks_kernel");
+}
+
+SCDA_API int scda_coco_prop_rows_hip(const float *proposals, const int *proposal_counts, int B, int P, int xyxy_as_xywh, double *dt_xywh,
+                                     double *dt_area, float *score, int *cat, void *stream) {
+    SCDA_CHECK_ARGS(proposals && proposal_counts && dt_xywh && dt_area && score && cat && B > 0 && P > 0 &&
+                    (long long)B * P < 0x7fffffffLL, "scda_coco_prop_rows_hip")
+    hipLaunchKernelGGL(prop_rows_kernel, dim3(ew_grid((long long)B * P)), dim3(256), 0, as_stream(stream), proposals, proposal_counts, B,
+                       P, xyxy_as_xywh, dt_xywh, dt_area, score, cat);
+    return launch_status("prop_rows_kernel");
+}
+
+SCDA_API int scda_coco_regroup_hip(int B, int D, int G, int K, const int *dt_counts, const double *in_xywh, const double *in_area,
+                                   const float *in_score, const int *in_cat, const int *gt_counts, const int *gt_cat,
+                                   const double *gt_area, const unsigned char *gt_iscrowd, const double *in_iou, double *dt_xywh,
+                                   double *dt_area, float *score, int *cat, double *out_gt_area, unsigned char *out_gt_iscrowd,
+                                   int *out_gt_cat, double *out_iou, int *perm_dets, int *perm_gts, void *stream) {
+    SCDA_CHECK_ARGS(dt_counts && in_xywh && in_area && in_score && in_cat && gt_counts && gt_cat && gt_area && gt_iscrowd && in_iou &&
+                    dt_xywh && dt_area && score && cat && out_gt_area && out_gt_iscrowd && out_gt_cat && out_iou && perm_dets && perm_gts &&
+                    in_iou != out_iou && in_xywh != dt_xywh && in_area != dt_area && in_score != score && in_cat != cat &&
+                    B > 0 && B <= 65535 && D > 0 && D <= kMaxPer && G > 0 && G <= kMaxPer && K > 0 && K <= 255, "scda_coco_regroup_hip")
+    const RegroupArgs args = {dt_counts, gt_counts, in_xywh, in_area, in_score, in_cat, gt_cat, gt_area, gt_iscrowd, D, G, K, dt_xywh,
+                              dt_area, score, cat, out_gt_area, out_gt_iscrowd, out_gt_cat, perm_dets, perm_gts};
+    hipLaunchKernelGGL(regroup_kernel, dim3(B), dim3(256), 0, as_stream(stream), args);
+    hipLaunchKernelGGL(regroup_iou_kernel, dim3(cdiv((long long)D * G, 256), B), dim3(256), 0, as_stream(stream), in_iou,
+                       (const int *)perm_dets, (const int *)perm_gts, D, G, out_iou);
+    return launch_status("regroup kernels");
 }
 
 SCDA_API size_t scda_coco_accumulate_workspace_bytes(int n_images, int D, int K, int A) {

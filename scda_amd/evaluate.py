@@ -145,7 +145,7 @@ def write_segm_results(writer, image_info, image_ids, out, category_of=None, inp
     return fallbacks
 
 
-def coco_stats(loader, predictor, evaluator, device=None, distributed=False, group=None):
+def coco_stats(loader, predictor, evaluator, device=None, distributed=False, group=None, proposals=False):
     """Drives a scda_amd.infer.Predictor over a loader into a scda_amd.coco_eval.CocoEvaluator and returns COCOeval's 12 stats (numpy
     float64).  Loader items are dicts: 'image' [B, 3, H, W], 'image_info' [B, >= 2], 'image_ids' int32 [B], and the ground truth as
     CocoEvaluator.add takes it -- 'gt_boxes' float64 [B, Gcap, 4] (x, y, w, h), 'gt_areas', 'gt_iscrowd', 'gt_categories', 'gt_counts',
@@ -168,7 +168,20 @@ def coco_stats(loader, predictor, evaluator, device=None, distributed=False, gro
 
     distributed=True, with torch.distributed initialised: the loader is this rank's UNPADDED shard (e.g. Subset(ds, range(rank, n,
     world)); a repeated image id raises ValueError) and CocoEvaluator.merge(group) runs before the summary, so every rank returns the
-    same stats.  The orig_status check stays this rank's own.  The default returns this rank's own result."""
+    same stats.  The orig_status check stays this rank's own.  The default returns this rank's own result.
+
+    proposals=True scores the RPN proposals instead (the reference's test types 'proposal' / 'person_proposal': average recall at 1,
+    100 and 1000 proposals with params={'max_dets': [1, 100, 1000]}): the evaluator must be a 'bbox' one built with use_cats=False and
+    max_dets_per_image = the Predictor's proposal capacity; it is fed out[0], out[1] through CocoEvaluator.add_proposals in place of
+    the detections.  Proposals stand at the network input's coordinates, so a Predictor with original_size is refused here.  A
+    use_cats=False evaluator with proposals=False is fed the detections (class rows scored category-agnostically).  A 'keypoints'
+    evaluator cannot be driven from here -- no keypoint head exists; feed CocoEvaluator.add directly -- and raises ValueError."""
+    if evaluator.iou_type == 'keypoints':
+        raise ValueError("coco_stats: there is no keypoint head to drive; feed a 'keypoints' evaluator through CocoEvaluator.add")
+    if proposals and (evaluator.use_cats or evaluator.iou_type != 'bbox'):
+        raise ValueError("coco_stats: proposals=True needs a 'bbox' evaluator built with use_cats=False")
+    if proposals and getattr(predictor, 'original_size', None) is not None:
+        raise ValueError("coco_stats: proposals=True is not covered for a Predictor with original_size")
     segm = evaluator.iou_type == 'segm'
     if segm and not (predictor.masks and predictor.rle):
         raise ValueError("coco_stats: a 'segm' evaluator needs Predictor(masks=True, rle=True)")
@@ -201,7 +214,10 @@ def coco_stats(loader, predictor, evaluator, device=None, distributed=False, gro
             kw = {}
             if segm:
                 kw = {'mask_bits': bits, 'det_areas': out[5]['area'], 'gt_mask_bits': gt[5], 'sizes': sizes}
-            evaluator.add(item['image_ids'], det, out[3], *gt[:5], **kw)
+            if proposals:
+                evaluator.add_proposals(item['image_ids'], out[0], out[1], *gt[:5])
+            else:
+                evaluator.add(item['image_ids'], det, out[3], *gt[:5], **kw)
     _merge_if_distributed(evaluator, distributed, group)
     stats = evaluator.summarize()
     flagged = [(int(i), int(v)) for ids, st in statuses for i, v in zip(_np(ids).reshape(-1), _np(st).reshape(-1)) if v]

@@ -761,11 +761,118 @@ def coco_box_iou(dt, dt_counts, gt, gt_counts, iscrowd, out=None):
     return out
 
 
+def _coco_rows_out(what, B, top_n, xywh, area, score, cat):
+    for t, name, dt, n in ((xywh, "xywh", torch.float64, 4), (area, "area", torch.float64, 1), (score, "score", torch.float32, 1),
+                           (cat, "cat", torch.int32, 1)):
+        _req(t, name, dt)
+        if t.numel() != B * top_n * n:
+            raise ValueError(f"{what}: {name} must hold [B, top_n{', 4' if n == 4 else ''}]")
+
+
+def coco_kp_rows(detections, detection_counts, keypoints, K, xywh, area, score, cat):
+    """coco_det_rows for keypoint results: detections float32 [B, top_n, 7] give score and class, keypoints float32 [B, top_n, Kp, 3]
+    the box and area (include/scda_ops.h: scda_coco_kp_rows_hip)"""
+    _req(detections, "detections"); _req(detection_counts, "detection_counts", torch.int32); _req(keypoints, "keypoints")
+    if detections.dim() != 3 or detections.shape[2] != 7 or detection_counts.numel() != detections.shape[0]:
+        raise ValueError("coco_kp_rows: detections [B, top_n, 7] and detection_counts [B]")
+    B, top_n = detections.shape[:2]
+    if keypoints.dim() != 4 or tuple(keypoints.shape[:2]) != (B, top_n) or keypoints.shape[3] != 3 or not 1 <= keypoints.shape[2] <= 32:
+        raise ValueError("coco_kp_rows: keypoints [B, top_n, Kp, 3], 1 <= Kp <= 32")
+    _coco_rows_out("coco_kp_rows", B, top_n, xywh, area, score, cat)
+    _check(lib().scda_coco_kp_rows_hip(_p(detections), _p(detection_counts), B, top_n, _p(keypoints), int(keypoints.shape[2]), int(K),
+                                       _p(xywh), _p(area), _p(score), _p(cat), _stream()), "scda_coco_kp_rows_hip")
+
+
+def coco_prop_rows(proposals, proposal_counts, xywh, area, score, cat, xyxy_as_xywh=False):
+    """coco_det_rows from proposals float32 [B, P, 6] = (b, x1, y1, x2, y2, score) + proposal_counts int32 [B], category 1
+    (include/scda_ops.h: scda_coco_prop_rows_hip); xyxy_as_xywh: the reference's 'proposal' rows, (x2, y2) taken as (w, h)"""
+    _req(proposals, "proposals"); _req(proposal_counts, "proposal_counts", torch.int32)
+    if proposals.dim() != 3 or proposals.shape[2] != 6 or proposal_counts.numel() != proposals.shape[0]:
+        raise ValueError("coco_prop_rows: proposals [B, P, 6] and proposal_counts [B]")
+    B, P = proposals.shape[:2]
+    _coco_rows_out("coco_prop_rows", B, P, xywh, area, score, cat)
+    _check(lib().scda_coco_prop_rows_hip(_p(proposals), _p(proposal_counts), B, P, int(bool(xyxy_as_xywh)), _p(xywh), _p(area), _p(score),
+                                         _p(cat), _stream()), "scda_coco_prop_rows_hip")
+
+
+def coco_oks(dt_keypoints, dt_counts, gt_keypoints, gt_boxes, gt_areas, gt_counts, vars_, out=None, gt_iscrowd=None,
+             gt_num_keypoints=None, gt_ignore=None):
+    """computeOks for B images: dt_keypoints float32 [B, D, Kp, 3], gt_keypoints float64 [B, G, Kp, 3], gt_boxes float64 [B, G, 4],
+    gt_areas float64 [B, G], counts int32 [B], vars_ float64 [Kp] -> oks float64 [B, G, D], written where d < dt_counts[b] and
+    g < gt_counts[b]; a fresh `out` is zero elsewhere.  gt_ignore uint8 [B, G] (with gt_iscrowd uint8 and gt_num_keypoints int32 [B, G]):
+    also iscrowd || num_keypoints == 0 per live GT (include/scda_ops.h: scda_coco_oks_hip)"""
+    _req(dt_keypoints, "dt_keypoints"); _req(gt_keypoints, "gt_keypoints", torch.float64); _req(gt_boxes, "gt_boxes", torch.float64)
+    _req(gt_areas, "gt_areas", torch.float64); _req(vars_, "vars", torch.float64)
+    _req(dt_counts, "dt_counts", torch.int32); _req(gt_counts, "gt_counts", torch.int32)
+    if dt_keypoints.dim() != 4 or gt_keypoints.dim() != 4 or dt_keypoints.shape[3] != 3 or gt_keypoints.shape[3] != 3 or \
+            gt_keypoints.shape[0] != dt_keypoints.shape[0] or gt_keypoints.shape[2] != dt_keypoints.shape[2]:
+        raise ValueError("coco_oks: dt_keypoints [B, D, Kp, 3] and gt_keypoints [B, G, Kp, 3]")
+    B, D, Kp = dt_keypoints.shape[:3]
+    G = gt_keypoints.shape[1]
+    if not (1 <= D <= 1024 and 1 <= G <= 1024 and 1 <= Kp <= 32):
+        raise ValueError("coco_oks: 1 <= D, G <= 1024, 1 <= Kp <= 32")
+    if gt_boxes.numel() != B * G * 4 or gt_areas.numel() != B * G or vars_.numel() != Kp or dt_counts.numel() != B or gt_counts.numel() != B:
+        raise ValueError("coco_oks: gt_boxes [B, G, 4], gt_areas [B, G], vars [Kp], counts [B]")
+    if gt_ignore is not None:
+        if gt_iscrowd is None or gt_num_keypoints is None:
+            raise ValueError("coco_oks: gt_ignore needs gt_iscrowd and gt_num_keypoints")
+        _req(gt_ignore, "gt_ignore", torch.uint8); _req(gt_iscrowd, "gt_iscrowd", torch.uint8)
+        _req(gt_num_keypoints, "gt_num_keypoints", torch.int32)
+        if gt_ignore.numel() < B * G or gt_iscrowd.numel() != B * G or gt_num_keypoints.numel() != B * G:
+            raise ValueError("coco_oks: gt_ignore, gt_iscrowd and gt_num_keypoints [B, G]")
+    if out is None:
+        out = torch.zeros(B, G, D, dtype=torch.float64, device=dt_keypoints.device)
+    _req(out, "out", torch.float64)
+    if out.numel() < B * G * D:
+        raise ValueError("coco_oks: out must hold [B, G, D]")
+    given = gt_ignore is not None
+    _check(lib().scda_coco_oks_hip(_p(dt_keypoints), _p(dt_counts), _p(gt_keypoints), _p(gt_boxes), _p(gt_areas), _p(gt_counts), _p(vars_),
+                                   Kp, _p(gt_iscrowd) if given else None, _p(gt_num_keypoints) if given else None, B, D, G, _p(out),
+                                   _p(gt_ignore), _stream()), "scda_coco_oks_hip")
+    return out
+
+
+def coco_regroup(K, dt_counts, in_xywh, in_area, in_score, in_cat, gt_counts, gt_cat, gt_area, gt_iscrowd, in_iou, xywh, area, score, cat,
+                 out_gt_area, out_gt_iscrowd, out_gt_cat, out_iou, perm_dets, perm_gts):
+    """the useCats = 0 order made physical (include/scda_ops.h: scda_coco_regroup_hip): rows and IoU block of B images regrouped by
+    (category ascending, given order); in_* [B, D(, 4)] and gt_* [B, G] are read, everything behind in_iou is written"""
+    B, D = in_cat.shape
+    G = gt_cat.shape[1]
+    _req_all("coco_regroup", ((dt_counts, "dt_counts", torch.int32, B), (in_xywh, "in_xywh", torch.float64, B * D * 4),
+                              (in_area, "in_area", torch.float64, B * D), (in_score, "in_score", torch.float32, B * D),
+                              (in_cat, "in_cat", torch.int32, B * D), (gt_counts, "gt_counts", torch.int32, B),
+                              (gt_cat, "gt_cat", torch.int32, B * G), (gt_area, "gt_area", torch.float64, B * G),
+                              (gt_iscrowd, "gt_iscrowd", torch.uint8, B * G), (in_iou, "in_iou", torch.float64, B * G * D),
+                              (xywh, "xywh", torch.float64, B * D * 4), (area, "area", torch.float64, B * D),
+                              (score, "score", torch.float32, B * D), (cat, "cat", torch.int32, B * D),
+                              (out_gt_area, "out_gt_area", torch.float64, B * G), (out_gt_iscrowd, "out_gt_iscrowd", torch.uint8, B * G),
+                              (out_gt_cat, "out_gt_cat", torch.int32, B * G), (out_iou, "out_iou", torch.float64, B * G * D),
+                              (perm_dets, "perm_dets", torch.int32, B * D), (perm_gts, "perm_gts", torch.int32, B * G)))
+    _check(lib().scda_coco_regroup_hip(B, D, G, int(K), _p(dt_counts), _p(in_xywh), _p(in_area), _p(in_score), _p(in_cat), _p(gt_counts),
+                                       _p(gt_cat), _p(gt_area), _p(gt_iscrowd), _p(in_iou), _p(xywh), _p(area), _p(score), _p(cat),
+                                       _p(out_gt_area), _p(out_gt_iscrowd), _p(out_gt_cat), _p(out_iou), _p(perm_dets), _p(perm_gts),
+                                       _stream()), "scda_coco_regroup_hip")
+
+
 def coco_match(iou, dt_counts, dt_cat, score, dt_area, gt_counts, gt_cat, gt_area, gt_iscrowd, K, iou_thrs, area_rng, max_det, rank, bits,
                npig, seen, dbg_match=None):
     """evaluateImg for B images (include/scda_ops.h: scda_coco_match_hip).  iou float64 [B, G, D]; dt_cat int32 / score float32 / dt_area
     float64 [B, D]; gt_cat int32 / gt_area float64 / gt_iscrowd uint8 [B, G]; iou_thrs float64 [T], area_rng float64 [A, 2] on the device
     -> rank int32 [B, D], bits int32 [B, D, A], and npig int32 [K, A], seen int32 [K] accumulated.  dbg_match int32 [B, D, A, T] or None."""
+    _coco_match(False, iou, dt_counts, dt_cat, score, dt_area, gt_counts, gt_cat, gt_area, gt_iscrowd, None, K, iou_thrs, area_rng, max_det,
+                rank, bits, npig, seen, dbg_match)
+
+
+def coco_match_ign(iou, dt_counts, dt_cat, score, dt_area, gt_counts, gt_cat, gt_area, gt_iscrowd, gt_ignore, K, iou_thrs, area_rng,
+                   max_det, rank, bits, npig, seen, dbg_match=None):
+    """coco_match with the GTs' ignore flags given apart from iscrowd (include/scda_ops.h: scda_coco_match_ign_hip): gt_ignore uint8
+    [B, G], or None for iscrowd -- then the results are coco_match's byte for byte"""
+    _coco_match(True, iou, dt_counts, dt_cat, score, dt_area, gt_counts, gt_cat, gt_area, gt_iscrowd, gt_ignore, K, iou_thrs, area_rng,
+                max_det, rank, bits, npig, seen, dbg_match)
+
+
+def _coco_match(ign, iou, dt_counts, dt_cat, score, dt_area, gt_counts, gt_cat, gt_area, gt_iscrowd, gt_ignore, K, iou_thrs, area_rng,
+                max_det, rank, bits, npig, seen, dbg_match):
     B, D = dt_cat.shape
     G = gt_cat.shape[1]
     T, A = iou_thrs.numel(), area_rng.shape[0]
@@ -776,7 +883,14 @@ def coco_match(iou, dt_counts, dt_cat, score, dt_area, gt_counts, gt_cat, gt_are
                             (gt_iscrowd, "gt_iscrowd", torch.uint8, B * G), (iou_thrs, "iou_thrs", torch.float64, T),
                             (area_rng, "area_rng", torch.float64, 2 * A), (rank, "rank", torch.int32, B * D),
                             (bits, "bits", torch.int32, B * D * A), (npig, "npig", torch.int32, K * A), (seen, "seen", torch.int32, K))
-             + (((dbg_match, "dbg_match", torch.int32, B * D * A * T),) if dbg_match is not None else ()))
+             + (((dbg_match, "dbg_match", torch.int32, B * D * A * T),) if dbg_match is not None else ())
+             + (((gt_ignore, "gt_ignore", torch.uint8, B * G),) if gt_ignore is not None else ()))
+    if ign:
+        _check(lib().scda_coco_match_ign_hip(_p(iou), B, D, G, _p(dt_counts), _p(dt_cat), _p(score), _p(dt_area), _p(gt_counts),
+                                             _p(gt_cat), _p(gt_area), _p(gt_iscrowd), _p(gt_ignore), int(K), _p(iou_thrs), T,
+                                             _p(area_rng), A, int(max_det), _p(rank), _p(bits), _p(npig), _p(seen), _p(dbg_match),
+                                             _stream()), "scda_coco_match_ign_hip")
+        return
     _check(lib().scda_coco_match_hip(_p(iou), B, D, G, _p(dt_counts), _p(dt_cat), _p(score), _p(dt_area), _p(gt_counts), _p(gt_cat),
                                      _p(gt_area), _p(gt_iscrowd), int(K), _p(iou_thrs), T, _p(area_rng), A, int(max_det), _p(rank),
                                      _p(bits), _p(npig), _p(seen), _p(dbg_match), _stream()), "scda_coco_match_hip")
