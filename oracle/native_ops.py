@@ -88,12 +88,19 @@ def roi_pool_bwd(top, arg, rois, feat_shape, ph, pw, scale):
     return g
 
 
-def roi_pool_bwd_scatter(top, arg, feat_shape, ph, pw):
+def roi_pool_bwd_scatter(top, arg, feat_shape, ph, pw, rois=None, scale=None):
+    """with rois and scale: the reference's backward (an argmax outside its RoI's rounded rectangle gets nothing), bit-identical to
+    roi_pool_bwd.  Without them: the plain argmax scatter, which adds such an argmax too (RoI extents 57, 114, 121, ...)."""
     top = _f32(top)
     arg = np.ascontiguousarray(arg, dtype=np.int32)
     B, C, H, W = feat_shape
     g = np.zeros((B, C, H, W), dtype=np.float32)
-    lib().orc_roi_pool_bwd_scatter(_p(top), _p(arg), I(top.shape[0]), I(B), I(C), I(H), I(W), I(ph), I(pw), _p(g))
+    if rois is None:
+        lib().orc_roi_pool_bwd_scatter(_p(top), _p(arg), I(top.shape[0]), I(B), I(C), I(H), I(W), I(ph), I(pw), _p(g))
+        return g
+    rois = _f32(rois)
+    lib().orc_roi_pool_bwd_scatter_gated(_p(top), _p(arg), _p(rois), I(rois.shape[0]), I(B), I(C), I(H), I(W), I(ph), I(pw),
+                                         F(scale), _p(g))
     return g
 
 

@@ -228,13 +228,33 @@ ORC_API int orc_roi_pool_bwd(const float *top_diff, const int32_t *argmax, const
 /* Scatter form of the same backward: walking the outputs in (roi, c, ph, pw) order and adding top_diff into
  * bottom_diff[argmax] visits, for every input element, its contributors in (roi, ph, pw) order -- the gather
  * kernel's order -- so the fp32 sums are bit-identical (asserted in tests/test_oracle_golden.py) at 1/1000 of the
- * cost.  Used by the model-level oracle / CPU baseline.                                                        */
+ * cost.  This entry point takes no RoIs and adds EVERY argmax; it equals the gather only where no argmax lies outside
+ * its RoI's rectangle (see the gated form below, which is what the model-level oracle / CPU baseline use).          */
 ORC_API int orc_roi_pool_bwd_scatter(const float *top_diff, const int32_t *argmax, int R, int B, int C, int H, int W,
                                      int PH, int PW, float *bottom_diff) {
     memset(bottom_diff, 0, (size_t)B * C * H * W * sizeof(float));
     const size_t total = (size_t)R * C * PH * PW;
     for (size_t i = 0; i < total; ++i)
         if (argmax[i] >= 0) bottom_diff[argmax[i]] += top_diff[i];
+    return 1;
+}
+
+/* The scatter form with the reference's `in_roi` gate: the gather only visits RoIs whose rounded rectangle holds the
+ * pixel (:161-166), while the forward's last bin can end one pixel past it (ceil(7 * fl(57 / 7)) = 58): such an argmax
+ * gets no gradient there, so none here.  Bit-identical to orc_roi_pool_bwd on every input.                         */
+ORC_API int orc_roi_pool_bwd_scatter_gated(const float *top_diff, const int32_t *argmax, const float *rois, int R, int B, int C,
+                                           int H, int W, int PH, int PW, float scale, float *bottom_diff) {
+    memset(bottom_diff, 0, (size_t)B * C * H * W * sizeof(float));
+    const size_t per_roi = (size_t)C * PH * PW;
+    for (int r = 0; r < R; ++r) {
+        int b, sw, sh, ew, eh;
+        orc_roi_rect(rois + (size_t)r * 5, scale, &b, &sw, &sh, &ew, &eh);
+        for (size_t i = (size_t)r * per_roi; i < (size_t)(r + 1) * per_roi; ++i) {
+            if (argmax[i] < 0) continue;
+            const int w = argmax[i] % W, h = (argmax[i] / W) % H;
+            if (w >= sw && w <= ew && h >= sh && h <= eh) bottom_diff[argmax[i]] += top_diff[i];
+        }
+    }
     return 1;
 }
 
@@ -398,7 +418,10 @@ ORC_API int orc_focal_softmax_bwd(int N, const float *logits, const int32_t *tar
         if (label >= 0) {
             float onemp = (float)(1. - (double)priors[base + label]);
             float p = priors[base + label];
-            b = (-powf(onemp, gamma) + gamma * powf(onemp, gamma - 1) * p * logf(fmaxf(p, FLT_MIN))) * z;
+            /* at p == 1 the reference's second term is gamma * 0^(gamma - 1) * 0: 0 for gamma >= 1, NaN below; its limit, 0, is used */
+            float lg = logf(fmaxf(p, FLT_MIN));
+            float second = lg == 0.f ? 0.f : gamma * powf(onemp, gamma - 1) * p * lg;
+            b = (-powf(onemp, gamma) + second) * z;
         }
         buff[r] = b;
     }

@@ -504,8 +504,12 @@ __global__ __launch_bounds__(256) void roi_pool_bwd_kernel(const float *__restri
 // adds them into the plane.  Bins of one RoI can share a pixel (floor/ceil bin edges overlap; tiny RoIs collapse onto one
 // pixel), and fp32 addition order matters, so equal targets are serialised lowest-bin-first: every pending lane posts its
 // lane id with an LDS atomicMin on a tag word of its pixel, the lane that finds its own id there adds and retires, the
-// rest go round again (1 round unless bins collide).  No window tests, no divisions, argmax/top read exactly once
-// (~100 MB for 512 RoIs x 512 channels); bit-identical to the gather kernel above, which remains the fallback.
+// rest go round again (1 round unless bins collide).  No divisions per bin edge, argmax/top read exactly once
+// (~100 MB for 512 RoIs x 512 channels).  The gather kernel above remains the fallback.
+// The reference's gather (roi_pooling_kernel.cu:161-166) only looks at RoIs whose rounded rectangle [sw..ew] x [sh..eh] holds the
+// pixel, and the forward's last bin can end one pixel PAST that rectangle (fl(roi / 7) * 7 rounds up for extents 57, 114, 121, 228,
+// ...): an argmax there gets no gradient in the reference.  The same gate is applied here when a RoI is staged, which is what
+// makes this form bit-identical to the gather kernel (tests/test_roi_edges_gpu.py sweeps the extents).
 constexpr int kScatterBands = 8;   // waves per plane
 constexpr int kScatterChunk = 32;  // RoIs staged per step
 
@@ -516,7 +520,8 @@ __global__ __launch_bounds__(64 * kScatterBands) void roi_pool_bwd_scatter_kerne
                                                                                  const int32_t *__restrict__ argmax,
                                                                                  const float *__restrict__ rois, const int R,
                                                                                  const int C, const int HW, const int bins,
-                                                                                 float *__restrict__ bottom) {
+                                                                                 float *__restrict__ bottom, const float scale,
+                                                                                 const int W) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int p = blockIdx.x;                   // plane = n * C + c
@@ -541,10 +546,17 @@ __global__ __launch_bounds__(64 * kScatterBands) void roi_pool_bwd_scatter_kerne
             const int e = tid + k * 64 * kScatterBands, r = r0 + (e >> 6), l = e & 63;
             ra[k] = -1;
             rg[k] = 0.f;
-            if (r < R && l < bins && (int)rois[(size_t)r * 5] == n) {
-                const size_t o = ((size_t)r * C + c) * bins + l;
-                const int a = argmax[o];
-                if (a >= 0) { ra[k] = a - pbase; rg[k] = top[o]; }
+            if (r < R && l < bins) {
+                // r is the same in all 64 lanes (e >> 6): one rectangle per staged RoI, not per bin
+                const RoiRect q = roi_rect(rois + (size_t)r * 5, scale);
+                if (q.b == n) {
+                    const size_t o = ((size_t)r * C + c) * bins + l;
+                    const int a = argmax[o] - pbase;
+                    if (a >= 0) {      // (-1 = empty bin; argmax of a RoI of image n lies in plane p)
+                        const int h = a / W, w = a - h * W;
+                        if (w >= q.sw && w <= q.ew && h >= q.sh && h <= q.eh) { ra[k] = a; rg[k] = top[o]; }
+                    }
+                }
             }
         }
     };
@@ -801,7 +813,12 @@ __global__ __launch_bounds__(256) void focal_softmax_bwd_weight_kernel(const int
         if (label >= 0) {
             const float onemp = (float)(1. - (double)P[base + label]);
             const float p = P[base + label];
-            b = (-powf(onemp, gamma) + gamma * powf(onemp, gamma - 1) * p * logf(fmaxf(p, FLT_MIN))) * z;
+            // p == 1 (logf == 0, onemp == 0): the second term is gamma * 0^(gamma - 1) * 0, i.e. 0 * inf = NaN for gamma < 1 (a softmax
+            // rounds to exactly 1 in fp32 from a logit gap of about 17; with one class always).  Its limit is 0, which is also what
+            // the expression gives for every gamma >= 1: same bits wherever the reference's value is a number.
+            const float lg = logf(fmaxf(p, FLT_MIN));
+            const float second = lg == 0.f ? 0.f : gamma * powf(onemp, gamma - 1) * p * lg;
+            b = (-powf(onemp, gamma) + second) * z;
         }
         buff[r] = b;
     }
@@ -1018,7 +1035,7 @@ SCDA_API int scda_roi_pool_bwd_hip(const float *top_grad, const int32_t *argmax,
     if (!big_lds_ok) (void)hipGetLastError();
     if (PH * PW <= 64 && scatter_lds <= (big_lds_ok ? 96 : 64) * (size_t)1024) {
         hipLaunchKernelGGL(roi_pool_bwd_scatter_kernel, dim3(B * C), dim3(64 * kScatterBands), scatter_lds, as_stream(stream),
-                           top_grad, argmax, rois, R, C, H * W, PH * PW, bottom_grad);
+                           top_grad, argmax, rois, R, C, H * W, PH * PW, bottom_grad, spatial_scale, W);
         return launch_status("roi_pool_bwd_scatter_kernel");
     }
     const size_t lds = (size_t)R * 5 * sizeof(int);
@@ -1032,6 +1049,7 @@ SCDA_API int scda_roi_pool_bwd_hip(const float *top_grad, const int32_t *argmax,
 static int roi_align_fwd_impl(const float *features, const float *rois, int R, int B, int C, int H, int W, int AH,
                               int AW, float spatial_scale, float *out, void *stream, int cmajor) {
     if (R < 0 || B <= 0 || C <= 0 || H <= 1 || W <= 1 || AH <= 1 || AW <= 1) { set_error("scda_roi_align_fwd_hip: bad shape"); return SCDA_EINVAL; }
+    if ((long long)B * C * H * W > 0x7fffffffLL) { set_error("scda_roi_align_fwd_hip: features exceed int32 indexing"); return SCDA_EINVAL; }
     if (R == 0) return SCDA_OK;
     if (!features || !rois || !out) { set_error("scda_roi_align_fwd_hip: null pointer"); return SCDA_EINVAL; }
     const long long total = (long long)R * C * AH * AW;
@@ -1053,6 +1071,7 @@ SCDA_API int scda_roi_align_cmajor_fwd_hip(const float *features, const float *r
 static int roi_align_bwd_impl(const float *top_grad, const float *rois, int R, int B, int C, int H, int W, int AH,
                               int AW, float spatial_scale, float *bottom_grad, void *stream, int cmajor) {
     if (R < 0 || B <= 0 || C <= 0 || H <= 1 || W <= 1 || AH <= 1 || AW <= 1) { set_error("scda_roi_align_bwd_hip: bad shape"); return SCDA_EINVAL; }
+    if ((long long)B * C * H * W > 0x7fffffffLL) { set_error("scda_roi_align_bwd_hip: features exceed int32 indexing"); return SCDA_EINVAL; }
     if (R == 0) return SCDA_OK;
     if (!top_grad || !rois || !bottom_grad) { set_error("scda_roi_align_bwd_hip: null pointer"); return SCDA_EINVAL; }
     const long long total = (long long)R * C * AH * AW;

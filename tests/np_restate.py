@@ -58,19 +58,32 @@ def roi_pool(feat, rois, PH, PW, scale):
                 if he <= hs or we <= ws:
                     continue
                 win = feat[b, :, hs:he, ws:we].reshape(C, -1)
+                # the scan keeps an element only if it is > the running maximum, which starts at -FLT_MAX: a NaN, -inf or -FLT_MAX
+                # never wins, and a window of nothing else yields (-FLT_MAX, -1)
+                lowest = np.finfo(f32).min
+                with np.errstate(invalid="ignore"):
+                    win = np.where(win > lowest, win, lowest)
                 k = win.argmax(1)  # first max in row-major scan order
-                out[n, :, ph, pw] = win[np.arange(C), k]
+                val = win[np.arange(C), k]
+                out[n, :, ph, pw] = val
                 hh, ww = hs + k // (we - ws), ws + k % (we - ws)
-                arg[n, :, ph, pw] = ((b * C + np.arange(C)) * H + hh) * W + ww
+                arg[n, :, ph, pw] = np.where(val > lowest, ((b * C + np.arange(C)) * H + hh) * W + ww, -1)
     return out, arg
 
 
-def roi_pool_bwd_scatter(top, arg, feat_shape):
-    """scatter in (roi, c, ph, pw) order == the reference's per-element (roi, ph, pw) order"""
+def roi_pool_bwd_scatter(top, arg, feat_shape, rois=None, scale=None):
+    """scatter in (roi, c, ph, pw) order == the reference's per-element (roi, ph, pw) order; with rois and scale, like the
+    reference's gather (roi_pooling_kernel.cu:161-166), an argmax outside its RoI's rounded rectangle receives nothing"""
+    B, C, H, W = feat_shape
     g = np.zeros(int(np.prod(feat_shape)), f32)
+    per_roi = arg[0].size if len(arg) else 0
     a = arg.reshape(-1)
     t = top.reshape(-1).astype(f32)
+    rect = None if rois is None else [[int(v) for v in round_half_away((r[1:5].astype(f32) * f32(scale)).astype(f32))] for r in rois]
     # sequential fp32 accumulation in index order
     for i in np.nonzero(a >= 0)[0]:
-        g[a[i]] = f32(g[a[i]] + t[i])
+        sw, sh, ew, eh = rect[i // per_roi] if rect is not None else (0, 0, W, H)
+        h, w = (a[i] // W) % H, a[i] % W
+        if sw <= w <= ew and sh <= h <= eh:
+            g[a[i]] = f32(g[a[i]] + t[i])
     return g.reshape(feat_shape)

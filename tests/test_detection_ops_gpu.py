@@ -5,6 +5,7 @@ import pytest
 import torch
 
 from oracle import native_ops as orc
+from roi_refs import roi_align as _roi_align_third_statement
 from test_oracle_golden import rand_boxes, rand_rois
 
 pytestmark = pytest.mark.gpu
@@ -133,7 +134,7 @@ def test_roi_pool_fwd_bwd_bit_exact(cuda, shape, R):
     g = native.roi_pool_bwd(dev(top, cuda), arg, dev(rois, cuda), shape, 7, 7, 1 / 16.).cpu().numpy()
     # every channel, bit for bit.  The scatter form of the oracle sums each input element's contributors in the gather kernel's
     # (roi, ph, pw) order (proved bit-identical to the O(B*C*H*W*R) gather restatement in test_oracle_golden.py) at 1/1000 the cost.
-    np.testing.assert_array_equal(g, orc.roi_pool_bwd_scatter(top, ea, shape, 7, 7))
+    np.testing.assert_array_equal(g, orc.roi_pool_bwd_scatter(top, ea, shape, 7, 7, rois, 1 / 16.))
     if C * R <= 4096:
         np.testing.assert_array_equal(g, orc.roi_pool_bwd(top, ea, rois, shape, 7, 7, 1 / 16.))
 
@@ -159,7 +160,7 @@ def test_roi_pool_bwd_on_shared_maxima(cuda, step):
         assert shared > R * C, shared          # the case under test occurs: more than one shared maximum per (RoI, channel) on average
         top = rs.randn(*eo.shape).astype(np.float32)
         g = native.roi_pool_bwd(dev(top, cuda), dev(ea, cuda), dev(rois, cuda), shape, 7, 7, 1 / 16.).cpu().numpy()
-        np.testing.assert_array_equal(g, orc.roi_pool_bwd_scatter(top, ea, shape, 7, 7))
+        np.testing.assert_array_equal(g, orc.roi_pool_bwd_scatter(top, ea, shape, 7, 7, rois, 1 / 16.))
 
 
 def test_roi_pool_equals_reference_roi_pool_py(cuda, golden_dir):
@@ -175,7 +176,7 @@ def test_roi_pool_equals_reference_roi_pool_py(cuda, golden_dir):
         check_argmax_first_max(feat, rois, o, a, PH, PW, scale, every=16 if feat.shape[1] > 64 else 1)
         top = np.random.RandomState(3).standard_normal(o.shape).astype(np.float32)
         g = native.roi_pool_bwd(dev(top, cuda), arg, dev(rois, cuda), feat.shape, PH, PW, scale).cpu().numpy()
-        np.testing.assert_array_equal(g, orc.roi_pool_bwd_scatter(top, a, feat.shape, PH, PW), err_msg=name)
+        np.testing.assert_array_equal(g, orc.roi_pool_bwd_scatter(top, a, feat.shape, PH, PW, rois, scale), err_msg=name)
 
 
 def test_roi_pool_empty_rois(cuda):
@@ -201,50 +202,6 @@ def test_roi_align_fwd_bwd(cuda):
     eg = orc.roi_align_bwd(top, rois, shape, 8, 8, 1 / 16.)
     g = native.roi_align_bwd(dev(top, cuda), dev(rois, cuda), shape, 8, 8, 1 / 16.)
     np.testing.assert_allclose(g.cpu().numpy(), eg, rtol=1e-5, atol=1e-5)  # atomics: order differs
-
-
-def _roi_align_third_statement(feat, rois, AH, AW, scale, top=None):
-    """A THIRD, independent statement of extensions/_roi_align/src/roi_align_kernel.cu:15-70 (forward) and :94-143 (backward), written
-    from the kernel text by flat-index arithmetic only -- it shares no helper with oracle/scda_oracle.c or tests/np_restate.py.  Sample
-    geometry in float32 exactly as the kernel's float variables hold it (the `1.` literals make the divisions double, the results are
-    stored to float), interpolation in float64.  -> out [R, C, AH, AW] (float64), and with `top` the gradient [B, C, H, W]."""
-    B, C, H, W = feat.shape
-    R = rois.shape[0]
-    f32 = np.float32
-    r = rois.astype(f32)
-    sc = f32(scale)
-    x1, y1, x2, y2 = (r[:, 1] * sc).astype(f32), (r[:, 2] * sc).astype(f32), (r[:, 3] * sc).astype(f32), (r[:, 4] * sc).astype(f32)
-    rw = np.maximum((x2 - x1).astype(np.float64) + 1.0, 0.0).astype(f32)          # fmaxf(roi_end_w - roi_start_w + 1., 0.)
-    rh = np.maximum((y2 - y1).astype(np.float64) + 1.0, 0.0).astype(f32)
-    bh = (rh.astype(np.float64) / (AH - 1.0)).astype(f32)                          # roi_height / (aligned_height - 1.)
-    bw = (rw.astype(np.float64) / (AW - 1.0)).astype(f32)
-    ph = np.arange(AH, dtype=f32)[None, :]
-    pw = np.arange(AW, dtype=f32)[None, :]
-    h = (ph * bh[:, None] + y1[:, None]).astype(f32)                               # [R, AH]   (float)(ph) * bin_size_h + roi_start_h
-    w = (pw * bw[:, None] + x1[:, None]).astype(f32)                               # [R, AW]
-    hs = np.minimum(np.floor(h), f32(H - 2)).astype(np.int64)                      # fminf(floor(h), height - 2)
-    ws = np.minimum(np.floor(w), f32(W - 2)).astype(np.int64)
-    inside = ~((h < 0) | (h >= H))[:, :, None] & ~((w < 0) | (w >= W))[:, None, :] # [R, AH, AW]
-    hr = (h - hs.astype(f32)).astype(f32).astype(np.float64)[:, :, None]           # h_ratio (float), used in double arithmetic
-    wr = (w - ws.astype(f32)).astype(f32).astype(np.float64)[:, None, :]
-    img = r[:, 0].astype(np.int64)
-    base = img[:, None, None] * (C * H * W) + np.where(inside, hs[:, :, None] * W + ws[:, None, :], 0)   # channel 0's up-left corner
-    flat = feat.astype(np.float64).reshape(-1)
-    coef = [(1.0 - hr) * (1.0 - wr), (1.0 - hr) * wr, hr * (1.0 - wr), hr * wr]
-    offs = [0, 1, W, W + 1]
-    chan = (np.arange(C, dtype=np.int64) * (H * W))[None, :, None, None]
-    idx0 = base[:, None, :, :] + chan                                               # [R, C, AH, AW]
-    out = np.zeros((R, C, AH, AW))
-    for cf, o in zip(coef, offs):
-        out += flat[idx0 + o] * cf[:, None, :, :]
-    out *= inside[:, None, :, :]
-    if top is None:
-        return out
-    grad = np.zeros(B * C * H * W)
-    t = top.astype(np.float64) * inside[:, None, :, :]
-    for cf, o in zip(coef, offs):
-        np.add.at(grad, (idx0 + o).reshape(-1), (t * cf[:, None, :, :]).reshape(-1))
-    return out, grad.reshape(B, C, H, W)
 
 
 def test_roi_align_unpinned_third_independent_statement(cuda):
