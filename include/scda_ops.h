@@ -215,6 +215,50 @@ int scda_proposal_finalize_hip(const float *cand_rois, const int *sel, const int
                                int gt_stride, int R, int num_classes, float image_index, float *rois5, long long *labels,
                                float *loc_targets, float *loc_weights, void *stream);
 
+/* ------------------------------------------- cluster-region generator (cluster_ops.hip) ---- */
+/* functions/mask.py:183-237 with the k-means on the device.  The rule restated is scikit-learn 1.7.2's
+ * KMeans(n_clusters=k, random_state=0).fit with its defaults (init 'k-means++', n_init 'auto' = 1 run, max_iter 300, tol 1e-4,
+ * Lloyd); the device path does not depend on the scikit-learn the process would import.
+ *   1. points     X[i] = ((x2 + x1) / 2, (y2 + y1) / 2) in float32 from the RoI rows (b, x1, y1, x2, y2, ...), stride roi_stride
+ *   2. tolerance  tol_abs = 1e-4 * mean(var(X, axis=0))
+ *   3. centring   mean = X.mean(axis=0) (rounded to float32); all work is on Xc = X - mean (a float32 subtraction);
+ *                 centres out = float32(centre) + mean, a float32 addition
+ *   4. seeding    (_kmeans_plusplus) every draw comes from ONE np.random.RandomState(0) that KMeans re-creates per fit, so the draws
+ *                 are constants of (N, k): first_index = searchsorted(cdf, random_sample(), side='right') with cdf the normalised
+ *                 float64 cumsum of p = 1/N, then t = trials = 2 + int(ln k) uniforms per further centre: uniforms_host [k-1][t]
+ *                 (a HOST array, passed on as kernel arguments).  closest = squared distance to the nearest chosen seed, pot = sum
+ *                 of closest; the t candidates of a round are searchsorted(cumsum(closest), u * pot) (side 'left'), clipped to N - 1,
+ *                 the cumsum sequential and float64 (stable_cumsum); the candidate whose min(closest, distance to it) sums to the
+ *                 lowest potential wins, the first one on a tie
+ *   5. Lloyd      label = the first minimum of the squared distance to each centre; each centre becomes the mean of its members;
+ *                 after that: labels equal to the iteration before's -> stop (strict convergence: the means just computed are
+ *                 returned, no further E-step); else sum_c |shift_c|^2 <= tol_abs -> stop and run one E-step against the final
+ *                 centres; else stop after 300 iterations (and run that E-step).  n_iter counts iterations as sklearn's n_iter_
+ *   6. a cluster that goes empty during Lloyd is NOT relocated as sklearn does: status bit 0 is raised and the caller takes the
+ *      host path for that call (also when a cluster is empty after the final E-step, where the reference raises)
+ *   7. members    row c of members [k,N] = the indices of cluster c ascending, then -1; counts [k] their numbers.  The caller
+ *                 takes the first `threshold` of a row, or draws np.random.choice(count, threshold, replace=True) from numpy's
+ *                 GLOBAL generator on the host (the reference's observable behaviour) and passes the picks to the gather.
+ * Arithmetic: float64 on the float32 centred points, direct squared distances dx * dx + dy * dy, one IEEE operation per operator.
+ * Every sum has a fixed order (lane l of one wave adds elements l, l + 64, ... in turn, then an xor butterfly over 32, 16, ... 1),
+ * no floating-point atomics: two runs are bit-identical.  ONE launch of ONE workgroup; nothing is allocated, the host is not
+ * waited for.  Capacity: N <= scda_kmeans_capacity() (1024) points, k <= 8, k <= N.
+ * Outputs (the caller's): centres f32 [k,2], labels i32 [N], counts i32 [k], members i32 [k,N], seed_index i32 [k], n_iter i32 [1],
+ * status i32 [1]: 0 ok; bit 0 = a cluster went empty; bit 1 = bad arguments or over capacity (only status and n_iter = 0 are
+ * written).  Bit 0 has two cases, told apart by n_iter: a cluster went empty DURING Lloyd -> the run ends there, only counts = 0
+ * (all k), n_iter = 0 and status are written and the other outputs keep what they held; a cluster is empty only AFTER the final
+ * E-step -> every output is written and valid (labels, the real counts with a 0 among them, members, seed_index, centres,
+ * n_iter >= 1), the flag says that the reference would raise on the empty cluster. */
+int scda_kmeans_capacity(void);
+int scda_kmeans_hip(const float *rois, int roi_stride, int N, int k, int first_index, const double *uniforms_host, int trials,
+                    float *centres, int *labels, int *counts, int *members, int *seed_index, int *n_iter, int *status, void *stream);
+/* out [k, threshold, F] (contiguous): out[c, j, :] = feats[row(c, j), :] (feats [N,F] f32, row stride feat_stride elements) with
+ * row(c, j) = members[c][j] where counts[c] >= threshold, else members[c][picks[c][j]] (picks i32 [k, threshold], may be NULL when no
+ * cluster is short); bit-equal to the index_select it replaces.  A row without a valid source (an empty cluster, a pick outside
+ * [0, counts[c])) is filled with zeros.  16-byte accesses when F, feat_stride and both addresses allow it. */
+int scda_cluster_gather_hip(const float *feats, long long feat_stride, int N, int F, const int *members, const int *counts,
+                            const int *picks_or_null, int k, int threshold, float *out, void *stream);
+
 /* ------------------------------------------- batched inference (infer_ops.hip) ---- */
 /* The test-time half of the detector's box logic (functions/rpn_proposal.py with the test config, functions/predict_bbox.py:13-66)
  * for B images at once, with nothing copied to the host and nothing allocated: a fixed-shape batch can be captured into one graph.

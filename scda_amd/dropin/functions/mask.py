@@ -2,7 +2,8 @@
 the first `threshold` member RoIs (or a with-replacement resample when the cluster is smaller) are stacked into
 [N_cluster, threshold, F].  The k-means is sklearn's (third-party, as in the reference: KMeans(n_clusters,
 random_state=0)); what changes here is the data path: the RoI features never leave the MI355X -- only the 512 RoI
-boxes (already on the host) feed the clustering, and the gather runs on the device.
+boxes (already on the host) feed the clustering, and the gather runs on the device.  Opt-in (SCDA_DEVICE_KMEANS=1): the k-means
+runs on the device too, as a restatement of scikit-learn 1.7.2's rule (scda_amd/device_clusters.py).
 
 As in the reference the result is a NEW leaf tensor: no gradient flows back into the detector through it
 (functions/mask.py:202-203,234 round-trip through numpy)."""
@@ -64,7 +65,17 @@ def cluster_indices(proposals_np, N_cluster=4, threshold=128):
 
 
 def compute_cluster_targets(proposals, features, N_cluster=4, threshold=128):
-    """proposals [N,>=5], features [N,F] -> (cluster features [N_cluster, threshold, F] (leaf), centres [N_cluster,2])"""
+    """proposals [N,>=5], features [N,F] -> (cluster features [N_cluster, threshold, F] (leaf), centres [N_cluster,2]).
+    SCDA_DEVICE_KMEANS=1 (default off) runs the k-means and the gather as HIP kernels (scda_amd/device_clusters.py, a restatement of
+    scikit-learn 1.7.2's rule); anything it does not cover comes back to `host_cluster_targets`."""
+    from scda_amd import device_clusters
+    if device_clusters.enabled():
+        return device_clusters.cluster_targets(proposals, features, N_cluster, threshold)
+    return host_cluster_targets(proposals, features, N_cluster, threshold)
+
+
+def host_cluster_targets(proposals, features, N_cluster=4, threshold=128):
+    """the host path: sklearn's k-means on the host copy of the RoIs, the gather by index_select"""
     idx, centres = cluster_indices(_np(proposals), N_cluster, threshold)
     if features.is_cuda:
         from scda_amd import native

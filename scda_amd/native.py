@@ -344,6 +344,59 @@ def proposal_finalize(cand_rois, sel, gt_of, enc, gts, num_classes, image_index)
     return rois, labels, t, w
 
 
+# ------------------------------------- cluster-region generator (cluster_ops.hip) ----
+def kmeans_capacity():
+    """most points one scda_kmeans_hip launch clusters (k <= 8)"""
+    return lib().scda_kmeans_capacity()
+
+
+def kmeans(rois, k, first_index, uniforms, bufs):
+    """rois [N, >=5] fp32 rows (b, x1, y1, x2, y2, ..) on the device; first_index / uniforms: the seeding constants of (N, k) (a ctypes
+    double array [k-1][t], or None for k = 1); bufs: caller-owned device buffers centres f32 [k,2], labels i32 [N], counts i32 [k],
+    members i32 [k,N], seed_index i32 [k], n_iter i32 [1], status i32 [1] (scda_kmeans_hip: the rule is stated in include/scda_ops.h).
+    One launch on the current stream; the caller reads status."""
+    _req(rois, "rois")
+    if rois.dim() != 2 or rois.shape[1] < 5 or k < 1:
+        raise ValueError("kmeans: rois must be [N, >=5] and k >= 1")
+    N = rois.shape[0]
+    i32 = torch.int32
+    _req_all("kmeans", ((bufs["centres"], "centres", torch.float32, 2 * k), (bufs["labels"], "labels", i32, N), (bufs["counts"], "counts", i32, k),
+                        (bufs["members"], "members", i32, k * N), (bufs["seed_index"], "seed_index", i32, k), (bufs["n_iter"], "n_iter", i32, 1),
+                        (bufs["status"], "status", i32, 1)))
+    if any(b.device != rois.device for b in bufs.values()):
+        raise ValueError("kmeans: every buffer must live on the device of rois")
+    if k >= 2 and (uniforms is None or len(uniforms) < k - 1):
+        raise ValueError("kmeans: uniforms must hold [k-1][t] draws")
+    trials = 0 if uniforms is None or k < 2 else len(uniforms) // (k - 1)
+    _check(lib().scda_kmeans_hip(_p(rois), rois.shape[1], N, k, first_index, uniforms, max(trials, 1), _p(bufs["centres"]), _p(bufs["labels"]),
+                                 _p(bufs["counts"]), _p(bufs["members"]), _p(bufs["seed_index"]), _p(bufs["n_iter"]), _p(bufs["status"]),
+                                 _stream()), "scda_kmeans_hip")
+
+
+def cluster_gather(feats, members, counts, picks, k, threshold, out=None):
+    """feats [N,F] fp32 (rows may be strided), members i32 [k,N], counts i32 [k], picks i32 [k, threshold] or None
+    -> out fp32 [k, threshold, F]: the rows the cluster-region generator selects (scda_cluster_gather_hip)"""
+    if not (isinstance(feats, torch.Tensor) and feats.is_cuda and feats.dtype == torch.float32 and feats.dim() == 2 and feats.stride(1) == 1):
+        raise ScdaNativeError("cluster_gather: feats must be a float32 [N,F] tensor on the HIP device with contiguous rows")
+    _req(members, "members", torch.int32); _req(counts, "counts", torch.int32)
+    if picks is not None:
+        _req(picks, "picks", torch.int32)
+        if picks.numel() != k * threshold:
+            raise ValueError("cluster_gather: picks must be [k, threshold]")
+    N, F = feats.shape
+    if members.numel() != k * N or counts.numel() < k:
+        raise ValueError("cluster_gather: members must be [k, N] and counts [k]")
+    if out is None:
+        out = torch.empty(k, threshold, F, dtype=torch.float32, device=feats.device)
+    else:
+        _req(out, "out")
+        if out.numel() != k * threshold * F:
+            raise ValueError("cluster_gather: out must be [k, threshold, F]")
+    _check(lib().scda_cluster_gather_hip(_p(feats), feats.stride(0), N, F, _p(members), _p(counts), _p(picks), k, threshold, _p(out), _stream()),
+           "scda_cluster_gather_hip")
+    return out
+
+
 def proposals_from_ranking(order, exp_wh, anchors64, loc, prob, A, fh, fw, img_h, img_w, min_size, nms_thresh, max_keep, image_index):
     """order int32 [n], exp_wh f32 [n,2] (device) -> (out6 fp32 [rows,6], num int64 [1]) on the device: decode + clip + size test,
     NMS, gather"""
