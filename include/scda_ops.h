@@ -385,6 +385,34 @@ int scda_mask_rescale_hip(const float *rois, int roi_stride, const int *cls_or_n
                           int W, const float *image_info, int info_stride, int masks_per_image, int Ho, int Wo, int packed,
                           float threshold, void *out, float *foot_rois, int *status, void *stream);
 
+/* ---- keypoints of the keypoint-branch detector (scda_amd/csrc/keypoint_ops.hip; opt-in: scda_amd.infer.Predictor(keypoints=True)) ----
+ * R x Kp heat maps -> one (x, y, score) row per RoI and keypoint, without writing any image-sized plane.
+ *
+ * PROVENANCE.  The reference's own heat-map -> keypoint code is in its missing models/mask_rcnn/mask_rcnn.py, so there is no reference
+ * keypoint decoder to restate: THE CHOICE OF THIS RULE IS OURS.  It is the one place where the reference takes a head's map to image
+ * coordinates, functions/mask.py:21-49 (predict_masks), followed by numpy's argmax, and its parity is pinned bit for bit to exactly
+ * that -- predict_masks + np.argmax (tests/golden/keypoints_ref.npz) --, not to a reference keypoint decoder.
+ *
+ * rois [R, roi_stride >= 5] float32 (b, x1, y1, x2, y2, ...); cls_or_null int32 [R] (< 0: a padding slot); heat float32
+ * [R, Kp, ph, pw] addressed by ELEMENT strides (NCHW, or the transposed tall channel-major view of the keypoint head; all >= 0);
+ * (H, W): the batch's padded shape; out float32 [R, Kp, 3], every element written.  For RoI r and keypoint k:
+ *   1. x1, y1, x2, y2 = the float32 values truncated towards zero; roi_w = x2 - x1 + 1, roi_h = y2 - y1 + 1.  A coordinate that is not
+ *      finite or beyond +-5e8, roi_w <= 0 or roi_h <= 0, or cls[r] < 0 gives the row (0, 0, 0).
+ *   2. M [roi_h, roi_w] = heat[r, k] resized as scda_mask_paste_hip resizes a plane (Pillow >= 7, mode F, BICUBIC: a horizontal pass
+ *      into float32, then a vertical pass, a pass of equal sizes skipped; the axis rule stated there, bit for bit).
+ *   3. Only the window pixels with 0 <= x1 + px < W and 0 <= y1 + py < H count (as in the paste); none visible: the row (0, 0, 0).
+ *   4. (py, px) = the first maximum of the visible part in row-major order -- np.argmax: a NaN is a maximum, the first NaN wins;
+ *      +0.0 and -0.0 are equal.
+ *   5. the row is ((float)(x1 + px), (float)(y1 + py), M[py, px]): the third value is the raw resized map value (COCO's OKS ignores a
+ *      detection's third value; it is carried because write_results_to_file writes it).
+ * Limits: ph, pw <= 64 (the keypoint head gives 56; anything larger returns SCDA_EINVAL, nothing is clamped), R, Kp <= 65535,
+ * H * W < 2^31.  workspace: scda_keypoint_decode_workspace_bytes(R, Kp, W) bytes (one (value, position) pair per 128-column strip,
+ * keypoint and RoI), fully rewritten by every call.  Two launches, no atomics (two runs give the same bytes), graph-capturable. */
+size_t scda_keypoint_decode_workspace_bytes(int R, int Kp, int W);
+int scda_keypoint_decode_hip(const float *rois, int roi_stride, const int *cls_or_null, const float *heat, long long stride_r,
+                             long long stride_k, long long stride_h, long long stride_w, int R, int Kp, int ph, int pw, int H, int W,
+                             void *workspace, float *out, void *stream);
+
 /* ---- COCO run-length results from packed masks (scda_amd/csrc/mask_rle.hip; opt-in: scda_amd.infer.Predictor(masks=True, rle=True)) ----
  * The per-mask primitives of the reference's datasets/pycocotools/common/maskApi.c on scda_mask_paste_hip's packed planes, bit for bit
  * (integers below 2^32 and one IEEE double division; no atomics: two runs give the same bytes).  tests/mask_rle_np.py restates the

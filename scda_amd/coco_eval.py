@@ -10,10 +10,11 @@ Every test type of the reference's utils/coco_eval.py is covered:
   'proposal', 'person_proposal'      CocoEvaluator(K, 'bbox', use_cats=False, params={'max_dets': [1, 100, 1000]}): useCats = 0, fed
                                      the Predictor's proposals through add_proposals() or class rows through add()
   'keypoints'                        CocoEvaluator(K, 'keypoints', num_keypoints=17): computeOks, Params.setKpParams, _summarizeKps
-                                     (10 stats); the caller brings keypoint detections as device tensors (tests/coco_kps_np.py
-                                     restates the rules)
+                                     (10 stats); the keypoint detections come from infer.Predictor(keypoints=True) through
+                                     evaluate.coco_stats, or from the caller as device tensors (tests/coco_kps_np.py restates the
+                                     rules)
 
-NOT covered: the keypoint head (nothing produces keypoint detections here), useCats = 0 for keypoints (the reference then evaluates
+NOT covered: useCats = 0 for keypoints (the reference then evaluates
 nothing), the text / JSON round trip, annotation loading: ground truth arrives as device tensors
 (scda_amd.coco_gt.GroundTruth builds them, masks included, from annotation dicts).  Detections and ground truth must be in the SAME coordinates -- dividing the
 network-input detections by resize_scale (or scaling the ground truth) stays with the caller.  Image ids must be distinct.

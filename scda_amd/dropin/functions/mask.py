@@ -249,3 +249,56 @@ def predict_masks_device(rois, heatmap, image_info, out=None):
     cls = rois[:, 6].to(torch.int32)                                          # int() of the class column: towards zero
     planes = native.mask_select(heatmap.detach().float(), cls)
     return native.mask_paste(rois, planes, image_h, image_w, out=out)
+
+
+def predict_keypoints(rois, heatmap, image_info, cls=None):
+    """The host path of the keypoint decode.  rois [R, >=5] (b, x1, y1, x2, y2, ...), heatmap [R, Kp, h, w], image_info [B, >=2] ->
+    float32 [R, Kp, 3] rows (x, y, score).  The rule (include/scda_ops.h; the choice is OURS, the reference's own decoder is in its missing
+    models/mask_rcnn/mask_rcnn.py): each heat map resized to its RoI by PIL exactly as `predict_masks` (functions/mask.py:21-49) resizes a
+    class plane, then np.argmax over the part of the window inside the image -- the first maximum in row-major order, a NaN being a
+    maximum -- gives (x1 + px, y1 + py, the resized value there).  A coordinate that is not finite (or beyond +-5e8), an empty window, a
+    window wholly outside the image or a padding slot (cls[r] < 0, cls optional) gives (0, 0, 0)."""
+    from PIL import Image
+    rois, heatmap, image_info = (np.asarray(_np(v)) for v in (rois, heatmap, image_info))
+    assert rois.shape[0] == heatmap.shape[0]
+    cls = None if cls is None else np.asarray(_np(cls))
+    R, Kp = heatmap.shape[:2]
+    out = np.zeros((R, Kp, 3), dtype=np.float32)
+    for r_ix in range(R):
+        box = rois[r_ix][1:5].astype(np.float32)
+        if (cls is not None and cls[r_ix] < 0) or not (np.abs(box) < np.float32(5.0e8)).all():
+            continue
+        x1, y1, x2, y2 = map(int, box)
+        roi_w, roi_h = x2 - x1 + 1, y2 - y1 + 1
+        image_h, image_w = map(int, image_info[int(rois[r_ix][0])][:2])
+        xa, xb, ya, yb = max(x1, 0), min(x1 + roi_w, image_w), max(y1, 0), min(y1 + roi_h, image_h)
+        if roi_w <= 0 or roi_h <= 0 or xa >= xb or ya >= yb:
+            continue
+        for k in range(Kp):
+            plane = np.array(Image.fromarray(np.ascontiguousarray(heatmap[r_ix, k], dtype=np.float32)).resize((roi_w, roi_h)))
+            seen = plane[ya - y1:yb - y1, xa - x1:xb - x1]
+            py, px = np.unravel_index(np.argmax(seen), seen.shape)
+            out[r_ix, k] = (xa + px, ya + py, seen[py, px])
+    return out
+
+
+def predict_keypoints_device(rois, heatmap, image_info, cls=None, out=None):
+    """`predict_keypoints` on the device: rois [R, >=5] and heatmap [R, Kp, h, w] (h, w <= 64, any strided order) on the HIP device ->
+    float32 [R, Kp, 3] on the device, bit for bit the host path's rows (scda_amd/csrc/keypoint_ops.hip; no image-sized plane is written).
+    Pillow >= 7 only (the restated resize is its BICUBIC default), and all images of the call must share (image_h, image_w)."""
+    import PIL
+    from scda_amd import native
+    if int(PIL.__version__.split(".")[0]) < 7:
+        raise ValueError("device keypoint path: Pillow %s resizes with NEAREST by default; the device path restates Pillow >= 7's BICUBIC "
+                         "default -- use predict_keypoints" % PIL.__version__)
+    info = np.asarray(_np(image_info))
+    sizes = {(int(h), int(w)) for h, w in info[:, :2]}
+    if len(sizes) != 1:
+        raise ValueError("predict_keypoints_device: all images of a call must share (h, w), got %s" % sorted(sizes))
+    (image_h, image_w), = sizes
+    if not (torch.is_tensor(rois) and rois.is_cuda and torch.is_tensor(heatmap) and heatmap.is_cuda):
+        raise native.ScdaNativeError("predict_keypoints_device: rois and heatmap must live on the HIP device (predict_keypoints is the "
+                                     "host path)")
+    if heatmap.dim() != 4 or rois.shape[0] != heatmap.shape[0] or rois.shape[1] < 5:
+        raise ValueError("predict_keypoints_device: rois must be [R, >=5] and heatmap [R, Kp, h, w]")
+    return native.keypoint_decode(rois.detach().float().contiguous(), heatmap.detach().float(), image_h, image_w, cls=cls, out=out)

@@ -97,8 +97,11 @@ class ResNet(FasterRCNN_AdEx):
         self.avgpool = L.GlobalAvgPool()                                     # AvgPool2d(7) on 7x7 maps
         self.fc_rcnn_cls = L.Linear(512 * block.expansion, cfg['num_classes'])
         self.fc_rcnn_loc = L.Linear(512 * block.expansion, cfg['num_classes'] * 4)
-        if cfg.get('with_keypoint'):
-            raise NotImplementedError("the keypoint branch (:141-144) is not part of any BASELINE configuration")
+        self.with_keypoint = bool(cfg.get('with_keypoint'))
+        if self.with_keypoint:                                               # keypoint branch (:142-145); test time only
+            self.num_keypoints = int(cfg['num_keypoints'])
+            self.keypoint_roipooling = RoIAlignAvg(14, 14, 1.0 / cfg['anchor_stride'])
+            self.keypoint_head = self._make_branch(1024, 512, self.num_keypoints, 8, upscaling=True)
         self.with_mask = bool(cfg.get('with_mask'))
         if self.with_mask:                                                   # mask branch (:146-149), BASELINE configs[4]
             self.mask_roipooling = RoIAlignAvg(14, 14, 1.0 / cfg['anchor_stride'])
@@ -121,15 +124,16 @@ class ResNet(FasterRCNN_AdEx):
         self._head_convs3x3 = [m for m in self.layer4.modules() if isinstance(m, L.Conv2d) and m.kernel_size == (3, 3)]
 
     def _make_branch(self, inplanes, midplanes, outplanes, depth, upscaling=False):
-        """FCN branch (:168-193): depth x (3x3 conv + ReLU), 2x2/2 transposed conv + ReLU, 1x1 conv to `outplanes` maps"""
-        if upscaling:
-            raise NotImplementedError("bilinear x2 behind the deconvolution: keypoint branch only")
+        """FCN branch (:168-193): depth x (3x3 conv + ReLU), 2x2/2 transposed conv + ReLU, with `upscaling` (the keypoint branch) a
+        bilinear x2 (align_corners=True, models/mask_rcnn/resnet.py:186-189), 1x1 conv to `outplanes` maps"""
         seq, cin = [], inplanes
         for _ in range(depth):
             seq.append(nn.Sequential(L.Conv2d(cin, midplanes, kernel_size=3, stride=1, padding=1, fused_act=ACT_RELU),
                                      L.FusedAct("ReLU")))
             cin = midplanes
         seq.append(nn.Sequential(L.ConvTranspose2x2s2(midplanes, midplanes), L.Activation("relu")))
+        if upscaling:
+            seq.append(L.Upsample2x())
         seq.append(L.Conv2d(midplanes, outplanes, kernel_size=1))
         return nn.Sequential(*seq)
 
@@ -215,6 +219,33 @@ class ResNet(FasterRCNN_AdEx):
             return self.mask_head(x)
         y = self.mask_head(x.view(1, x.shape[0], R * 14, 14))               # [1, classes, R*28, 28]
         return y.view(y.shape[1], R, 28, 28).transpose(0, 1)
+
+    def keypoint_predictor(self, x, rois):
+        """:261-265: [R, 5] RoIs -> keypoint heat maps [R, num_keypoints, 56, 56].  Test time only: the reference's keypoint targets and
+        loss are in its missing models/mask_rcnn/mask_rcnn.py, so nothing here trains the branch.  Like `mask_predictor` the branch runs
+        CHANNEL-MAJOR when R % 4 == 0: pooled maps [C, R, 14, 14] as one [1, C, R*14, 14] image, the eight 3x3 convolutions with row
+        period 14, the transposed convolution's pixel shuffle keeps the stack a stack ([1, C, R*28, 28]).  The bilinear x2 must not
+        blend the last row of one RoI with the first row of the next: it runs on the [C*R, 1, 28, 28] view of that stack (the kernel
+        takes B*C planes), and its result is seen as [1, C, R*56, 56] by the 1x1 convolution.  The returned tensor is a view in the
+        reference's index order either way."""
+        assert rois.shape[1] == 5
+        R = rois.shape[0]
+        tall = self.tall_head and R > 0 and R % 4 == 0 and not os.environ.get("SCDA_RESNET_HEAD_NCHW")
+        self.keypoint_roipooling.channel_major = tall
+        for m in self.keypoint_head.modules():
+            if isinstance(m, L.Conv2d) and m.kernel_size == (3, 3):
+                m.row_period = 14 if tall else 0
+        x = self.keypoint_roipooling(x, rois)
+        if not tall:
+            return self.keypoint_head(x)
+        C = x.shape[0]
+        y = x.view(1, C, R * 14, 14)
+        for m in self.keypoint_head[:-2]:                                   # 8 x (3x3 conv + ReLU), 2x2/2 transposed conv + ReLU
+            y = m(y)
+        C = y.shape[1]
+        y = self.keypoint_head[-2](y.contiguous().view(C * R, 1, 28, 28))   # bilinear x2 per RoI plane: no seam between the RoIs
+        y = self.keypoint_head[-1](y.view(1, C, R * 56, 56))                # [1, Kp, R*56, 56]
+        return y.view(y.shape[1], R, 56, 56).transpose(0, 1)
 
     def _extra_source_losses(self, input, feat, proposals):
         """The mask loss of the source image.  The reference's loss code for this branch is in the missing

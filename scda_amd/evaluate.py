@@ -145,7 +145,37 @@ def write_segm_results(writer, image_info, image_ids, out, category_of=None, inp
     return fallbacks
 
 
-def coco_stats(loader, predictor, evaluator, device=None, distributed=False, group=None, proposals=False):
+def write_keypoint_results(writer, image_info, image_ids, out, category_of=None, keep_num=100):
+    """The JSON lines of the reference's write_results_to_file (tools/mask_rcnn_train_val.py:381-430) for the keypoint case (:415-418)
+    from one scda_amd.infer.Predictor(keypoints=True) pass: per image the `keep_num` best detections by score (ties in the detections'
+    order, as write_segm_results), one line each with `image_id`, `bbox` = [x, y, w, h] of the detection box divided by resize_scale in
+    float32 (:408), `score`, `category_id` (category_of(class), default the class index) and `keypoints` = the detection's
+    keypoints_orig row flattened to 3 Kp numbers (x, y divided by resize_scale, :417; the third value of each keypoint is the raw
+    resized heat-map value).  image_info [B, >=3] rows (h, w, resize_scale, ...); image_ids: B ids.  `out`: the pass's result tuple (its
+    last two entries are keypoints, keypoints_orig) or an OriginalSizeResult of a pass that also had original_size."""
+    from scda_amd import infer
+    info = _np(image_info)
+    if info.ndim != 2 or info.shape[1] < 3 or len(image_ids) != info.shape[0]:
+        raise ValueError("write_keypoint_results: image_info [B, >=3] and B image ids")
+    original = isinstance(out, infer.OriginalSizeResult)
+    kps = _np(out.keypoints_orig if original else out[-1])
+    det, det_counts = _np(out[2]), _np(out[3])
+    if kps.ndim != 4 or kps.shape[:2] != det.shape[:2] or kps.shape[3] != 3:
+        raise ValueError("write_keypoint_results: the pass carries no keypoints (Predictor(keypoints=True))")
+    for b in range(info.shape[0]):
+        d = det[b, :int(det_counts[b])]
+        order = np.argsort(-d[:, 5], kind='stable')[:keep_num]
+        for ix in order:
+            box = (d[ix, 1:5] / np.float32(info[b, 2])).tolist()
+            cls = int(d[ix, 6])
+            res = {'image_id': int(image_ids[b]), 'bbox': [box[0], box[1], box[2] - box[0], box[3] - box[1]], 'score': d[ix, 5].tolist(),
+                   'category_id': category_of(cls) if category_of is not None else cls,
+                   'keypoints': kps[b, ix].reshape(-1).tolist()}
+            writer.write(json.dumps(res) + '\n')
+        writer.flush()
+
+
+def coco_stats(loader, predictor, evaluator, device=None, distributed=False, group=None, proposals=False, original_keypoints=False):
     """Drives a scda_amd.infer.Predictor over a loader into a scda_amd.coco_eval.CocoEvaluator and returns COCOeval's 12 stats (numpy
     float64).  Loader items are dicts: 'image' [B, 3, H, W], 'image_info' [B, >= 2], 'image_ids' int32 [B], and the ground truth as
     CocoEvaluator.add takes it -- 'gt_boxes' float64 [B, Gcap, 4] (x, y, w, h), 'gt_areas', 'gt_iscrowd', 'gt_categories', 'gt_counts',
@@ -174,10 +204,27 @@ def coco_stats(loader, predictor, evaluator, device=None, distributed=False, gro
     100 and 1000 proposals with params={'max_dets': [1, 100, 1000]}): the evaluator must be a 'bbox' one built with use_cats=False and
     max_dets_per_image = the Predictor's proposal capacity; it is fed out[0], out[1] through CocoEvaluator.add_proposals in place of
     the detections.  Proposals stand at the network input's coordinates, so a Predictor with original_size is refused here.  A
-    use_cats=False evaluator with proposals=False is fed the detections (class rows scored category-agnostically).  A 'keypoints'
-    evaluator cannot be driven from here -- no keypoint head exists; feed CocoEvaluator.add directly -- and raises ValueError."""
-    if evaluator.iou_type == 'keypoints':
-        raise ValueError("coco_stats: there is no keypoint head to drive; feed a 'keypoints' evaluator through CocoEvaluator.add")
+    use_cats=False evaluator with proposals=False is fed the detections (class rows scored category-agnostically).
+
+    A 'keypoints' evaluator (CocoEvaluator(K, 'keypoints', num_keypoints=Kp)) needs a Predictor(keypoints=True) -- ValueError otherwise
+    -- with evaluator.D == the Predictor's top_n and evaluator.Kp == model.num_keypoints.  It is fed the pass's `keypoints` (the network
+    input's coordinates, like the detections), or with original_keypoints=True its `keypoints_orig` (x, y divided by resize_scale:
+    COCO's own annotations then need no rescaling); the ground truth also carries 'gt_keypoints' float64 [B, Gcap, Kp, 3] and
+    'gt_num_keypoints' int32 [B, Gcap], from the item or built from its 'annotations' by coco_gt.flatten_annotations(...,
+    keypoints=True).  COCOeval's 10 keypoint stats come back.  proposals=True does not apply."""
+    kps = evaluator.iou_type == 'keypoints'
+    if kps:
+        if not getattr(predictor, 'keypoints', False):
+            raise ValueError("coco_stats: a 'keypoints' evaluator needs a Predictor built with keypoints=True (a detector with the "
+                             "keypoint branch)")
+        if proposals:
+            raise ValueError("coco_stats: proposals=True does not apply to a 'keypoints' evaluator")
+        top_n, n_kp = int(predictor.box_cfg['top_n']), int(predictor.model.num_keypoints)
+        if evaluator.D != top_n or evaluator.Kp != n_kp:
+            raise ValueError("coco_stats: the 'keypoints' evaluator holds %d detections of %d keypoints per image, the Predictor gives %d "
+                             "of %d" % (evaluator.D, evaluator.Kp, top_n, n_kp))
+    elif original_keypoints:
+        raise ValueError("coco_stats: original_keypoints=True goes with a 'keypoints' evaluator")
     if proposals and (evaluator.use_cats or evaluator.iou_type != 'bbox'):
         raise ValueError("coco_stats: proposals=True needs a 'bbox' evaluator built with use_cats=False")
     if proposals and getattr(predictor, 'original_size', None) is not None:
@@ -205,15 +252,22 @@ def coco_stats(loader, predictor, evaluator, device=None, distributed=False, gro
                         ground_truth = coco_gt.GroundTruth(device, evaluator.G, bits.shape[2], bits.shape[3])
                     gt = ground_truth.load(item['annotations'], sizes if original else item['sizes'])
                 else:
-                    flat = coco_gt.flatten_annotations(item['annotations'], sizes if original else item['sizes'], evaluator.G)
+                    flat = coco_gt.flatten_annotations(item['annotations'], sizes if original else item['sizes'], evaluator.G,
+                                                       **({'keypoints': True, 'num_keypoints': evaluator.Kp} if kps else {}))
                     gt = tuple(native.upload(flat[k], device) for k in ('gt_boxes', 'gt_areas', 'gt_iscrowd', 'gt_categories', 'gt_counts'))
                     gt += (None,)
+                    if kps:
+                        gt_kp = (native.upload(flat['gt_keypoints'], device), native.upload(flat['gt_num_keypoints'], device))
             else:
                 gt = (item['gt_boxes'], item['gt_areas'], item['gt_iscrowd'], item['gt_categories'], item['gt_counts'],
                       item['gt_mask_bits'] if segm else None)
+                if kps:
+                    gt_kp = (item['gt_keypoints'], item['gt_num_keypoints'])
             kw = {}
             if segm:
                 kw = {'mask_bits': bits, 'det_areas': out[5]['area'], 'gt_mask_bits': gt[5], 'sizes': sizes}
+            if kps:
+                kw = {'keypoints': out[-1] if original_keypoints else out[-2], 'gt_keypoints': gt_kp[0], 'gt_num_keypoints': gt_kp[1]}
             if proposals:
                 evaluator.add_proposals(item['image_ids'], out[0], out[1], *gt[:5])
             else:

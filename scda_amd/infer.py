@@ -31,7 +31,15 @@ Results at the original image size (opt-in on top, `Predictor(model, cfg, masks=
 scda_amd/csrc/mask_rescale.hip, one fused kernel that never writes the float plane to memory) and thresholded there with `>` (:423)
 into mask_bits_orig; det_orig holds the boxes divided by resize_scale (:408).  With rle=True the run-length results are those of
 mask_bits_orig.  The limits (original sizes above (Ho, Wo), a down-scale above native.mask_rescale_max_ratio() = 4) are flagged per
-image on the device; mask_rows and segm_rows raise for a flagged image."""
+image on the device; mask_rows and segm_rows raise for a flagged image.
+
+Keypoints (opt-in, `Predictor(model, cfg, keypoints=True)`, the detector built with the keypoint branch; independent of `masks`): behind
+the box prediction the detections become the keypoint head's RoIs, `model.keypoint_predictor` gives [B * top_n, Kp, 56, 56] heat maps and
+scda_amd/csrc/keypoint_ops.hip turns them into (x, y, score) rows without writing an image-sized plane: each heat map resized to its
+box as functions/mask.py:21-49 resizes a mask plane, then np.argmax over the part of the box inside the padded image.  The reference's own
+heat-map decoder is in its missing models/mask_rcnn/mask_rcnn.py: the CHOICE OF THIS RULE IS OURS, and its parity is pinned to
+predict_masks + np.argmax, not to a reference keypoint decoder (include/scda_ops.h).  Not covered: training the branch, heat maps above
+64 x 64, images of one call with different (h, w) in the host-side helpers (the Predictor decodes against the batch's padded shape)."""
 import numpy as np
 import torch
 
@@ -113,9 +121,18 @@ class Predictor:
     of the hard NMS, and the per-image top_n ranks by the rescored scores -- the rows the eval forward gives with the same dict under
     test_predict_bbox_cfg's `soft_nms` key, which is also where this argument's default comes from (the argument overrides the key).
     None and no key: hard NMS, the bytes as ever.  ValueError for an unknown method, a sigma <= 0 or a post_nms_top_n above the kernel's
-    capacity of 2048 rows per list.  The RPN stage keeps its hard NMS."""
+    capacity of 2048 rows per list.  The RPN stage keeps its hard NMS.
 
-    def __init__(self, model, cfg, masks=False, mask_threshold=0.5, rle=False, rle_capacity=None, soft_nms=None, original_size=None):
+    keypoints=True (a detector with the keypoint branch only; image_info [B, >= 3] = (h, w, resize_scale, ...); independent of masks):
+    the result grows by TWO entries, appended after every other one: keypoints float32 [B, top_n, Kp, 3] = (x, y, score) per detection
+    and keypoint at the network input's coordinates (the rule: include/scda_ops.h, scda_keypoint_decode_hip; score = the raw resized
+    heat-map value), and keypoints_orig, the same with x and y divided in float32 by resize_scale (tools/mask_rcnn_train_val.py:417, as
+    det_orig divides its boxes).  Rows of padding detections are zero.  With original_size the two are also named: .keypoints,
+    .keypoints_orig.  The heat maps the decode read stay reachable as `pred.keypoint_heat` ([B * top_n, Kp, 56, 56], a view) until the
+    next pass.  Fixed buffers per shape, two more launches behind the head, no additional wait for the host."""
+
+    def __init__(self, model, cfg, masks=False, mask_threshold=0.5, rle=False, rle_capacity=None, soft_nms=None, original_size=None,
+                 keypoints=False):
         if model.training:
             raise ValueError("Predictor: put the detector in eval mode first (model.eval())")
         self.masks, self.mask_threshold = bool(masks), float(mask_threshold)
@@ -137,6 +154,15 @@ class Predictor:
             if int(PIL.__version__.split(".")[0]) < 7:
                 raise ValueError("device mask path: Pillow %s resizes with NEAREST by default; the device path restates Pillow >= 7's "
                                  "BICUBIC default -- use predict_masks on the host" % PIL.__version__)
+        self.keypoints = bool(keypoints)
+        if self.keypoints:
+            if not getattr(model, 'with_keypoint', False):
+                raise ValueError("Predictor: keypoints=True needs a detector with the keypoint branch (cfg with_keypoint)")
+            import PIL
+            if int(PIL.__version__.split(".")[0]) < 7:
+                raise ValueError("device keypoint path: Pillow %s resizes with NEAREST by default; the device path restates Pillow >= "
+                                 "7's BICUBIC default -- use predict_keypoints on the host" % PIL.__version__)
+        self.keypoint_heat = None
         self.model, self.cfg = model, cfg
         self.rpn_cfg, self.box_cfg = _sections(cfg)
         if not self.box_cfg.get('bbox_normalize_stats_precomputed', False):
@@ -177,6 +203,26 @@ class Predictor:
         self.mask_cls = torch.zeros(R, dtype=torch.int32, device=dev)
         self.mask_planes = None                                               # [R, h, w] once the head's output size is known
         self.mask_bits = torch.zeros(B, self.top_n, H, (W + 31) // 32, dtype=torch.int32, device=dev)
+
+    def _allocate_keypoints(self, B, W, dev):
+        R, Kp = B * self.top_n, int(self.model.num_keypoints)
+        self.kp_rois = torch.zeros(R, 5, dtype=torch.float32, device=dev)
+        self.kp_cls = torch.zeros(R, dtype=torch.int32, device=dev)
+        self.kp_out = torch.zeros(B, self.top_n, Kp, 3, dtype=torch.float32, device=dev)
+        self.kp_out_orig = torch.zeros(B, self.top_n, Kp, 3, dtype=torch.float32, device=dev)
+        self.kp_ws = torch.empty(max(N.keypoint_decode_workspace_bytes(R, Kp, W), 8), dtype=torch.uint8, device=dev)
+
+    def _keypoints(self, feat, info, B, H, W):
+        """detections -> RoIs -> keypoint head -> each heat map's first maximum inside its resized window; x and y / resize_scale"""
+        N.det_rois(self.det, self.det_counts, self.kp_rois, self.kp_cls)
+        heat = self.model.keypoint_predictor(feat, self.kp_rois).detach()
+        if heat.shape[1] != self.kp_out.shape[2]:
+            raise ValueError("Predictor: the keypoint head gives %d maps, model.num_keypoints is %d" % (heat.shape[1], self.kp_out.shape[2]))
+        self.keypoint_heat = heat
+        N.keypoint_decode(self.kp_rois, heat, H, W, cls=self.kp_cls, out=self.kp_out.view(B * self.top_n, -1, 3), ws=self.kp_ws)
+        self.kp_out_orig.copy_(self.kp_out)
+        self.kp_out_orig[:, :, :, 0:2].div_(info[:, 2].view(B, 1, 1, 1))
+        return self.kp_out, self.kp_out_orig
 
     def _allocate_orig(self, B, dev):
         Ho, Wo = self.original_size
@@ -262,6 +308,8 @@ class Predictor:
             raise ValueError("Predictor: image_info must be [B, >=2] (h, w, ...)")
         if self.original_size is not None and info.shape[1] < 5:
             raise ValueError("Predictor: original_size needs image_info [B, >=5] (h, w, resize_scale, origin_h, origin_w)")
+        if self.keypoints and info.shape[1] < 3:
+            raise ValueError("Predictor: keypoints=True needs image_info [B, >=3] (h, w, resize_scale, ...)")
         feat = model.feature_extractor(images)
         rpn_cls, rpn_loc = model.rpn(feat)
         prob = _objectness(rpn_cls).contiguous()
@@ -277,6 +325,8 @@ class Predictor:
                 self._allocate_orig(B, dev)
             if self.rle:
                 self._allocate_rle(B, *(self.original_size or images.shape[2:]), dev)
+            if self.keypoints:
+                self._allocate_keypoints(B, images.shape[3], dev)
             self.shape = shape
             self.graph = None
         N.rpn_proposals_batched(prob, loc, self.anchors64, info, int(rc['pre_nms_top_n']), float(rc['roi_min_size']),
@@ -300,6 +350,13 @@ class Predictor:
                                            {'mask_bits_orig': n, 'det_orig': n + 1, 'orig_status': n + 2, 'rle': 5 if self.rle else None})
         elif self.rle:
             self._out += (self._rle(info, B, images.shape[2], images.shape[3]),)
+        if self.keypoints:
+            kp = self._keypoints(feat, info, B, images.shape[2], images.shape[3])
+            if isinstance(self._out, OriginalSizeResult):
+                n = len(self._out)
+                self._out = OriginalSizeResult(tuple(self._out) + kp, dict(self._out._names, keypoints=n, keypoints_orig=n + 1))
+            else:
+                self._out += kp
         return self._out
 
     def capture(self, images, image_info):
@@ -327,7 +384,7 @@ _PREDICTORS = {}
 
 
 def predict(model, images, image_info, cfg, masks=False, mask_threshold=0.5, rle=False, rle_capacity=None, soft_nms=None,
-            original_size=None):
+            original_size=None, keypoints=False):
     """images [B,3,H,W] on the device, image_info [B,>=2] (host or device) -> device tensors
     (proposals [B,P,6] = (b, x1, y1, x2, y2, score), proposal_counts int32 [B], detections [B,top_n,7] =
     (b, x1, y1, x2, y2, score, class), detection_counts int32 [B]); rows past an image's count are padding.
@@ -335,6 +392,7 @@ def predict(model, images, image_info, cfg, masks=False, mask_threshold=0.5, rle
     run-length results (see Predictor, segm_rows).
     soft_nms: see Predictor (a dict; None = the cfg's own `soft_nms` key, if any).
     original_size=(Ho, Wo): see Predictor; the result is then an OriginalSizeResult (image_info [B,>=5]).
+    keypoints=True: see Predictor; two more entries at the end, keypoints and keypoints_orig float32 [B,top_n,Kp,3] (image_info [B,>=3]).
     One Predictor per (model, cfg, masks, mask_threshold, rle, rle_capacity, soft_nms, original_size) is kept and reused; its buffers are overwritten by
     the next call."""
     key = (id(model), id(cfg)) if not masks else (id(model), id(cfg), True, float(mask_threshold))
@@ -344,10 +402,12 @@ def predict(model, images, image_info, cfg, masks=False, mask_threshold=0.5, rle
         key += ('soft_nms', N.soft_nms_setting(soft_nms))
     if original_size is not None:
         key += ('original_size', int(original_size[0]), int(original_size[1]))
+    if keypoints:
+        key += ('keypoints',)
     p = _PREDICTORS.get(key)
     if p is None or p.model is not model:
         p = _PREDICTORS[key] = Predictor(model, cfg, masks=masks, mask_threshold=mask_threshold, rle=rle, rle_capacity=rle_capacity,
-                                         soft_nms=soft_nms, original_size=original_size)
+                                         soft_nms=soft_nms, original_size=original_size, keypoints=keypoints)
     return p(images, image_info)
 
 

@@ -566,6 +566,51 @@ def mask_paste(rois, planes, H, W, cls=None, packed=False, threshold=0.5, out=No
     return out
 
 
+KEYPOINT_PLANE_MAX = 64
+
+
+def keypoint_decode_workspace_bytes(R, Kp, W):
+    return int(lib().scda_keypoint_decode_workspace_bytes(int(R), int(Kp), int(W)))
+
+
+def keypoint_decode(rois, heat, H, W, cls=None, out=None, ws=None):
+    """R x Kp heat maps -> float32 [R, Kp, 3] rows (x, y, score) on the device (include/scda_ops.h states the rule: each heat map resized
+    to its RoI as functions/mask.py:21-49 resizes a mask plane, then np.argmax over the part of the window inside (H, W); the choice
+    of rule is ours, its parity is pinned to predict_masks + np.argmax).  rois [R, >=5] (b, x1, y1, x2, y2, ...), heat [R, Kp, h, w]
+    in any strided order (not required contiguous), h, w <= 64; cls int32 [R]: rows with cls < 0 (padding) give (0, 0, 0), as do empty
+    or non-finite windows and windows wholly outside (H, W).  ws: a uint8 buffer of keypoint_decode_workspace_bytes(R, Kp, W)."""
+    _req(rois, "rois")
+    if not isinstance(heat, torch.Tensor) or not heat.is_cuda or heat.dtype != torch.float32:
+        raise ScdaNativeError("heat must be a float32 tensor on the HIP device; there is no CPU path")
+    if rois.dim() != 2 or rois.shape[1] < 5 or heat.dim() != 4 or heat.shape[0] != rois.shape[0]:
+        raise ValueError("keypoint_decode: rois must be [R, >=5] and heat [R, Kp, h, w]")
+    R, Kp, h, w = heat.shape
+    if h > KEYPOINT_PLANE_MAX or w > KEYPOINT_PLANE_MAX:
+        raise ValueError("keypoint_decode: heat maps of at most %d x %d" % (KEYPOINT_PLANE_MAX, KEYPOINT_PLANE_MAX))
+    if min(heat.stride()) < 0:
+        raise ValueError("keypoint_decode: negative strides")
+    if cls is not None:
+        _req(cls, "cls", torch.int32)
+        if cls.numel() != R:
+            raise ValueError("keypoint_decode: cls must be [R]")
+    H, W = int(H), int(W)
+    if out is None:
+        out = torch.empty(R, Kp, 3, dtype=torch.float32, device=rois.device)
+    _req(out, "out")
+    if tuple(out.shape) != (R, Kp, 3):
+        raise ValueError("keypoint_decode: out must be [R, Kp, 3]")
+    need = keypoint_decode_workspace_bytes(R, Kp, W)
+    if ws is None:
+        ws = torch.empty(max(need, 8), dtype=torch.uint8, device=rois.device)
+    _req(ws, "ws", torch.uint8)
+    if ws.numel() < need:
+        raise ValueError("keypoint_decode: ws holds %d bytes, %d needed" % (ws.numel(), need))
+    sr, sk, sh, sw = heat.stride()
+    _check(lib().scda_keypoint_decode_hip(_p(rois), rois.shape[1], _p(cls), _p(heat), sr, sk, sh, sw, R, Kp, h, w, H, W, _p(ws), _p(out),
+                                          _stream()), "scda_keypoint_decode_hip")
+    return out
+
+
 def mask_rescale_max_ratio():
     """the largest down-scale h / oh, w / ow of mask_rescale (a capacity of the kernel's LDS tables)"""
     return int(lib().scda_mask_rescale_max_ratio())

@@ -263,6 +263,11 @@ class ScdaTrainer:
         collectives: issue the four per-phase all-reduces (default: world_size > 1).  True with a one-rank process group runs
         the whole RCCL path -- async all-reduce on the device buckets, waits, stream hand-over -- on a single GPU
         (tests/test_distributed_gpu.py::test_rccl_one_rank_group_matches_plain_step)."""
+        if models is not None and getattr(models[0], 'with_keypoint', False):
+            # the reference's keypoint targets and loss are in its missing models/mask_rcnn/mask_rcnn.py: no loss reaches the branch, and
+            # its parameters would sit in the flat buckets without ever getting a gradient
+            raise ValueError("ScdaTrainer: training the keypoint branch is not covered (the detector was built with with_keypoint; the "
+                             "branch runs at test time only -- build the training detector without it)")
         # parity tests: a scda_amd.probe.Probe (replayed selections / RPN outputs / dropout masks of the CPU oracle), visible to the
         # product's modules while THIS trainer's step() runs and at no other time; None in production
         self.probe = probe
