@@ -11,13 +11,12 @@
 // maximum and the first NaN wins).  That is a total order on (value, position) pairs with distinct positions, so the result does not
 // depend on the order in which lanes, waves or strips are combined.
 //
-// LDS.  Planes go up to 64 x 64.  Tabulating a down-scaled axis as mask_ops.hip does (n_in - 1 samples of n_in taps) would take
-// 63 * 64 doubles = 32 KB per axis, 113 KB with the plane and the horizontal pass: one workgroup per CU.  Here an up-scaled (or equal)
-// axis -- at most 5 taps per sample -- is tabulated, and a down-scaled axis (fewer than 64 output samples, a small window) keeps per
-// sample only the first tap, the tap count and the weights' sum, and recomputes bicubic(.) / sum per tap: the same IEEE operations in
-// the same order as axis_taps.  16 KB plane + 32 KB horizontal pass + 7.5 KB tables + 3 KB per-sample entries = 58.6 KB.
+// LDS.  Planes go up to 64 x 64, so a down-scaled axis (fewer than 64 output samples, a small window) has up to 64 taps per sample:
+// tabulating it would take 63 * 64 doubles = 32 KB per axis, 113 KB with the plane and the horizontal pass -- one workgroup per CU.
+// mask_resample.h's tables keep the weights of a run of samples only when they fit (5 per sample on average), and otherwise per sample
+// the first tap, the tap count and the weights' sum.  16 KB plane + 32 KB horizontal pass + 6 KB and 3 KB tables = 57.0 KB.
 #include "eval_prims.h"
-#include "mask_resample.h"      // bicubic, axis_ksize, axis_taps, trunc_ok
+#include "mask_resample.h"      // RoiWindow, AxisTable, horizontal_pass
 
 #include <climits>
 
@@ -27,8 +26,8 @@ using namespace scda;
 constexpr int kMaxIn = 64;                      // largest plane side (the keypoint head gives 56)
 constexpr int kStrip = 128;                     // image columns per workgroup
 constexpr int kRows = 64;                       // window rows per vertical-table refill
-constexpr int kThreads = 256;
-constexpr int kUpTaps = 5;                      // taps of a sample of an up-scaled or equal axis: ceil(2.0) * 2 + 1
+constexpr int kThreads = kResampleThreads;
+constexpr int kTaps = 5;                        // table room per sample: an up-scaled or equal axis has 5 taps (mask_resample.h)
 
 struct Best { float v; int at; };               // a resized value and its position y * W + x in the image; INT_MAX: none yet
 
@@ -38,36 +37,6 @@ __device__ inline bool better(float av, int aat, float bv, int bat) {
     if (an != bn) return an;
     if (an || av == bv) return aat < bat;
     return av > bv;
-}
-
-// one sample of a DOWN-scaled axis n_in -> n_out (n_out < n_in): first tap, tap count and the left-to-right sum of the raw weights,
-// as axis_taps computes them
-__device__ inline void axis_sum(int n_in, int n_out, int xx, int ks, int *first, int *count, double *sum) {
-    const double scale = (double)n_in / n_out;
-    const double fs = scale < 1.0 ? 1.0 : scale;
-    const double support = 2.0 * fs, ss = 1.0 / fs;
-    const double center = (xx + 0.5) * scale;
-    int xmin = (int)(center - support + 0.5);
-    if (xmin < 0) xmin = 0;
-    int xmax = (int)(center + support + 0.5);
-    if (xmax > n_in) xmax = n_in;
-    int n = xmax - xmin;
-    if (n > ks) n = ks;
-    if (n < 0) n = 0;
-    double ww = 0.0;
-    for (int k = 0; k < n; ++k) ww += bicubic((k + xmin - center + 0.5) * ss);
-    *first = xmin; *count = n; *sum = ww;
-}
-
-// tap k of that sample: axis_taps' w[k] after its normalisation
-__device__ inline double axis_weight(int n_in, int n_out, int xx, int first, int k, double sum) {
-    const double scale = (double)n_in / n_out;
-    const double fs = scale < 1.0 ? 1.0 : scale;
-    const double ss = 1.0 / fs;
-    const double center = (xx + 0.5) * scale;
-    double w = bicubic((k + first - center + 0.5) * ss);
-    if (sum != 0.0) w /= sum;
-    return w;
 }
 
 __device__ inline Best wave_best(Best b) {
@@ -88,84 +57,37 @@ __global__ __launch_bounds__(kThreads) void keypoint_strip_kernel(const float *_
                                                                   Best *__restrict__ part) {
     __shared__ float plane[kMaxIn * kMaxIn];
     __shared__ float tmp[kMaxIn * kStrip];                         // the horizontal pass: [ph][this strip's columns]
-    __shared__ double hw[kStrip * kUpTaps], vw[kRows * kUpTaps];   // the weights of an up-scaled or equal axis
-    __shared__ double hsum[kMaxIn], vsum[kMaxIn];                  // the weights' sums of a down-scaled axis (fewer than kMaxIn samples)
-    __shared__ int hfirst[kStrip], hcount[kStrip], vfirst[kRows], vcount[kRows];
+    __shared__ AxisTable<kStrip, kTaps>::Lds hlds;
+    __shared__ AxisTable<kRows, kTaps, true>::Lds vlds;
     __shared__ Best wave_part[kThreads / 64];
+    AxisTable<kStrip, kTaps> htab(hlds);
+    AxisTable<kRows, kTaps, true> vtab(vlds);            // the one table a run may not fit: 64 rows down-scaled to more than 21
+    static_assert(htab.holds(kMaxIn), "a down-scaled axis of the largest plane fits the horizontal table");
     const int r = blockIdx.z, k = blockIdx.y, c0 = blockIdx.x * kStrip, t = threadIdx.x;
-    // ---- the RoI (uniform over the workgroup), as mask_paste_kernel reads it
-    const float *roi = rois + (size_t)r * roi_stride;
-    int x1 = 0, y1 = 0, x2 = 0, y2 = 0;
-    bool live = !(cls && cls[r] < 0);
-    live = trunc_ok(roi[1], &x1) && live;
-    live = trunc_ok(roi[2], &y1) && live;
-    live = trunc_ok(roi[3], &x2) && live;
-    live = trunc_ok(roi[4], &y2) && live;
-    int roi_w = 0, roi_h = 0;
-    if (live) {
-        roi_w = x2 - x1 + 1; roi_h = y2 - y1 + 1;
-        live = roi_w > 0 && roi_h > 0;
-    }
-    // columns [ca, cb) of this strip and rows [ya, yb) of the image lie inside the window
+    // columns [ca, cb) of this strip and rows [ya, yb) of the image lie inside the window (uniform over the workgroup)
+    const RoiWindow win = read_roi_window(rois, roi_stride, cls, r);
     int ca = 0, cb = 0, ya = 0, yb = 0;
-    if (live) {
-        ca = x1 > c0 ? x1 : c0;
-        cb = min(min(x1 + roi_w, W), c0 + kStrip);
-        ya = y1 > 0 ? y1 : 0;
-        yb = min(y1 + roi_h, H);
-        live = ca < cb && ya < yb;
-    }
+    const bool live = win.live && win.clip_x(c0, min(W, c0 + kStrip), &ca, &cb) && win.clip_y(0, H, &ya, &yb);
     Best best = {-INFINITY, INT_MAX};
     if (live) {
         const int na = cb - ca;                                    // 1 .. kStrip
-        const bool down_h = roi_w < pw, down_v = roi_h < ph;       // a down-scaled axis has fewer than kMaxIn samples in all
-        const int ksh = axis_ksize(pw, roi_w), ksv = axis_ksize(ph, roi_h);     // <= kUpTaps unless down-scaled
         const float *src_plane = heat + r * sr + k * sk;
         for (int i = t; i < ph * pw; i += kThreads) {
             const int y = i / pw, x = i - y * pw;
             plane[i] = src_plane[y * sh + x * sw];
         }
-        for (int i = t; i < na; i += kThreads) {
-            if (down_h) axis_sum(pw, roi_w, ca + i - x1, ksh, &hfirst[i], &hcount[i], &hsum[i]);
-            else axis_taps(pw, roi_w, ca + i - x1, ksh, &hfirst[i], &hcount[i], &hw[i * kUpTaps]);
-        }
+        htab.fill(pw, win.w, ca - win.x1, na);
         __syncthreads();
-        for (int i = t; i < ph * na; i += kThreads) {
-            const int row = i / na, xa = i - row * na;
-            const int first = hfirst[xa], n = hcount[xa];
-            const float *src = plane + row * pw + first;
-            double s = 0.0;
-            if (down_h) {
-                const double sum = hsum[xa];
-                for (int q = 0; q < n; ++q) s += (double)src[q] * axis_weight(pw, roi_w, ca + xa - x1, first, q, sum);
-            } else {
-                const double *w = hw + xa * kUpTaps;
-                for (int q = 0; q < n; ++q) s += (double)src[q] * w[q];
-            }
-            tmp[row * kStrip + xa] = (float)s;
-        }
+        horizontal_pass(plane, pw, ph, htab, na, tmp, kStrip, [](int xa) { return xa; });
         // ---- the vertical pass over the visible rows, kRows at a time; nothing is stored but each thread's best
         for (int ybase = ya; ybase < yb; ybase += kRows) {
             const int nv = min(yb - ybase, kRows);
             __syncthreads();                                       // tmp is complete / the previous refill has been read
-            for (int i = t; i < nv; i += kThreads) {
-                if (down_v) axis_sum(ph, roi_h, ybase + i - y1, ksv, &vfirst[i], &vcount[i], &vsum[i]);
-                else axis_taps(ph, roi_h, ybase + i - y1, ksv, &vfirst[i], &vcount[i], &vw[i * kUpTaps]);
-            }
+            vtab.fill(ph, win.h, ybase - win.y1, nv);
             __syncthreads();
             for (int i = t; i < nv * na; i += kThreads) {          // row-major over this refill's part of the strip
                 const int ty = i / na, xa = i - ty * na;
-                const int first = vfirst[ty], n = vcount[ty];
-                const float *col = tmp + first * kStrip + xa;
-                double s = 0.0;
-                if (down_v) {
-                    const double sum = vsum[ty];
-                    for (int q = 0; q < n; ++q) s += (double)col[q * kStrip] * axis_weight(ph, roi_h, ybase + ty - y1, first, q, sum);
-                } else {
-                    const double *w = vw + ty * kUpTaps;
-                    for (int q = 0; q < n; ++q) s += (double)col[q * kStrip] * w[q];
-                }
-                const float v = (float)s;
+                const float v = vtab.dot(ty, tmp + vtab.first(ty) * kStrip + xa, kStrip);
                 const int at = (ybase + ty) * W + ca + xa;
                 if (better(v, at, best.v, best.at)) { best.v = v; best.at = at; }
             }

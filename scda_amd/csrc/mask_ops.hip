@@ -7,7 +7,7 @@
 // IEEE operation per source operator (compiled with -ffp-contract=off), which makes the result Pillow's bit for bit; the rule is
 // stated in include/scda_ops.h and restated in numpy by tests/test_mask_infer_rules.py.
 #include "eval_prims.h"
-#include "mask_resample.h"      // bicubic, axis_ksize, axis_taps, trunc_ok
+#include "mask_resample.h"      // RoiWindow, AxisTable, horizontal_pass
 
 namespace {
 using namespace scda;
@@ -15,71 +15,41 @@ using namespace scda;
 constexpr int kMaxIn = 32;                      // largest plane side (the mask head gives 28; the golden cases use 14)
 constexpr int kStrip = 128;                     // image columns per workgroup
 constexpr int kRows = 64;                       // image rows per vertical-table refill
-constexpr int kThreads = 256;
+constexpr int kThreads = kResampleThreads;
 constexpr int kTmpStride = kStrip + kStrip / 32;    // room for the bit form's one-in-32 padding
-// weights per axis and table: an up-scale (or identity) has at most 5 taps per sample, a down-scale at most n_in taps on at most
-// n_in - 1 samples
-constexpr int kTabH = kStrip * 5 > (kMaxIn - 1) * kMaxIn ? kStrip * 5 : (kMaxIn - 1) * kMaxIn;
-constexpr int kTabV = kRows * 5 > (kMaxIn - 1) * kMaxIn ? kRows * 5 : (kMaxIn - 1) * kMaxIn;
+constexpr int kTaps = 5;                        // table room per sample: an up-scaled axis has 5 taps; a down-scaled one of <= 32 fits too
 
 template <bool BITS> __device__ inline int tmp_col(int x) { return BITS ? x + (x >> 5) : x; }
 
 // grid (column strips, R), 256 threads.  A workgroup owns columns [c0, c0 + 128) of RoI r's plane and writes EVERY row of them.
+// LDS: 4 KB plane + 16.5 KB horizontal pass + 6 KB and 3 KB tables = 29.5 KB.
 template <bool BITS>
 __global__ __launch_bounds__(kThreads) void mask_paste_kernel(const float *__restrict__ rois, int roi_stride, const int *__restrict__ cls,
                                                               const float *__restrict__ planes, int ph, int pw, int H, int W, int Wd,
                                                               float threshold, int vec4, void *__restrict__ out_) {
     __shared__ float plane[kMaxIn * kMaxIn];
     __shared__ __align__(16) float tmp[kMaxIn * kTmpStride];       // the horizontal pass: [ph][this strip's columns]
-    __shared__ double hw[kTabH], vw[kTabV];
-    __shared__ int hfirst[kStrip], hcount[kStrip], vfirst[kRows], vcount[kRows];
+    __shared__ AxisTable<kStrip, kTaps>::Lds hlds;
+    __shared__ AxisTable<kRows, kTaps>::Lds vlds;
+    AxisTable<kStrip, kTaps> htab(hlds);
+    AxisTable<kRows, kTaps> vtab(vlds);
+    static_assert(htab.holds(kMaxIn) && vtab.holds(kMaxIn), "a down-scaled axis of the largest plane fits both tables");
     const int r = blockIdx.y, c0 = blockIdx.x * kStrip, t = threadIdx.x;
-    // ---- the RoI (uniform over the workgroup)
-    const float *roi = rois + (size_t)r * roi_stride;
-    int x1 = 0, y1 = 0, x2 = 0, y2 = 0;
-    bool live = !(cls && cls[r] < 0);
-    live = trunc_ok(roi[1], &x1) && live;
-    live = trunc_ok(roi[2], &y1) && live;
-    live = trunc_ok(roi[3], &x2) && live;
-    live = trunc_ok(roi[4], &y2) && live;
-    int roi_w = 0, roi_h = 0;
-    if (live) {
-        roi_w = x2 - x1 + 1; roi_h = y2 - y1 + 1;
-        live = roi_w > 0 && roi_h > 0;
-    }
-    // columns [ca, cb) of this strip and rows [ya, yb) of the plane lie inside the window
+    // columns [ca, cb) of this strip and rows [ya, yb) of the plane lie inside the window (uniform over the workgroup)
+    const RoiWindow win = read_roi_window(rois, roi_stride, cls, r);
     int ca = 0, cb = 0, ya = 0, yb = 0;
+    const bool live = win.live && win.clip_x(c0, min(W, c0 + kStrip), &ca, &cb) && win.clip_y(0, H, &ya, &yb);
     if (live) {
-        ca = x1 > c0 ? x1 : c0;
-        cb = min(min(x1 + roi_w, W), c0 + kStrip);
-        ya = y1 > 0 ? y1 : 0;
-        yb = min(y1 + roi_h, H);
-        live = ca < cb && ya < yb;
-    }
-    const int na = cb - ca;
-    int ksh = 1, ksv = 1;
-    if (live) {
-        ksh = axis_ksize(pw, roi_w); ksv = axis_ksize(ph, roi_h);
         for (int i = t; i < ph * pw; i += kThreads) plane[i] = planes[(size_t)r * ph * pw + i];
-        for (int i = t; i < na; i += kThreads) axis_taps(pw, roi_w, ca + i - x1, ksh, &hfirst[i], &hcount[i], &hw[i * ksh]);
+        htab.fill(pw, win.w, ca - win.x1, cb - ca);
         __syncthreads();
-        for (int i = t; i < ph * na; i += kThreads) {
-            const int row = i / na, xa = i - row * na;
-            const float *src = plane + row * pw + hfirst[xa];
-            const double *w = hw + xa * ksh;
-            double s = 0.0;
-            for (int k = 0; k < hcount[xa]; ++k) s += (double)src[k] * w[k];
-            tmp[row * kTmpStride + tmp_col<BITS>(ca - c0 + xa)] = (float)s;
-        }
+        horizontal_pass(plane, pw, ph, htab, cb - ca, tmp, kTmpStride, [=](int xa) { return tmp_col<BITS>(ca - c0 + xa); });
     }
     for (int ybase = 0; ybase < H; ybase += kRows) {
         const bool hit = live && ybase < yb && ybase + kRows > ya;
         const int tv0 = ya > ybase ? ya : ybase;               // the first table row of this refill
         __syncthreads();                                       // tmp is complete / the previous refill has been read
-        if (hit) {
-            const int nv = min(yb, ybase + kRows) - tv0;
-            for (int i = t; i < nv; i += kThreads) axis_taps(ph, roi_h, tv0 + i - y1, ksv, &vfirst[i], &vcount[i], &vw[i * ksv]);
-        }
+        if (hit) vtab.fill(ph, win.h, tv0 - win.y1, min(yb, ybase + kRows) - tv0);
         __syncthreads();
         if (BITS) {
             // one row and one 32-column word per thread
@@ -89,17 +59,14 @@ __global__ __launch_bounds__(kThreads) void mask_paste_kernel(const float *__res
                 const int left = W - word * 32;
                 unsigned int bits = 0.f >= threshold ? (left >= 32 ? 0xffffffffu : (1u << left) - 1u) : 0u;
                 if (hit && y >= ya && y < yb) {
-                    const int ty = y - tv0, n = vcount[ty];
-                    const double *w = vw + ty * ksv;
-                    const float *col = tmp + vfirst[ty] * kTmpStride;
+                    const int ty = y - tv0, n = vtab.count(ty);
+                    const double *w = vtab.weights(ty);
+                    const float *col = tmp + vtab.first(ty) * kTmpStride;
                     const int cl = word * 32 - c0;
                     for (int j = 0; j < 32; ++j) {
                         const int c = word * 32 + j;
-                        if (c >= ca && c < cb) {
-                            double s = 0.0;
-                            for (int k = 0; k < n; ++k) s += (double)col[k * kTmpStride + tmp_col<true>(cl + j)] * w[k];
-                            bits = (float)s >= threshold ? bits | (1u << j) : bits & ~(1u << j);
-                        }
+                        if (c >= ca && c < cb)
+                            bits = resample_dot(col + tmp_col<true>(cl + j), kTmpStride, w, n) >= threshold ? bits | (1u << j) : bits & ~(1u << j);
                     }
                 }
                 ((unsigned int *)out_)[((size_t)r * H + y) * Wd + word] = bits;
@@ -111,16 +78,11 @@ __global__ __launch_bounds__(kThreads) void mask_paste_kernel(const float *__res
             for (int y = ybase + (t >> 5); y < min(ybase + kRows, H); y += kThreads / 32) {
                 float v[4] = {0.f, 0.f, 0.f, 0.f};
                 if (hit && y >= ya && y < yb && c < cb && c + 3 >= ca) {
-                    const int ty = y - tv0, n = vcount[ty];
-                    const double *w = vw + ty * ksv;
-                    const float *col = tmp + vfirst[ty] * kTmpStride + cl;
-                    double s[4] = {0.0, 0.0, 0.0, 0.0};
-                    for (int k = 0; k < n; ++k) {              // (columns outside the window read what LDS holds and are dropped below)
-                        const float4 p = *(const float4 *)(col + k * kTmpStride);
-                        s[0] += (double)p.x * w[k]; s[1] += (double)p.y * w[k]; s[2] += (double)p.z * w[k]; s[3] += (double)p.w * w[k];
-                    }
+                    const int ty = y - tv0;
+                    float s[4];                                // (columns outside the window read what LDS holds and are dropped below)
+                    resample_dot(tmp + vtab.first(ty) * kTmpStride + cl, kTmpStride, vtab.weights(ty), vtab.count(ty), s);
                     for (int q = 0; q < 4; ++q)
-                        if (c + q >= ca && c + q < cb) v[q] = (float)s[q];
+                        if (c + q >= ca && c + q < cb) v[q] = s[q];
                 }
                 float *dst = out + ((size_t)r * H + y) * W + c;
                 if (vec4 && c + 3 < W) {

@@ -4,8 +4,11 @@
 // One fused kernel: the pasted plane P of a detection is never written to global memory.  A workgroup owns 32 output columns (one
 // word) of one detection and walks down the output rows in blocks of 4; per block it rebuilds in LDS the rows of P its vertical taps
 // reach (the paste's two passes, mask_ops.hip), resizes them horizontally and then vertically.  The arithmetic is the paste's: the
-// coefficients of mask_resample.h, every sample (float) of the left-to-right double sum of (double)pixel * weight, one IEEE operation per
+// resampler of mask_resample.h, every sample (float) of the left-to-right double sum of (double)pixel * weight, one IEEE operation per
 // source operator (-ffp-contract=off).  The rule is stated in include/scda_ops.h and restated in numpy by tests/mask_orig_np.py.
+//
+// LDS: 4 KB plane + 17.6 KB horizontal pass of the paste + 16 KB P + 3.7 KB Q + 6.6 KB table of the paste's axes + 4.5 KB and 0.6 KB
+// tables of the second resize = 53.0 KB.
 #include "eval_prims.h"
 #include "mask_resample.h"
 
@@ -15,16 +18,14 @@ using namespace scda;
 constexpr int kMaxIn = 32;                      // largest plane side of the mask head (as mask_ops.hip)
 constexpr int kStrip = 32;                      // output columns per workgroup: one word of the packed form
 constexpr int kRows = 4;                        // output rows per block
-constexpr int kThreads = 256;
+constexpr int kThreads = kResampleThreads;
 constexpr int kRatio = 4;                       // largest down-scale n_in / n_out of the second resize the tables below hold
 constexpr int kKs2 = 2 * (2 * kRatio) + 1;      // taps per sample of the second resize: ceil(2 * ratio) * 2 + 1 = 17
 // input samples that n adjacent output samples reach: < (n - 1) * ratio + 2 * support + 1, support = 2 * ratio
 constexpr int kIC = (kStrip - 1) * kRatio + 4 * kRatio + 1;     // 141 columns of P per strip
 constexpr int kIR = (kRows - 1) * kRatio + 4 * kRatio + 1;      // 29 rows of P per block
 constexpr int kQStride = kStrip + 1;
-// weights of the paste's passes over those columns / rows: an up-scale (or identity) has at most 5 taps per sample, a down-scale at most
-// n_in taps on at most n_in - 1 samples
-constexpr int kTab1 = kIC * 5 > (kMaxIn - 1) * kMaxIn ? kIC * 5 : (kMaxIn - 1) * kMaxIn;
+constexpr int kTaps = 5;                        // table room per sample of the paste's axes: an up-scaled or equal one has 5 taps
 
 enum { FLAG_CAPACITY = 1, FLAG_EMPTY = 2, FLAG_RATIO = 4, FLAG_INPUT = 8 };
 
@@ -39,10 +40,14 @@ __global__ __launch_bounds__(kThreads) void mask_rescale_kernel(const float *__r
     __shared__ float tmp1[kMaxIn * kIC];            // the paste's horizontal pass: [ph][the columns of P this strip reaches]
     __shared__ float P[kIR * kIC];                  // the rows of P one block reaches
     __shared__ float Q[kIR * kQStride];             // their second horizontal pass: [rows][strip]
-    __shared__ double tab1[kTab1];                  // the paste's weights: horizontal before the row loop, vertical inside it
-    __shared__ double h2w[kStrip * kKs2], v2w[kRows * kKs2];
-    __shared__ int t1first[kIC], t1count[kIC], h2first[kStrip], h2count[kStrip], v2first[kRows], v2count[kRows];
+    __shared__ AxisTable<kIC, kTaps>::Lds lds1;
+    __shared__ AxisTable<kStrip, kKs2>::Lds ldsh2;
+    __shared__ AxisTable<kRows, kKs2>::Lds ldsv2;
     __shared__ int foot_s[4];
+    AxisTable<kIC, kTaps> tab1(lds1);               // the paste's taps: horizontal before the row loop, vertical inside it
+    AxisTable<kStrip, kKs2> h2(ldsh2);              // the second resize: always tabulated, FLAG_RATIO has emptied what kKs2 cannot hold
+    AxisTable<kRows, kKs2> v2(ldsv2);
+    static_assert(tab1.holds(kMaxIn), "a down-scaled axis of the largest plane fits the paste's table");
     const int r = blockIdx.y, word = blockIdx.x, oc0 = blockIdx.x * kStrip, t = threadIdx.x;
     const int b = r / per_image;
     // ---- the image (uniform over the workgroup)
@@ -63,23 +68,9 @@ __global__ __launch_bounds__(kThreads) void mask_rescale_kernel(const float *__r
     if (word == 0 && t == 0 && r % per_image == 0) status[b] = flag;
     if (flag) oh = ow = 0;                                      // an empty mask: every word below is cleared
     // ---- the RoI and its window [xa, xb) x [ya, yb) inside the h x w image
-    const float *roi = rois + (size_t)r * roi_stride;
-    int x1 = 0, y1 = 0, x2 = 0, y2 = 0;
-    bool live = !flag && !(cls && cls[r] < 0);
-    live = trunc_ok(roi[1], &x1) && live;
-    live = trunc_ok(roi[2], &y1) && live;
-    live = trunc_ok(roi[3], &x2) && live;
-    live = trunc_ok(roi[4], &y2) && live;
-    int roi_w = 0, roi_h = 0, xa = 0, xb = 0, ya = 0, yb = 0;
-    if (live) {
-        roi_w = x2 - x1 + 1; roi_h = y2 - y1 + 1;
-        live = roi_w > 0 && roi_h > 0;
-    }
-    if (live) {
-        xa = x1 > 0 ? x1 : 0; xb = min(x1 + roi_w, w);
-        ya = y1 > 0 ? y1 : 0; yb = min(y1 + roi_h, h);
-        live = xa < xb && ya < yb;
-    }
+    const RoiWindow win = read_roi_window(rois, roi_stride, cls, r, !flag);
+    int xa = 0, xb = 0, ya = 0, yb = 0;
+    bool live = win.live && win.clip_x(0, w, &xa, &xb) && win.clip_y(0, h, &ya, &yb);
     // ---- the footprint: the output samples with a tap inside the window (contiguous on both axes)
     if (t == 0) { foot_s[0] = foot_s[1] = 0x7fffffff; foot_s[2] = foot_s[3] = -1; }
     __syncthreads();
@@ -126,10 +117,9 @@ __global__ __launch_bounds__(kThreads) void mask_rescale_kernel(const float *__r
         return;
     }
     // ---- the second horizontal pass's taps of this strip and the columns [ic0, ic1) of P they reach; [pa, pb) of them lie in the window
-    const int ks2h = min(axis_ksize(w, ow), kKs2), ks2v = min(axis_ksize(h, oh), kKs2);
-    if (t < ncol) axis_taps(w, ow, oc0 + t, ks2h, &h2first[t], &h2count[t], &h2w[t * kKs2]);
+    h2.fill<true>(w, ow, oc0, ncol);
     __syncthreads();
-    const int ic0 = h2first[0], ic1 = h2first[ncol - 1] + h2count[ncol - 1], IC = ic1 - ic0;
+    const int ic0 = h2.first(0), ic1 = h2.first(ncol - 1) + h2.count(ncol - 1), IC = ic1 - ic0;
     const int pa = max(ic0, xa), pb = min(ic1, xb), np = pb - pa;
     // IC > kIC (and IR > kIR below) cannot happen: FLAG_RATIO has emptied every image with n_in > kRatio * n_out, and below that
     // IC < (kStrip - 1) * kRatio + 4 * kRatio + 1 = kIC, IR < kIR -- both tiles are DERIVED from kRatio, kStrip and kRows above, so
@@ -139,18 +129,10 @@ __global__ __launch_bounds__(kThreads) void mask_rescale_kernel(const float *__r
         return;
     }
     // ---- the paste's horizontal pass pw -> roi_w for those columns
-    const int ks1h = axis_ksize(pw, roi_w), ks1v = axis_ksize(ph, roi_h);
     for (int i = t; i < ph * pw; i += kThreads) plane[i] = planes[(size_t)r * ph * pw + i];
-    for (int i = t; i < np; i += kThreads) axis_taps(pw, roi_w, pa + i - x1, ks1h, &t1first[i], &t1count[i], &tab1[i * ks1h]);
+    tab1.fill<true>(pw, win.w, pa - win.x1, np);
     __syncthreads();
-    for (int i = t; i < ph * np; i += kThreads) {
-        const int row = i / np, xi = i - row * np;
-        const float *src = plane + row * pw + t1first[xi];
-        const double *wt = tab1 + xi * ks1h;
-        double s = 0.0;
-        for (int k = 0; k < t1count[xi]; ++k) s += (double)src[k] * wt[k];
-        tmp1[row * kIC + (pa - ic0 + xi)] = (float)s;
-    }
+    horizontal_pass(plane, pw, ph, tab1, np, tmp1, kIC, [=](int xi) { return pa - ic0 + xi; });
     // ---- down the rows: blocks before and behind the footprint hold the constant
     const int by0 = fy1 / kRows * kRows, by1 = min((fy2 / kRows + 1) * kRows, Ho);
     fill(0, by0);
@@ -158,29 +140,22 @@ __global__ __launch_bounds__(kThreads) void mask_rescale_kernel(const float *__r
     for (int oy0 = by0; oy0 < by1; oy0 += kRows) {
         const int nrow = min(kRows, oh - oy0), rend = min(oy0 + kRows, Ho);
         __syncthreads();                                        // tmp1 is complete / the previous block has been read
-        if (t < nrow) axis_taps(h, oh, oy0 + t, ks2v, &v2first[t], &v2count[t], &v2w[t * kKs2]);
+        v2.fill<true>(h, oh, oy0, nrow);
         __syncthreads();
-        const int ir0 = v2first[0], ir1 = v2first[nrow - 1] + v2count[nrow - 1], IR = ir1 - ir0;
+        const int ir0 = v2.first(0), ir1 = v2.first(nrow - 1) + v2.count(nrow - 1), IR = ir1 - ir0;
         const int qa = max(ir0, ya), qb = min(ir1, yb), nq = qb - qa;
         if (IR > kIR || nq <= 0) {
             fill(oy0, rend);
             continue;
         }
         // the paste's vertical pass ph -> roi_h for rows [qa, qb) of P; the rest of the tile is the zero plane around the window
-        for (int i = t; i < nq; i += kThreads) axis_taps(ph, roi_h, qa + i - y1, ks1v, &t1first[i], &t1count[i], &tab1[i * ks1v]);
+        tab1.fill<true>(ph, win.h, qa - win.y1, nq);
         __syncthreads();
         for (int i = t; i < IR * IC; i += kThreads) {
             const int rr = i / IC, cc = i - rr * IC;
             const int row = ir0 + rr, col = ic0 + cc;
             float v = 0.f;
-            if (row >= qa && row < qb && col >= pa && col < pb) {
-                const int ty = row - qa, n = t1count[ty];
-                const double *wt = tab1 + ty * ks1v;
-                const float *src = tmp1 + t1first[ty] * kIC + cc;
-                double s = 0.0;
-                for (int k = 0; k < n; ++k) s += (double)src[k * kIC] * wt[k];
-                v = (float)s;
-            }
+            if (row >= qa && row < qb && col >= pa && col < pb) v = tab1.dot(row - qa, tmp1 + tab1.first(row - qa) * kIC + cc, kIC);
             P[rr * kIC + cc] = v;
         }
         __syncthreads();
@@ -189,29 +164,14 @@ __global__ __launch_bounds__(kThreads) void mask_rescale_kernel(const float *__r
             const int rr = i >> 5, ci = i & 31;
             const int row = ir0 + rr;
             float v = 0.f;
-            if (ci < ncol && row >= qa && row < qb) {
-                const float *src = P + rr * kIC + (h2first[ci] - ic0);
-                const double *wt = h2w + ci * kKs2;
-                const int n = h2count[ci];
-                double s = 0.0;
-                for (int k = 0; k < n; ++k) s += (double)src[k] * wt[k];
-                v = (float)s;
-            }
+            if (ci < ncol && row >= qa && row < qb) v = h2.dot(ci, P + rr * kIC + (h2.first(ci) - ic0), 1);
             Q[rr * kQStride + ci] = v;
         }
         __syncthreads();
         // the second vertical pass h -> oh, the threshold and the store: thread = (row of the block, column of the strip)
         const int j = t >> 5, ci = t & 31;
         const bool valid = j < nrow && ci < ncol;
-        float v = 0.f;
-        if (valid) {
-            const float *src = Q + (v2first[j] - ir0) * kQStride + ci;
-            const double *wt = v2w + j * kKs2;
-            const int n = v2count[j];
-            double s = 0.0;
-            for (int k = 0; k < n; ++k) s += (double)src[k * kQStride] * wt[k];
-            v = (float)s;
-        }
+        const float v = valid ? v2.dot(j, Q + (v2.first(j) - ir0) * kQStride + ci, kQStride) : 0.f;
         if (BITS) {
             const unsigned long long set = __ballot(valid && v > threshold);      // a wave holds two rows of 32 columns
             if (ci == 0 && j < kRows && oy0 + j < rend)

@@ -111,7 +111,7 @@ def write_segm_results(writer, image_info, image_ids, out, category_of=None, inp
     input_resolution=True and then gets box AND mask of such an image at the network-input resolution (the box NOT divided by
     resize_scale, so the two agree) and rescales them himself.
 
-    A pass of Predictor(masks=True, rle=True, original_size=(Ho, Wo)) carries that second resize (infer.OriginalSizeResult): its lines
+    A pass of Predictor(masks=True, rle=True, original_size=(Ho, Wo)) carries that second resize (its mask_bits_orig): its lines
     are the reference's for any resize_scale -- `bbox` from det_orig (the box divided by resize_scale in float32, :408), `segmentation`
     the RLE of the mask resized to the original size and thresholded there with `>` (:422-423), 'size' = [origin_h, origin_w].
     input_resolution=True has no meaning for such a pass (ValueError); an image beyond the device limits (orig_status) raises ValueError."""
@@ -119,7 +119,7 @@ def write_segm_results(writer, image_info, image_ids, out, category_of=None, inp
     info = _np(image_info)
     if info.ndim != 2 or info.shape[1] < 3 or len(image_ids) != info.shape[0]:
         raise ValueError("write_segm_results: image_info [B, >=3] and B image ids")
-    original = isinstance(out, infer.OriginalSizeResult)
+    original = getattr(out, 'mask_bits_orig', None) is not None
     if original and input_resolution:
         raise ValueError("write_segm_results: the pass carries original-size results; input_resolution=True does not apply to it")
     if not input_resolution and not original:
@@ -152,13 +152,12 @@ def write_keypoint_results(writer, image_info, image_ids, out, category_of=None,
     float32 (:408), `score`, `category_id` (category_of(class), default the class index) and `keypoints` = the detection's
     keypoints_orig row flattened to 3 Kp numbers (x, y divided by resize_scale, :417; the third value of each keypoint is the raw
     resized heat-map value).  image_info [B, >=3] rows (h, w, resize_scale, ...); image_ids: B ids.  `out`: the pass's result tuple (its
-    last two entries are keypoints, keypoints_orig) or an OriginalSizeResult of a pass that also had original_size."""
-    from scda_amd import infer
+    last two entries are keypoints, keypoints_orig; an infer.PredictorResult names them)."""
     info = _np(image_info)
     if info.ndim != 2 or info.shape[1] < 3 or len(image_ids) != info.shape[0]:
         raise ValueError("write_keypoint_results: image_info [B, >=3] and B image ids")
-    original = isinstance(out, infer.OriginalSizeResult)
-    kps = _np(out.keypoints_orig if original else out[-1])
+    named = getattr(out, 'keypoints_orig', None)
+    kps = _np(out[-1] if named is None else named)
     det, det_counts = _np(out[2]), _np(out[3])
     if kps.ndim != 4 or kps.shape[:2] != det.shape[:2] or kps.shape[3] != 3:
         raise ValueError("write_keypoint_results: the pass carries no keypoints (Predictor(keypoints=True))")

@@ -60,22 +60,41 @@ def _sections(cfg):
     return rpn, box
 
 
-class OriginalSizeResult(tuple):
-    """The output tuple of a Predictor(original_size=...) pass.  Entries 0..4 (and 5 with rle=True) stand where they stand without
-    original_size; the new entries follow them and also have names: .mask_bits_orig int32 [B, top_n, Ho, ceil(Wo/32)], .det_orig
-    float32 [B, top_n, 7], .orig_status int32 [B] (0 = fine, see include/scda_ops.h), and .rle (entry 5, the run-length results of
-    mask_bits_orig; None without rle=True)."""
+class PredictorResult(tuple):
+    """The output tuple of a Predictor pass.  Entries 0..3 are proposals, proposal_counts, detections, detection_counts; every option
+    appends its entries behind them in the order masks (mask_bits), rle (the run-length dict, entry 5), original_size (mask_bits_orig
+    int32 [B, top_n, Ho, ceil(Wo/32)], det_orig float32 [B, top_n, 7], orig_status int32 [B], 0 = fine, see include/scda_ops.h),
+    keypoints (keypoints, keypoints_orig).  Every entry is also an attribute of the name in FIELDS; one the pass does not carry is None."""
+    FIELDS = ('proposals', 'proposal_counts', 'detections', 'detection_counts', 'mask_bits', 'rle', 'mask_bits_orig', 'det_orig',
+              'orig_status', 'keypoints', 'keypoints_orig')
 
-    def __new__(cls, entries, names):
+    def __new__(cls, entries=(), names=()):
         self = super().__new__(cls, entries)
-        self._names = dict(names)
+        self._names = dict(names)                           # name -> position (None: absent)
         return self
 
+    def plus(self, **named):
+        """this result with the named entries appended"""
+        n = len(self)
+        return PredictorResult(tuple(self) + tuple(named.values()), dict(self._names, **{k: n + i for i, k in enumerate(named)}))
+
     def __getattr__(self, name):
-        names = self.__dict__.get('_names', {})
-        if name in names:
-            return None if names[name] is None else self[names[name]]
+        at = self.__dict__.get('_names', {}).get(name)
+        if at is not None:
+            return self[at]
+        if name in self.FIELDS:
+            return None
         raise AttributeError(name)
+
+
+OriginalSizeResult = PredictorResult                        # the name of the result of an original_size pass before every pass had one
+
+
+def _need_pillow7(what):
+    import PIL
+    if int(PIL.__version__.split(".")[0]) < 7:
+        raise ValueError("device %s path: Pillow %s resizes with NEAREST by default; the device path restates Pillow >= 7's BICUBIC "
+                         "default -- use predict_%ss on the host" % (what, PIL.__version__, what))
 
 
 def _check_status(status, what):
@@ -109,7 +128,7 @@ class Predictor:
     width); a default, not a guarantee: segm_rows encodes an overflowing mask on the host.
 
     original_size=(Ho, Wo) (with masks=True; image_info [B, >= 5] = (h, w, resize_scale, origin_h, origin_w)): the capacity of the
-    original-size planes.  The result becomes an OriginalSizeResult: today's entries where they are, then mask_bits_orig int32
+    original-size planes.  The result (a PredictorResult, as of every pass) grows behind the entries above by mask_bits_orig int32
     [B, top_n, Ho, ceil(Wo/32)] -- bit = (the pasted float plane of the image's (h, w), resized by Pillow's rule to (origin_h, origin_w),
     > mask_threshold), zero outside origin_h x origin_w --, det_orig float32 [B, top_n, 7] = the detections with their box divided by
     resize_scale in float32, and orig_status int32 [B], non-zero for an image beyond the kernel's limits (its masks are empty).  With
@@ -127,8 +146,8 @@ class Predictor:
     the result grows by TWO entries, appended after every other one: keypoints float32 [B, top_n, Kp, 3] = (x, y, score) per detection
     and keypoint at the network input's coordinates (the rule: include/scda_ops.h, scda_keypoint_decode_hip; score = the raw resized
     heat-map value), and keypoints_orig, the same with x and y divided in float32 by resize_scale (tools/mask_rcnn_train_val.py:417, as
-    det_orig divides its boxes).  Rows of padding detections are zero.  With original_size the two are also named: .keypoints,
-    .keypoints_orig.  The heat maps the decode read stay reachable as `pred.keypoint_heat` ([B * top_n, Kp, 56, 56], a view) until the
+    det_orig divides its boxes).  Rows of padding detections are zero.  The two are also named: .keypoints, .keypoints_orig.  The
+    heat maps the decode read stay reachable as `pred.keypoint_heat` ([B * top_n, Kp, 56, 56], a view) until the
     next pass.  Fixed buffers per shape, two more launches behind the head, no additional wait for the host."""
 
     def __init__(self, model, cfg, masks=False, mask_threshold=0.5, rle=False, rle_capacity=None, soft_nms=None, original_size=None,
@@ -150,18 +169,12 @@ class Predictor:
         if self.masks:
             if not getattr(model, 'with_mask', False):
                 raise ValueError("Predictor: masks=True needs a detector with the mask branch (cfg with_mask)")
-            import PIL
-            if int(PIL.__version__.split(".")[0]) < 7:
-                raise ValueError("device mask path: Pillow %s resizes with NEAREST by default; the device path restates Pillow >= 7's "
-                                 "BICUBIC default -- use predict_masks on the host" % PIL.__version__)
+            _need_pillow7("mask")
         self.keypoints = bool(keypoints)
         if self.keypoints:
             if not getattr(model, 'with_keypoint', False):
                 raise ValueError("Predictor: keypoints=True needs a detector with the keypoint branch (cfg with_keypoint)")
-            import PIL
-            if int(PIL.__version__.split(".")[0]) < 7:
-                raise ValueError("device keypoint path: Pillow %s resizes with NEAREST by default; the device path restates Pillow >= "
-                                 "7's BICUBIC default -- use predict_keypoints on the host" % PIL.__version__)
+            _need_pillow7("keypoint")
         self.keypoint_heat = None
         self.model, self.cfg = model, cfg
         self.rpn_cfg, self.box_cfg = _sections(cfg)
@@ -338,26 +351,23 @@ class Predictor:
         N.box_predict(self.rois, self.counts, cprob, bloc.detach().contiguous(), info, bc['bbox_normalize_stds'],
                       bc['bbox_normalize_means'], float(bc['score_thresh']), float(bc['nms_iou_thresh']), self.top_n, self.box_ws,
                       self.det, self.det_counts, soft_nms=self.soft_nms)
-        self._out = (self.props.view(B, self.P, 6), self.counts, self.det, self.det_counts)
+        H, W = images.shape[2:]
+        out = PredictorResult().plus(proposals=self.props.view(B, self.P, 6), proposal_counts=self.counts, detections=self.det,
+                                     detection_counts=self.det_counts)
         if self.masks:
-            self._out += (self._masks(feat, B, images.shape[2], images.shape[3]),)
+            out = out.plus(mask_bits=self._masks(feat, B, H, W))
         if self.original_size is not None:
-            self._orig(info, B, images.shape[2], images.shape[3])
+            self._orig(info, B, H, W)
             if self.rle:
-                self._out += (self._rle_orig(info, B),)
-            n = len(self._out)
-            self._out = OriginalSizeResult(self._out + (self.mask_bits_orig, self.det_orig, self.orig_status),
-                                           {'mask_bits_orig': n, 'det_orig': n + 1, 'orig_status': n + 2, 'rle': 5 if self.rle else None})
+                out = out.plus(rle=self._rle_orig(info, B))
+            out = out.plus(mask_bits_orig=self.mask_bits_orig, det_orig=self.det_orig, orig_status=self.orig_status)
         elif self.rle:
-            self._out += (self._rle(info, B, images.shape[2], images.shape[3]),)
+            out = out.plus(rle=self._rle(info, B, H, W))
         if self.keypoints:
-            kp = self._keypoints(feat, info, B, images.shape[2], images.shape[3])
-            if isinstance(self._out, OriginalSizeResult):
-                n = len(self._out)
-                self._out = OriginalSizeResult(tuple(self._out) + kp, dict(self._out._names, keypoints=n, keypoints_orig=n + 1))
-            else:
-                self._out += kp
-        return self._out
+            kp, kp_orig = self._keypoints(feat, info, B, H, W)
+            out = out.plus(keypoints=kp, keypoints_orig=kp_orig)
+        self._out = out
+        return out
 
     def capture(self, images, image_info):
         """record one pass over static copies of (images, image_info) into a graph (call once eagerly first); returns the outputs"""
@@ -391,19 +401,14 @@ def predict(model, images, image_info, cfg, masks=False, mask_threshold=0.5, rle
     masks=True: a fifth tensor, mask_bits int32 [B,top_n,H,ceil(W/32)] (see Predictor); rle=True on top: a sixth element, the dict of
     run-length results (see Predictor, segm_rows).
     soft_nms: see Predictor (a dict; None = the cfg's own `soft_nms` key, if any).
-    original_size=(Ho, Wo): see Predictor; the result is then an OriginalSizeResult (image_info [B,>=5]).
+    original_size=(Ho, Wo): see Predictor; three more entries, mask_bits_orig, det_orig and orig_status (image_info [B,>=5]).
     keypoints=True: see Predictor; two more entries at the end, keypoints and keypoints_orig float32 [B,top_n,Kp,3] (image_info [B,>=3]).
-    One Predictor per (model, cfg, masks, mask_threshold, rle, rle_capacity, soft_nms, original_size) is kept and reused; its buffers are overwritten by
-    the next call."""
-    key = (id(model), id(cfg)) if not masks else (id(model), id(cfg), True, float(mask_threshold))
-    if rle:
-        key += ('rle', rle_capacity)
-    if soft_nms is not None:
-        key += ('soft_nms', N.soft_nms_setting(soft_nms))
-    if original_size is not None:
-        key += ('original_size', int(original_size[0]), int(original_size[1]))
-    if keypoints:
-        key += ('keypoints',)
+    The result is a PredictorResult: the tuple above, every entry also reachable by name.
+    One Predictor per (model, cfg, masks, mask_threshold with masks, rle, rle_capacity with rle, soft_nms, original_size, keypoints) is
+    kept and reused; its buffers are overwritten by the next call."""
+    key = (id(model), id(cfg), bool(masks), float(mask_threshold) if masks else None, bool(rle), rle_capacity if rle else None,
+           None if soft_nms is None else N.soft_nms_setting(soft_nms),
+           None if original_size is None else (int(original_size[0]), int(original_size[1])), bool(keypoints))
     p = _PREDICTORS.get(key)
     if p is None or p.model is not model:
         p = _PREDICTORS[key] = Predictor(model, cfg, masks=masks, mask_threshold=mask_threshold, rle=rle, rle_capacity=rle_capacity,
@@ -464,12 +469,12 @@ def segm_rows(out, with_fallbacks=False):
     is encoded here from its own plane of mask_bits by scda_amd.mask_rle_host (the same rule, the same bytes); their number is logged and,
     with with_fallbacks=True, returned as a second value.  This call waits for the device.  What crosses to the host: 28 bytes per
     detection slot, 12 per image, each image's strings (its real detections x the longest of them) and one plane per fallback.
-    The result of a pass with original_size (an OriginalSizeResult): the same at the ORIGINAL image size -- 'size' = [origin_h, origin_w],
-    the masks those of mask_bits_orig; ValueError for an image whose orig_status is set."""
+    The result of a pass with original_size (it carries mask_bits_orig): the same at the ORIGINAL image size -- 'size' = [origin_h,
+    origin_w], the masks those of mask_bits_orig; ValueError for an image whose orig_status is set."""
     import logging
     from scda_amd import mask_rle_host
     det_counts, mask_bits, rle = out[3], out[4], out[5]
-    if isinstance(out, OriginalSizeResult):
+    if getattr(out, 'mask_bits_orig', None) is not None:
         if out.rle is None:
             raise ValueError("segm_rows: the pass has no run-length results (Predictor(rle=True))")
         _check_status(out.orig_status, "segm_rows")

@@ -540,20 +540,26 @@ def mask_select(logits, cls, sigmoid=False, out=None):
 MASK_PLANE_MAX = 32
 
 
+def _check_windows(who, rois, planes, ndim, what, noun, cls, max_side):
+    """the common arguments of the kernels that resize a plane to its RoI window (dtypes and devices of rois and planes already
+    checked): rois [R, >=5], planes [R, ..., h, w] of ndim axes with h, w <= max_side, cls None or int32 [R]"""
+    if rois.dim() != 2 or rois.shape[1] < 5 or planes.dim() != ndim or planes.shape[0] != rois.shape[0]:
+        raise ValueError("%s: rois must be [R, >=5] and %s" % (who, what))
+    if max(planes.shape[-2:]) > max_side:
+        raise ValueError("%s: %s of at most %d x %d" % (who, noun, max_side, max_side))
+    if cls is not None:
+        _req(cls, "cls", torch.int32)
+        if cls.numel() != rois.shape[0]:
+            raise ValueError("%s: cls must be [R]" % who)
+
+
 def mask_paste(rois, planes, H, W, cls=None, packed=False, threshold=0.5, out=None):
     """functions/mask.py:21-49 on the device (include/scda_ops.h states the rule): rois [R, >=5] (b, x1, y1, x2, y2, ...), planes
     [R, h, w] -> float32 [R, H, W], or with packed=True uint32 [R, H, ceil(W/32)] of (value >= threshold), stored as int32.  Rows
     with cls < 0 give an empty mask; the part of a window outside the plane is dropped.  Every element of `out` is written."""
     _req(rois, "rois"); _req(planes, "planes")
-    if rois.dim() != 2 or rois.shape[1] < 5 or planes.dim() != 3 or planes.shape[0] != rois.shape[0]:
-        raise ValueError("mask_paste: rois must be [R, >=5] and planes [R, h, w]")
+    _check_windows("mask_paste", rois, planes, 3, "planes [R, h, w]", "planes", cls, MASK_PLANE_MAX)
     R, h, w = planes.shape
-    if h > MASK_PLANE_MAX or w > MASK_PLANE_MAX:
-        raise ValueError("mask_paste: planes of at most %d x %d" % (MASK_PLANE_MAX, MASK_PLANE_MAX))
-    if cls is not None:
-        _req(cls, "cls", torch.int32)
-        if cls.numel() != R:
-            raise ValueError("mask_paste: cls must be [R]")
     H, W = int(H), int(W)
     shape, dtype = ((R, H, (W + 31) // 32), torch.int32) if packed else ((R, H, W), torch.float32)
     if out is None:
@@ -582,17 +588,10 @@ def keypoint_decode(rois, heat, H, W, cls=None, out=None, ws=None):
     _req(rois, "rois")
     if not isinstance(heat, torch.Tensor) or not heat.is_cuda or heat.dtype != torch.float32:
         raise ScdaNativeError("heat must be a float32 tensor on the HIP device; there is no CPU path")
-    if rois.dim() != 2 or rois.shape[1] < 5 or heat.dim() != 4 or heat.shape[0] != rois.shape[0]:
-        raise ValueError("keypoint_decode: rois must be [R, >=5] and heat [R, Kp, h, w]")
+    _check_windows("keypoint_decode", rois, heat, 4, "heat [R, Kp, h, w]", "heat maps", cls, KEYPOINT_PLANE_MAX)
     R, Kp, h, w = heat.shape
-    if h > KEYPOINT_PLANE_MAX or w > KEYPOINT_PLANE_MAX:
-        raise ValueError("keypoint_decode: heat maps of at most %d x %d" % (KEYPOINT_PLANE_MAX, KEYPOINT_PLANE_MAX))
     if min(heat.stride()) < 0:
         raise ValueError("keypoint_decode: negative strides")
-    if cls is not None:
-        _req(cls, "cls", torch.int32)
-        if cls.numel() != R:
-            raise ValueError("keypoint_decode: cls must be [R]")
     H, W = int(H), int(W)
     if out is None:
         out = torch.empty(R, Kp, 3, dtype=torch.float32, device=rois.device)
@@ -625,18 +624,11 @@ def mask_rescale(rois, planes, H, W, image_info, Ho, Wo, cls=None, packed=False,
     rectangle outside which nothing was computed -- mask_rle's `rois` hint when threshold >= 0 --, status int32 [B], non-zero for an image
     beyond the limits, whose masks are empty).  Every element of the three is written.  No wait for the host."""
     _req(rois, "rois"); _req(planes, "planes"); _req(image_info, "image_info")
-    if rois.dim() != 2 or rois.shape[1] < 5 or planes.dim() != 3 or planes.shape[0] != rois.shape[0]:
-        raise ValueError("mask_rescale: rois must be [R, >=5] and planes [R, h, w]")
+    _check_windows("mask_rescale", rois, planes, 3, "planes [R, h, w]", "planes", cls, MASK_PLANE_MAX)
     R, h, w = planes.shape
-    if h > MASK_PLANE_MAX or w > MASK_PLANE_MAX:
-        raise ValueError("mask_rescale: planes of at most %d x %d" % (MASK_PLANE_MAX, MASK_PLANE_MAX))
     if image_info.dim() != 2 or image_info.shape[1] < 5 or image_info.shape[0] < 1 or R % image_info.shape[0]:
         raise ValueError("mask_rescale: image_info must be [B, >=5] (h, w, resize_scale, origin_h, origin_w) with R a multiple of B")
     B = image_info.shape[0]
-    if cls is not None:
-        _req(cls, "cls", torch.int32)
-        if cls.numel() != R:
-            raise ValueError("mask_rescale: cls must be [R]")
     H, W, Ho, Wo = int(H), int(W), int(Ho), int(Wo)
     if min(H, W, Ho, Wo) < 1:
         raise ValueError("mask_rescale: H, W, Ho, Wo must be >= 1")

@@ -15,14 +15,11 @@ import torch.nn.functional as F
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "golden"))
 import make_golden_keypoints as gk  # noqa: E402
+from gpu_arrays import bits as _bits, dev as _dev  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 KP = 17
-
-
-def _dev(a, cuda):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(cuda)
 
 
 def _tall(heat, cuda):
@@ -31,10 +28,6 @@ def _tall(heat, cuda):
     t = _dev(heat.transpose(1, 0, 2, 3), cuda).view(Kp, R, h, w).transpose(0, 1)
     assert not t.is_contiguous() and tuple(t.shape) == heat.shape
     return t
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def test_decode_equals_reference_golden(cuda, golden_dir):

@@ -8,22 +8,10 @@ import pytest
 import torch
 
 import mask_cases as mcases
+from gpu_arrays import dev as _dev, unpack as _unpack, words as _words
 from test_mask_infer_rules import own_planes, pack_statement, paste_statement
 
 pytestmark = pytest.mark.gpu
-
-
-def _dev(a, cuda):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(cuda)
-
-
-def _words(t):
-    return t.cpu().numpy().view(np.uint32)
-
-
-def _unpack(words, W):
-    """uint32 [..., Wd] -> bool [..., W]"""
-    return np.unpackbits(np.ascontiguousarray(words).view(np.uint8), axis=-1, bitorder='little')[..., :W].astype(bool)
 
 
 def sigmoid_statement(x):

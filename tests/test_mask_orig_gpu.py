@@ -16,20 +16,13 @@ import torch
 import coco_eval_np as cnp
 import mask_orig_np as O
 import mask_rle_np as RLE
+from gpu_arrays import dev as _dev, words as _words
 from test_mask_infer_rules import own_planes, paste_statement
 
 pytestmark = pytest.mark.gpu
 
 H, W = 96, 160
 N_CASES = 8
-
-
-def _dev(a, cuda):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(cuda)
-
-
-def _words(t):
-    return t.cpu().numpy().view(np.uint32)
 
 
 @pytest.fixture(scope="module")
@@ -256,7 +249,8 @@ def test_existing_entries_unchanged_and_predict_passes_the_argument(cuda, whole_
     from scda_amd import infer
     p = whole_pass
     plain = infer.Predictor(p['det'], p['cfg'], masks=True, rle=True)(p['x'], p['info'])
-    assert type(plain) is tuple and len(plain) == 6
+    assert type(plain) is infer.PredictorResult and isinstance(plain, tuple) and len(plain) == 6
+    assert plain.rle is plain[5] and plain.mask_bits is plain[4] and plain.mask_bits_orig is None and plain.orig_status is None
     for i in range(5):
         assert torch.equal(plain[i], p['out'][i]), i
     assert np.array_equal(plain[5]['size'].cpu().numpy(), [[256, 400], [240, 384]])      # without original_size: the input resolution
