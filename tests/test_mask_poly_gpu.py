@@ -7,19 +7,13 @@ import pytest
 import torch
 
 import mask_poly_np as mp
+from gpu_arrays import pack as _pack
 from scda_amd import coco_gt
 from test_mask_poly_rules import annotation_of, fixture_cases
 
 pytestmark = pytest.mark.gpu
 
 EMPTY_AT = (0, 17, 101)                         # images without an annotation, put between the cases: planes that nothing maps to
-
-
-def _pack(mask, H, Wd):
-    """bool [h, w] -> uint32 [H, Wd], zero outside the image"""
-    full = np.zeros((H, Wd * 32), dtype=np.uint8)
-    full[:mask.shape[0], :mask.shape[1]] = mask
-    return np.packbits(full, axis=-1, bitorder='little').view(np.uint32).reshape(H, Wd)
 
 
 _RUNS = {}

@@ -7,32 +7,10 @@ import pytest
 import torch
 
 import mask_rle_np as R
+from gpu_arrays import check_mask as _check_mask, dev as _dev, dev_words as _bits, host as _host
 from test_mask_rle_rules import GROUPS, IOU_SETS, fixture_cases, iou_set
 
 pytestmark = pytest.mark.gpu
-
-
-def _dev(a, cuda):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(cuda)
-
-
-def _bits(a, cuda):
-    return _dev(np.ascontiguousarray(a).view(np.int32), cuda)
-
-
-def _host(out):
-    return {k: v.cpu().numpy() for k, v in out.items()}
-
-
-def _check_mask(got, r, want, where):
-    """one mask of a mask_rle result against {'n_runs', 'counts', 'chars', 'area', 'bbox'}"""
-    n = int(got['n_runs'][r])
-    assert n == want['n_runs'], (where, n, want['n_runs'])
-    assert np.array_equal(got['counts'][r, :n].view(np.uint32), want['counts']), where
-    nb = int(got['n_bytes'][r])
-    assert got['chars'][r, :nb].tobytes() == want['chars'], where
-    assert int(got['area'][r].view(np.uint32)) == want['area'], where
-    assert got['bbox'][r].view(np.uint32).tolist() == want['bbox'], (where, got['bbox'][r], want['bbox'])
 
 
 @pytest.mark.parametrize("group", GROUPS)
