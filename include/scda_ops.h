@@ -413,6 +413,38 @@ int scda_keypoint_decode_hip(const float *rois, int roi_stride, const int *cls_o
                              long long stride_k, long long stride_h, long long stride_w, int R, int Kp, int ph, int pw, int H, int W,
                              void *workspace, float *out, void *stream);
 
+/* ---- training the keypoint branch: the heat-map loss (scda_amd/csrc/keypoint_loss.hip; scda_amd.autograd_ops.keypoint_heatmap_loss) ----
+ * PROVENANCE.  The reference's keypoint targets and loss are in its missing models/mask_rcnn/mask_rcnn.py; its driver only names the
+ * contract (tools/mask_rcnn_train_val.py:309-329: 'ground_truth_keypoints' [b, max_gts, K, 3] in, a fifth loss out).  THE TARGET RULE AND
+ * THE LOSS BELOW ARE OUR CHOICE, parity unpinned.
+ *
+ * The target rule (host code, dropin.functions.mask.compute_keypoint_targets) is the inverse of the decode above, which resizes a map to
+ * a window of roi_w x roi_h pixels.  With M_w x M_h the map size, (x1, y1, x2, y2) the integer-clipped RoI, roi_w = x2 - x1 + 1,
+ * roi_h = y2 - y1 + 1 and (kx, ky, v) the keypoint of the RoI's matched ground truth, in float64:
+ *   the pair (RoI, keypoint) is COUNTED iff v > 0 and x1 <= kx < x2 + 1 and y1 <= ky < y2 + 1;
+ *   then bx = min(floor((kx - x1) * M_w / roi_w), M_w - 1), by likewise with y, and target = by * M_w + bx;
+ *   every other pair has target -1.
+ *
+ * The loss is the soft-max cross-entropy over the HW positions of each counted map (the Mask R-CNN keypoint loss), averaged over the
+ * counted pairs:  row_loss = logsumexp(map) - map[target];  out2[0] = sum of row_loss over counted pairs / their number, out2[1] = that
+ * number; with no counted pair out2 = (0, 0) and the gradient is all zeros (no division by zero, no NaN).  A target outside [0, HW) is
+ * uncounted, whatever its value.
+ *
+ * heat float32: R x Kp planes of HW contiguous elements each, plane (r, k) at heat + r * stride_r + k * stride_k (ELEMENT strides, >= 0:
+ * [R, Kp, h, w], or the transposed channel-major view of the keypoint head, taken as it is).  1 <= HW <= 4096 (the decode's 64 x 64
+ * limit; anything larger returns SCDA_EINVAL and nothing is launched).  targets int32 [R * Kp].  stats float32 [R * Kp * 2]: (max,
+ * log of the sum of exp(x - max)) per counted map, (0, 0) per uncounted one; row_loss float32 [R * Kp] (0 for uncounted maps); both are
+ * fully written.  Forward: one workgroup per map, which reads its map once (uncounted maps are not read), then one single-workgroup
+ * launch sums row_loss in a fixed order.  Backward: dheat plane (r, k) at dheat + r * dstride_r + k * dstride_k gets
+ * (exp(x - max - logsum) - onehot(target)) * grad_scalar[0] / out2[1] for counted maps and exactly 0.0f for uncounted ones; every plane
+ * is fully written, nothing between planes is touched.  grad_scalar: one float32 on the device.  No atomics: the same input gives the
+ * same bytes on every launch; graph-capturable. */
+int scda_keypoint_ce_fwd_hip(const float *heat, long long stride_r, long long stride_k, int R, int Kp, int HW, const int *targets,
+                             float *stats, float *row_loss, float *out2, void *stream);
+int scda_keypoint_ce_bwd_hip(const float *heat, long long stride_r, long long stride_k, int R, int Kp, int HW, const int *targets,
+                             const float *stats, const float *out2, const float *grad_scalar, float *dheat, long long dstride_r,
+                             long long dstride_k, void *stream);
+
 /* ---- COCO run-length results from packed masks (scda_amd/csrc/mask_rle.hip; opt-in: scda_amd.infer.Predictor(masks=True, rle=True)) ----
  * The per-mask primitives of the reference's datasets/pycocotools/common/maskApi.c on scda_mask_paste_hip's packed planes, bit for bit
  * (integers below 2^32 and one IEEE double division; no atomics: two runs give the same bytes).  tests/mask_rle_np.py restates the

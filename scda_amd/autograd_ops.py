@@ -388,6 +388,23 @@ class SoftmaxCEFn(Function):
         return N.softmax_ce_bwd(probs, targets, out2, _c(g).reshape(1), ctx.ignore), None, None
 
 
+class KeypointCEFn(Function):
+    """The keypoint heat-map loss: heat [R, Kp, h, w] (any R / Kp strides, planes contiguous), targets int32 [R, Kp] (-1: not
+    counted) -> the mean over the counted pairs of logsumexp(map) - map[target].  No copy either way: the kernels take the head's
+    transposed channel-major view as it is and the gradient comes back with the input's strides."""
+
+    @staticmethod
+    def forward(ctx, heat, targets):
+        out2, stats, _ = N.keypoint_ce_fwd(heat, targets)
+        ctx.save_for_backward(heat, targets, stats, out2)
+        return out2[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        heat, targets, stats, out2 = ctx.saved_tensors
+        return N.keypoint_ce_bwd(heat, targets, stats, out2, _c(g).reshape(1)), None
+
+
 class SmoothL1Fn(Function):
     """smooth_l1_loss_with_sigma(pred*mask, target, sigma) * scale -> 0-dim loss"""
 
@@ -613,6 +630,11 @@ def adversarial_loss(groups, scale=1.0):
 
 def cross_entropy(logits, targets, ignore_index=-100):
     return SoftmaxCEFn.apply(logits, targets, ignore_index)
+
+
+def keypoint_heatmap_loss(heat, targets):
+    """heat [R, Kp, h, w] on the device, targets int32 [R, Kp] on the device (by * w + bx, or -1) -> 0-dim loss (include/scda_ops.h)"""
+    return KeypointCEFn.apply(heat, targets)
 
 
 def smooth_l1_sum(pred, mask, target, sigma=3.0, scale=1.0):

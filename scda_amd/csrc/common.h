@@ -37,6 +37,43 @@ static inline int ew_grid(long long n, int block = 256) {
 
 constexpr int kWave = 64;  // gfx950 wavefront
 
+// ---- workgroup reductions of the layer and loss kernels (nn_ops.hip, keypoint_loss.hip): fixed-shape trees, no float atomics ----
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    return v;
+}
+
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_down(v, o, 64));
+    return v;
+}
+
+// sum over the workgroup; result valid in every thread. blockDim.x multiple of 64, <= 1024
+__device__ __forceinline__ float block_sum(float v, float *red /* >= 16 floats of LDS */) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    v = wave_sum(v);
+    __syncthreads();  // protect red[] against a previous use
+    if (lane == 0) red[wave] = v;
+    __syncthreads();
+    float t = 0.f;
+    for (int i = 0; i < nw; ++i) t += red[i];  // fixed order -> deterministic
+    return t;
+}
+
+// maximum over the workgroup, as block_sum (fmaxf: a NaN loses against a number)
+__device__ __forceinline__ float block_max(float v, float *red /* >= 16 floats of LDS */) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    v = wave_max(v);
+    __syncthreads();
+    if (lane == 0) red[wave] = v;
+    __syncthreads();
+    float t = red[0];
+    for (int i = 1; i < nw; ++i) t = fmaxf(t, red[i]);
+    return t;
+}
+
 // in-register transpose of a 32 x 32 bit block (mask_rle.hip, mask_poly.hip): afterwards a[j] bit i = (before) a[i] bit j
 __host__ __device__ inline void transpose32(uint32_t a[32]) {
     uint32_t m = 0x0000ffffu;

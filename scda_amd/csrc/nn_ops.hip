@@ -9,24 +9,7 @@
 
 namespace scda {
 
-// ------------------------------------------------------------ reductions ----
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-
-// sum over the workgroup; result valid in every thread. blockDim.x multiple of 64, <= 1024
-__device__ __forceinline__ float block_sum(float v, float *red /* >= 16 floats of LDS */) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    v = wave_sum(v);
-    __syncthreads();  // protect red[] against a previous use
-    if (lane == 0) red[wave] = v;
-    __syncthreads();
-    float t = 0.f;
-    for (int i = 0; i < nw; ++i) t += red[i];  // fixed order -> deterministic
-    return t;
-}
+// (reductions: wave_sum / block_sum of common.h)
 
 // ------------------------------------------------------------- max pool -----
 // 2x2 stride 2 (models/faster_rcnn/vgg_adver_expansion_cluster.py:106). idx: 0..3 = winner (dy*2+dx)

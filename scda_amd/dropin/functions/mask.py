@@ -160,22 +160,19 @@ def generate_mask_labels(rois, masks, mask_h, mask_w, index=None):
     return np.clip(out, 0, 255).astype(np.int32)
 
 
-def compute_mask_targets(proposals, cfg, ground_truth_bboxes, ground_truth_masks, image_info, ignore_regions=None):
-    """proposals [N, >=5] (b, x1, y1, x2, y2, ...), gts [B, G, >=5], gt masks [B, G, H, W] ->
-    rois [R, 6] fp32 (b, x1, y1, x2, y2, class) and labels [R, num_classes, label_h, label_w] fp32 (-1 = ignore; the RoI's own
-    class plane holds its 0/1 mask).  functions/mask.py:73-179: RoIs with IoU > positive_iou_thresh, integer-clipped, at most
-    batch_size_per_image per image (np.random.choice without replacement -- the only RNG draw)."""
+def _positive_rois(proposals, cfg, gts_all, image_info):
+    """The RoI selection of functions/mask.py:97-131, shared by the mask and the keypoint targets (numpy arrays in): per image with a
+    positive RoI yields (b_ix, pos_rois int32 [n, 4], gts [g, >=5] after the padded-gt filter, pos_g [n] into those gts, keep [g] into
+    the image's unfiltered gts).  RoIs with IoU > positive_iou_thresh, integer-clipped, at most batch_size_per_image per image
+    (np.random.choice without replacement -- the only RNG draw)."""
     from scda_amd.dropin.utils import bbox_helper
-    dev = proposals.device if torch.is_tensor(proposals) else torch.device("cpu")
-    proposals, gts_all, masks_all, image_info = (np.asarray(_np(v)) for v in (proposals, ground_truth_bboxes, ground_truth_masks, image_info))
-    batch_rois, batch_labels = [], []
     for b_ix in range(gts_all.shape[0]):
         rois = proposals[proposals[:, 0] == b_ix][:, 1:5]
-        gts, masks = gts_all[b_ix], masks_all[b_ix]
+        gts = gts_all[b_ix]
         keep = np.where(gts[:, 2] > gts[:, 1] + 1)[0]              # the reference's padded-gt filter (:108), as written
         if keep.size == 0:
             continue
-        gts = gts[keep]                                            # (the mask planes stay where they are: `keep` indexes them)
+        gts = gts[keep]
         if cfg['append_gts']:
             rois = np.vstack([rois, gts[:, :4]])
         rois = bbox_helper.clip_bbox(rois.astype(np.int32), image_info[b_ix].astype(np.int32))
@@ -190,7 +187,58 @@ def compute_mask_targets(proposals, cfg, ground_truth_bboxes, ground_truth_masks
         if 0 < cfg['batch_size_per_image'] < pos_r.shape[0]:
             pick = np.random.choice(pos_r.shape[0], size=cfg['batch_size_per_image'], replace=False)
             pos_r, pos_g = pos_r[pick], pos_g[pick]
-        pos_rois = rois[pos_r]
+        yield b_ix, rois[pos_r], gts, pos_g, keep
+
+
+def keypoint_target_bins(rois, keypoints, label_w, label_h):
+    """The target rule alone: integer RoIs [n, 4] (x1, y1, x2, y2) and their matched ground truths' keypoints [n, Kp, 3] rows
+    (x, y, v) -> int32 [n, Kp]: by * label_w + bx of a counted pair, -1 otherwise (`compute_keypoint_targets` states the rule)"""
+    kp = np.asarray(keypoints, dtype=np.float64)
+    x1, y1, x2, y2 = (np.asarray(rois)[:, c].astype(np.float64)[:, None] for c in range(4))
+    roi_w, roi_h = x2 - x1 + 1.0, y2 - y1 + 1.0
+    kx, ky, v = kp[..., 0], kp[..., 1], kp[..., 2]
+    counted = (v > 0) & (kx >= x1) & (kx < x2 + 1.0) & (ky >= y1) & (ky < y2 + 1.0)
+    with np.errstate(invalid='ignore', over='ignore', divide='ignore'):
+        bx = np.minimum(np.floor((kx - x1) * label_w / roi_w), label_w - 1)
+        by = np.minimum(np.floor((ky - y1) * label_h / roi_h), label_h - 1)
+        target = np.where(counted, by * label_w + bx, -1.0)
+    return target.astype(np.int32)
+
+
+def compute_keypoint_targets(proposals, cfg, ground_truth_bboxes, ground_truth_keypoints, image_info, ignore_regions=None):
+    """proposals [N, >=5] (b, x1, y1, x2, y2, ...), gts [B, G, >=5], gt keypoints [B, G, Kp, 3] rows (x, y, v) ->
+    rois fp32 [R, 5] (b, x1, y1, x2, y2) and targets int32 [R, Kp], both on the HOST.  The RoIs are `compute_mask_targets`' selection
+    (`_positive_rois`).  The target rule is OURS (the reference's is in its missing models/mask_rcnn/mask_rcnn.py; include/scda_ops.h
+    states it): the inverse of `predict_keypoints`, which resizes a label_w x label_h map to the roi_w x roi_h window.  In float64, with
+    (kx, ky, v) the keypoint of the RoI's matched ground truth: counted iff v > 0 and x1 <= kx < x2 + 1 and y1 <= ky < y2 + 1; then
+    bx = min(floor((kx - x1) * label_w / roi_w), label_w - 1), by likewise, target = by * label_w + bx; every other pair is -1.
+    No positive RoI at all: one all-zero RoI row and one row of -1 (the mask path's placeholder)."""
+    proposals, gts_all, kps_all, image_info = (np.asarray(_np(v)) for v in (proposals, ground_truth_bboxes, ground_truth_keypoints, image_info))
+    if kps_all.ndim != 4 or kps_all.shape[3] != 3 or kps_all.shape[:2] != gts_all.shape[:2]:
+        raise ValueError("ground_truth_keypoints must be [B, G, Kp, 3] with the ground-truth boxes' B and G, got %s" % (kps_all.shape,))
+    Kp, mw, mh = kps_all.shape[2], int(cfg['label_w']), int(cfg['label_h'])
+    batch_rois, batch_targets = [], []
+    for b_ix, pos_rois, gts, pos_g, keep in _positive_rois(proposals, cfg, gts_all, image_info):
+        batch_rois.append(np.hstack([np.full((pos_rois.shape[0], 1), b_ix), pos_rois]))
+        batch_targets.append(keypoint_target_bins(pos_rois, kps_all[b_ix][keep[pos_g]], mw, mh))
+    if not batch_rois:
+        rois_out, targets_out = np.zeros((1, 5), dtype=np.float32), -np.ones((1, Kp), dtype=np.int32)
+    else:
+        rois_out, targets_out = np.vstack(batch_rois), np.vstack(batch_targets)
+    return (torch.from_numpy(np.ascontiguousarray(rois_out, dtype=np.float32)),
+            torch.from_numpy(np.ascontiguousarray(targets_out, dtype=np.int32)))
+
+
+def compute_mask_targets(proposals, cfg, ground_truth_bboxes, ground_truth_masks, image_info, ignore_regions=None):
+    """proposals [N, >=5] (b, x1, y1, x2, y2, ...), gts [B, G, >=5], gt masks [B, G, H, W] ->
+    rois [R, 6] fp32 (b, x1, y1, x2, y2, class) and labels [R, num_classes, label_h, label_w] fp32 (-1 = ignore; the RoI's own
+    class plane holds its 0/1 mask).  functions/mask.py:73-179: RoIs with IoU > positive_iou_thresh, integer-clipped, at most
+    batch_size_per_image per image (np.random.choice without replacement -- the only RNG draw)."""
+    dev = proposals.device if torch.is_tensor(proposals) else torch.device("cpu")
+    proposals, gts_all, masks_all, image_info = (np.asarray(_np(v)) for v in (proposals, ground_truth_bboxes, ground_truth_masks, image_info))
+    batch_rois, batch_labels = [], []
+    for b_ix, pos_rois, gts, pos_g, keep in _positive_rois(proposals, cfg, gts_all, image_info):
+        masks = masks_all[b_ix]                                    # (the mask planes stay where they are: `keep` indexes them)
         classes = gts[pos_g][:, 4].astype(np.int64)
         n = pos_rois.shape[0]
         labels = -np.ones((n, cfg['num_classes'], cfg['label_h'], cfg['label_w']))

@@ -98,10 +98,12 @@ class ResNet(FasterRCNN_AdEx):
         self.fc_rcnn_cls = L.Linear(512 * block.expansion, cfg['num_classes'])
         self.fc_rcnn_loc = L.Linear(512 * block.expansion, cfg['num_classes'] * 4)
         self.with_keypoint = bool(cfg.get('with_keypoint'))
-        if self.with_keypoint:                                               # keypoint branch (:142-145); test time only
+        if self.with_keypoint:                                               # keypoint branch (:142-145)
             self.num_keypoints = int(cfg['num_keypoints'])
             self.keypoint_roipooling = RoIAlignAvg(14, 14, 1.0 / cfg['anchor_stride'])
             self.keypoint_head = self._make_branch(1024, 512, self.num_keypoints, 8, upscaling=True)
+            # None: the branch runs at test time only (ScdaTrainer refuses such a detector); a dict: it trains (`_keypoint_loss`)
+            self.keypoint_target_cfg = dict(cfg['train_keypoint_target']) if cfg.get('train_keypoint_target') else None
         self.with_mask = bool(cfg.get('with_mask'))
         if self.with_mask:                                                   # mask branch (:146-149), BASELINE configs[4]
             self.mask_roipooling = RoIAlignAvg(14, 14, 1.0 / cfg['anchor_stride'])
@@ -221,8 +223,8 @@ class ResNet(FasterRCNN_AdEx):
         return y.view(y.shape[1], R, 28, 28).transpose(0, 1)
 
     def keypoint_predictor(self, x, rois):
-        """:261-265: [R, 5] RoIs -> keypoint heat maps [R, num_keypoints, 56, 56].  Test time only: the reference's keypoint targets and
-        loss are in its missing models/mask_rcnn/mask_rcnn.py, so nothing here trains the branch.  Like `mask_predictor` the branch runs
+        """:261-265: [R, 5] RoIs -> keypoint heat maps [R, num_keypoints, 56, 56].  At test time (scda_amd.infer) and, for a detector
+        built with cfg['train_keypoint_target'], in training (`_keypoint_loss`).  Like `mask_predictor` the branch runs
         CHANNEL-MAJOR when R % 4 == 0: pooled maps [C, R, 14, 14] as one [1, C, R*14, 14] image, the eight 3x3 convolutions with row
         period 14, the transposed convolution's pixel shuffle keeps the stack a stack ([1, C, R*28, 28]).  The bilinear x2 must not
         blend the last row of one RoI with the first row of the next: it runs on the [C*R, 1, 28, 28] view of that stack (the kernel
@@ -248,12 +250,65 @@ class ResNet(FasterRCNN_AdEx):
         return y.view(y.shape[1], R, 56, 56).transpose(0, 1)
 
     def _extra_source_losses(self, input, feat, proposals):
-        """The mask loss of the source image.  The reference's loss code for this branch is in the missing
+        """The branch losses of the source image, in this order: the mask loss, then the keypoint loss (each only when its branch
+        trains and its ground truth is given; the keypoint targets draw from numpy's generator AFTER the mask targets, so nothing
+        moves for a mask-only detector).  `last_extra_loss_names` names what was returned."""
+        losses, names = [], []
+        for name, term in (('mask_loss', self._mask_loss), ('keypoint_loss', self._keypoint_source_loss)):
+            got = term(input, feat, proposals)
+            if got is not None:
+                losses.append(got)
+                names.append(name)
+        self.last_extra_loss_names = tuple(names)
+        return losses
+
+    def _keypoint_source_loss(self, input, feat, proposals):
+        """The keypoint loss of the source image, or None.  The reference's targets and loss for this branch are in the missing
+        models/mask_rcnn/mask_rcnn.py; its driver passes 'ground_truth_keypoints' [b, max_gts, K, 3] and unpacks a `keypoint_loss`
+        (tools/mask_rcnn_train_val.py:309-329).  Used here (our choice, include/scda_ops.h): targets that invert this project's decode,
+        and the soft-max cross-entropy over each visible keypoint's heat map, averaged over the visible keypoints."""
+        if not (self.with_keypoint and self.training and self.keypoint_target_cfg) or input.get('ground_truth_keypoints') is None:
+            return None
+        from scda_amd.dropin.functions.mask import compute_keypoint_targets
+        kps = input['ground_truth_keypoints']
+        if torch.is_tensor(kps) and kps.is_cuda:
+            # host code like the mask targets: keypoints on the device would come back with a synchronous copy behind the whole
+            # compute-stream backlog, every iteration
+            raise ValueError("ground_truth_keypoints must stay on the host (pass the [1, G, Kp, 3] tensor as the loader yields it)")
+        if kps.shape[2] != self.num_keypoints:
+            raise ValueError("ground_truth_keypoints has %d keypoints, the branch predicts %d" % (kps.shape[2], self.num_keypoints))
+        rois, targets = compute_keypoint_targets(proposals, self.keypoint_target_cfg, input['ground_truth_bboxes'], kps,
+                                                 input['image_info'], input.get('ignore_regions'))
+        if rois.shape[0] == 1 and not bool(rois.any()) and bool((targets < 0).all()):    # the placeholder: no positive RoI
+            return feat.new_zeros(())
+        return self._keypoint_loss(feat, rois, targets)
+
+    def _keypoint_loss(self, feat, rois, targets):
+        """rois fp32 [R, 5] and targets int32 [R, Kp] on the host -> the heat-map loss of the keypoint head on `feat`.  The RoI list is
+        padded to the next multiple of 4 with copies of its first row and targets of -1, so that `keypoint_predictor` stays on the
+        stacked channel-major path: an uncounted map is not read by the loss and gets an exactly zero gradient, so a padding row
+        changes no parameter gradient beyond the order of summation.  (The [R, C, 14, 14] layout it avoids cost the mask branch 10 ms
+        of a 55 ms iteration, see `mask_predictor`.)"""
+        R = rois.shape[0]
+        pad = (-R) % 4 if self.tall_head and not os.environ.get("SCDA_RESNET_HEAD_NCHW") else 0
+        if pad:
+            rois = torch.cat([rois, rois[:1].expand(pad, -1)])
+            targets = torch.cat([targets, targets.new_full((pad, targets.shape[1]), -1)])
+        dev = feat.device
+        # host -> device through pinned staging, non-blocking (a pageable .to(dev) is a synchronous copy on the compute stream)
+        rois_dev = N.upload(rois.contiguous(), dev)
+        targets_dev = N.upload(targets.contiguous(), dev)
+        heat = self.keypoint_predictor(feat, rois_dev)
+        self.last_keypoint_rois = int(rois.shape[0])
+        return A.keypoint_heatmap_loss(heat, targets_dev)
+
+    def _mask_loss(self, input, feat, proposals):
+        """The mask loss of the source image, or None.  The reference's loss code for this branch is in the missing
         models/mask_rcnn/mask_rcnn.py; what exists is the target contract (functions/mask.py:73-179: labels are -1 = ignore on
         every class plane but the RoI's own).  Used here: the Mask R-CNN definition -- the mean binary cross-entropy of
         sigmoid(logits) on each positive RoI's own class plane, averaged over the RoIs."""
         if not (self.with_mask and self.training) or input.get('ground_truth_masks') is None:
-            return []
+            return None
         from scda_amd.dropin.functions.mask import compute_mask_targets
         masks = input['ground_truth_masks']
         if torch.is_tensor(masks) and masks.is_cuda:
@@ -264,7 +319,7 @@ class ResNet(FasterRCNN_AdEx):
                                             masks, input['image_info'], input.get('ignore_regions'))
         dev = feat.device
         if rois.shape[1] < 6:                        # the all-ignore placeholder row: no positive RoI in this image
-            return [feat.new_zeros(())]
+            return feat.new_zeros(())
         cls = rois[:, 5].long()
         r = torch.arange(rois.shape[0])
         # host -> device through pinned staging, non-blocking (a pageable .to(dev) is a synchronous copy on the compute stream)
@@ -274,7 +329,7 @@ class ResNet(FasterRCNN_AdEx):
         logits = self.mask_predictor(feat, rois_dev)
         sel = logits[torch.arange(rois.shape[0], device=dev), cls_dev].reshape(rois.shape[0], -1)
         self.last_mask_rois = int(rois.shape[0])
-        return [A.adversarial_loss([(sel, own, None)], scale=1.0 / rois.shape[0])]
+        return A.adversarial_loss([(sel, own, None)], scale=1.0 / rois.shape[0])
 
 
 DEFAULT_MASK_TARGET = {'positive_iou_thresh': 0.5, 'batch_size_per_image': 64, 'label_h': 28, 'label_w': 28, 'append_gts': True}

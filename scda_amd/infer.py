@@ -38,8 +38,8 @@ the box prediction the detections become the keypoint head's RoIs, `model.keypoi
 scda_amd/csrc/keypoint_ops.hip turns them into (x, y, score) rows without writing an image-sized plane: each heat map resized to its
 box as functions/mask.py:21-49 resizes a mask plane, then np.argmax over the part of the box inside the padded image.  The reference's own
 heat-map decoder is in its missing models/mask_rcnn/mask_rcnn.py: the CHOICE OF THIS RULE IS OURS, and its parity is pinned to
-predict_masks + np.argmax, not to a reference keypoint decoder (include/scda_ops.h).  Not covered: training the branch, heat maps above
-64 x 64, images of one call with different (h, w) in the host-side helpers (the Predictor decodes against the batch's padded shape)."""
+predict_masks + np.argmax, not to a reference keypoint decoder (include/scda_ops.h).  Training the branch is the detector's (cfg['train_keypoint_target'],
+ScdaTrainer.step(..., gt_keypoints=)), with targets that invert this decode.  Not covered: heat maps above 64 x 64, images of one call with different (h, w) in the host-side helpers (the Predictor decodes against the batch's padded shape)."""
 import numpy as np
 import torch
 

@@ -610,6 +610,61 @@ def keypoint_decode(rois, heat, H, W, cls=None, out=None, ws=None):
     return out
 
 
+def _keypoint_planes(who, heat, name="heat"):
+    """heat float32 [R, Kp, h, w] on the device whose (h, w) planes are contiguous, R and Kp strided at will -> (R, Kp, HW, sr, sk)"""
+    if not isinstance(heat, torch.Tensor) or not heat.is_cuda or heat.dtype != torch.float32:
+        raise ScdaNativeError(f"{who}: {name} must be a float32 tensor on the HIP device; there is no CPU path")
+    if heat.dim() != 4 or heat.numel() == 0:
+        raise ValueError(f"{who}: {name} must be a non-empty [R, Kp, h, w]")
+    R, Kp, h, w = heat.shape
+    if h * w > KEYPOINT_PLANE_MAX * KEYPOINT_PLANE_MAX:
+        raise ValueError(f"{who}: maps of {h} x {w} = {h * w} elements; the kernel holds at most "
+                         f"{KEYPOINT_PLANE_MAX * KEYPOINT_PLANE_MAX} ({KEYPOINT_PLANE_MAX} x {KEYPOINT_PLANE_MAX}, the decode's limit)")
+    sr, sk, sh, sw = heat.stride()
+    if (w > 1 and sw != 1) or (h > 1 and sh != w) or sr < 0 or sk < 0:
+        raise ValueError(f"{who}: every (h, w) plane of {name} must be contiguous (strides {tuple(heat.stride())})")
+    return R, Kp, h * w, sr, sk
+
+
+def keypoint_ce_fwd(heat, targets, stats=None, row_loss=None):
+    """The keypoint heat-map loss (include/scda_ops.h states it): heat [R, Kp, h, w] -- contiguous, or the keypoint head's transposed
+    channel-major view, taken as it is --, targets int32 [R, Kp] (-1: not counted) -> (out2 = (mean over the counted pairs of
+    logsumexp(map) - map[target], their number), stats [R * Kp, 2] for the backward, row_loss [R * Kp]).  stats, row_loss: optional
+    buffers of those shapes to fill."""
+    R, Kp, HW, sr, sk = _keypoint_planes("keypoint_ce_fwd", heat)
+    _req(targets, "targets", torch.int32)
+    if tuple(targets.shape) != (R, Kp):
+        raise ValueError("keypoint_ce_fwd: targets must be [R, Kp] = [%d, %d], got %s" % (R, Kp, tuple(targets.shape)))
+    if stats is None:
+        stats = torch.empty(R * Kp, 2, dtype=torch.float32, device=heat.device)
+    if row_loss is None:
+        row_loss = torch.empty(R * Kp, dtype=torch.float32, device=heat.device)
+    _req(stats, "stats"); _req(row_loss, "row_loss")
+    if tuple(stats.shape) != (R * Kp, 2) or tuple(row_loss.shape) != (R * Kp,):
+        raise ValueError("keypoint_ce_fwd: stats must be [R * Kp, 2] and row_loss [R * Kp]")
+    out2 = torch.empty(2, dtype=torch.float32, device=heat.device)
+    _check(lib().scda_keypoint_ce_fwd_hip(_p(heat), sr, sk, R, Kp, HW, _p(targets), _p(stats), _p(row_loss), _p(out2), _stream()),
+           "scda_keypoint_ce_fwd_hip")
+    return out2, stats, row_loss
+
+
+def keypoint_ce_bwd(heat, targets, stats, out2, g, out=None):
+    """-> d loss / d heat in heat's own layout (a tensor of heat's shape and strides): (softmax - onehot) * g / count on counted maps,
+    exactly zero on the others.  g: one float32 on the device.  out: a tensor of heat's shape with contiguous planes to fill."""
+    R, Kp, HW, sr, sk = _keypoint_planes("keypoint_ce_bwd", heat)
+    _req(g, "g"); _req(targets, "targets", torch.int32); _req(stats, "stats"); _req(out2, "out2")
+    if targets.numel() != R * Kp or stats.numel() != 2 * R * Kp or out2.numel() != 2 or g.numel() != 1:
+        raise ValueError("keypoint_ce_bwd: targets [R, Kp], stats [R * Kp, 2], out2 [2] and g [1] of the forward call are needed")
+    if out is None:
+        out = torch.empty_like(heat)          # (preserve_format: heat's strides when it is dense, its dimension order otherwise)
+    if tuple(out.shape) != tuple(heat.shape):
+        raise ValueError("keypoint_ce_bwd: out must have heat's shape")
+    _, _, _, dsr, dsk = _keypoint_planes("keypoint_ce_bwd", out, "out")
+    _check(lib().scda_keypoint_ce_bwd_hip(_p(heat), sr, sk, R, Kp, HW, _p(targets), _p(stats), _p(out2), _p(g), _p(out), dsr, dsk,
+                                          _stream()), "scda_keypoint_ce_bwd_hip")
+    return out
+
+
 def mask_rescale_max_ratio():
     """the largest down-scale h / oh, w / ow of mask_rescale (a capacity of the kernel's LDS tables)"""
     return int(lib().scda_mask_rescale_max_ratio())

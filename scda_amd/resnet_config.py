@@ -23,9 +23,11 @@ RECON_HW = (128, 256)
 
 MASK_ROIS = 64                # positive RoIs per image the mask branch trains on (train_mask_target.batch_size_per_image)
 MASK_TARGET = {'positive_iou_thresh': 0.5, 'batch_size_per_image': MASK_ROIS, 'label_h': 28, 'label_w': 28, 'append_gts': True}
+KEYPOINT_ROIS = 64            # positive RoIs per image the keypoint branch trains on (train_keypoint_target.batch_size_per_image)
+KEYPOINT_TARGET = {'positive_iou_thresh': 0.5, 'batch_size_per_image': KEYPOINT_ROIS, 'label_h': 56, 'label_w': 56, 'append_gts': True}
 
 
-def build_models(cfg, cluster_num=4, threshold=128, with_mask=False, mask_iou=None):
+def build_models(cfg, cluster_num=4, threshold=128, with_mask=False, mask_iou=None, with_keypoint=False, num_keypoints=17):
     """with_mask: BASELINE.json configs[4] -- the same detector with the mask branch of models/mask_rcnn/resnet.py:146-149
     (RoIAlignAvg(14, 14), four 3x3 convs 1024 -> 256, 2x2/2 transposed conv, 1x1 conv to per-class 28 x 28 masks) and its loss added
     to the detector's; the step takes ground-truth masks (`ScdaTrainer.step(..., gt_masks=)`)"""
@@ -36,15 +38,20 @@ def build_models(cfg, cluster_num=4, threshold=128, with_mask=False, mask_iou=No
         shared.update(with_mask=True, train_mask_target=dict(MASK_TARGET))
         if mask_iou is not None:      # synthetic runs: an untrained RPN puts few proposals on the objects (bench.py says what it used)
             shared['train_mask_target']['positive_iou_thresh'] = mask_iou
+    if with_keypoint:
+        shared.update(with_keypoint=True, num_keypoints=num_keypoints, train_keypoint_target=dict(KEYPOINT_TARGET))
+        if mask_iou is not None:
+            shared['train_keypoint_target']['positive_iou_thresh'] = mask_iou
     det = resnet50(cfg=shared)
     dis, dec, dis_patch = builder_gan(cluster_num, threshold, 256, neww=FEAT_HW[0], newh=FEAT_HW[1])
     return det, dec, dis, dis_patch
 
 
-def make_trainer(cfg, device, lr=1.25e-5, world_size=1, with_mask=False, mask_iou=None):
+def make_trainer(cfg, device, lr=1.25e-5, world_size=1, with_mask=False, mask_iou=None, with_keypoint=False, num_keypoints=17):
     from scda_amd.train_step import ScdaTrainer
     return ScdaTrainer(cfg, device, lr=lr, new_w=W, new_h=H, world_size=world_size,
-                       models=build_models(cfg, with_mask=with_mask, mask_iou=mask_iou), recon_hw=RECON_HW)
+                       models=build_models(cfg, with_mask=with_mask, mask_iou=mask_iou, with_keypoint=with_keypoint,
+                                           num_keypoints=num_keypoints), recon_hw=RECON_HW)
 
 
 def synth_masks(gts, h=H, w=W):
@@ -56,6 +63,28 @@ def synth_masks(gts, h=H, w=W):
     for i, (x1, y1, x2, y2) in enumerate(g[:, :4]):
         if x2 > x1 and y2 > y1:
             out[0, i] = ((((xx - (x1 + x2) / 2.0) / ((x2 - x1) / 2.0)) ** 2 + ((yy - (y1 + y2) / 2.0) / ((y2 - y1) / 2.0)) ** 2) <= 1.0)
+    return torch.from_numpy(out)
+
+
+def synth_keypoints(gts, Kp=17, seed=0):
+    """[1, G, Kp, 3] float32 rows (x, y, v): seeded points inside every ground-truth box, v = 2 (visible) except every fourth one
+    (v = 0, not labelled); per box the first keypoint lies exactly on x1 and the second just below x2 + 1, the two ends of the half-open
+    interval a keypoint target is counted on (include/scda_ops.h)"""
+    import numpy as np
+    g = (gts[0].numpy() if torch.is_tensor(gts) else np.asarray(gts[0])).astype(np.float64)
+    rs = np.random.RandomState(seed)
+    out = np.zeros((1, g.shape[0], Kp, 3), dtype=np.float32)
+    for i, (x1, y1, x2, y2) in enumerate(g[:, :4]):
+        if not (x2 > x1 and y2 > y1):
+            continue                                   # a padding row stays all zero
+        u = rs.uniform(0.0, 1.0, (Kp, 2))
+        out[0, i, :, 0] = x1 + u[:, 0] * (x2 - x1)
+        out[0, i, :, 1] = y1 + u[:, 1] * (y2 - y1)
+        out[0, i, :, 2] = np.where((np.arange(Kp) + i) % 4 == 3, 0.0, 2.0)
+        out[0, i, 0, 0] = x1
+        if Kp > 1:
+            out[0, i, 1, 0] = np.nextafter(np.float32(x2 + 1.0), np.float32(0.0))
+        out[0, i, :2, 2] = 2.0
     return torch.from_numpy(out)
 
 

@@ -263,11 +263,12 @@ class ScdaTrainer:
         collectives: issue the four per-phase all-reduces (default: world_size > 1).  True with a one-rank process group runs
         the whole RCCL path -- async all-reduce on the device buckets, waits, stream hand-over -- on a single GPU
         (tests/test_distributed_gpu.py::test_rccl_one_rank_group_matches_plain_step)."""
-        if models is not None and getattr(models[0], 'with_keypoint', False):
-            # the reference's keypoint targets and loss are in its missing models/mask_rcnn/mask_rcnn.py: no loss reaches the branch, and
-            # its parameters would sit in the flat buckets without ever getting a gradient
-            raise ValueError("ScdaTrainer: training the keypoint branch is not covered (the detector was built with with_keypoint; the "
-                             "branch runs at test time only -- build the training detector without it)")
+        if models is not None and getattr(models[0], 'with_keypoint', False) and not getattr(models[0], 'keypoint_target_cfg', None):
+            # built for test time: no loss would reach the branch, and its parameters would sit in the flat buckets without ever
+            # getting a gradient
+            raise ValueError("ScdaTrainer: the detector was built with with_keypoint but without cfg['train_keypoint_target'], so its "
+                             "keypoint branch runs at test time only -- build the training detector with that key (scda_amd."
+                             "resnet_config.KEYPOINT_TARGET) or without the branch")
         # parity tests: a scda_amd.probe.Probe (replayed selections / RPN outputs / dropout masks of the CPU oracle), visible to the
         # product's modules while THIS trainer's step() runs and at no other time; None in production
         self.probe = probe
@@ -502,18 +503,21 @@ class ScdaTrainer:
             c = self._ones_row_cache = torch.ones(row, dtype=torch.float32, device=self.device)
         return c
 
-    def step(self, image, gts, image_info, target, gt_masks=None):
+    def step(self, image, gts, image_info, target, gt_masks=None, gt_keypoints=None):
         """image/target [1,3,H,W] on the device; gts [1,G,5]; image_info [1,3]; gt_masks [1,G,H,W] binary (detectors with a mask
-        branch, BASELINE configs[4]) -> dict of 0-dim loss tensors"""
+        branch, BASELINE configs[4]); gt_keypoints [1,G,Kp,3] rows (x, y, v) on the host (detectors whose keypoint branch trains)
+        -> dict of 0-dim loss tensors"""
         with P.installed(self.probe):
-            return self._step(image, gts, image_info, target, gt_masks)
+            return self._step(image, gts, image_info, target, gt_masks, gt_keypoints)
 
-    def _step(self, image, gts, image_info, target, gt_masks=None):
+    def _step(self, image, gts, image_info, target, gt_masks=None, gt_keypoints=None):
         dev, ws, C = self.device, float(self.world_size), self.cluster_num
         x = {'cfg': self.cfg, 'image': image, 'image_info': image_info, 'ground_truth_bboxes': gts,
              'ignore_regions': None, 'cluster_num': self.cluster_num, 'threshold': self.threshold}
         if gt_masks is not None:
             x['ground_truth_masks'] = gt_masks
+        if gt_keypoints is not None:
+            x['ground_truth_keypoints'] = gt_keypoints
         pending = {}
         for sch in self._warmup or ():     # :510-514 -- the warm-up schedulers step at the top of the iteration
             sch.step()
@@ -523,7 +527,7 @@ class ScdaTrainer:
             # detector loss carries no gradient into the detector), so its backward -- and, multi-GPU,
             # the 547 MB all-reduce -- starts here and runs underneath the rest of the iteration.
             total = losses[0] + losses[1] + losses[2] + losses[3]
-            for extra in losses[4:]:          # branches beyond RPN + RCNN (the mask loss of configs[4])
+            for extra in losses[4:]:          # branches beyond RPN + RCNN (the mask loss of configs[4], the keypoint loss)
                 total = total + extra
             det_loss = total / ws
             self.opt['det'].zero_grad()
@@ -607,7 +611,13 @@ class ScdaTrainer:
         mark('phase4+det_step')
 
         self.last_num_proposals = outputs.get('num_proposals')     # post-NMS proposal counts (source, target) of this iteration
-        extra_logged = {'mask_loss': outputs['losses'][4].detach()} if len(outputs['losses']) > 4 else {}
+        # the branch losses behind the four detector losses, under the names the detector reports for them
+        extra = outputs['losses'][4:]
+        extra_names = getattr(self.model, 'last_extra_loss_names', ()) if extra else ()
+        if len(extra_names) != len(extra):
+            raise RuntimeError("the detector returned %d losses beyond the four detector losses and names %s"
+                               % (len(extra), list(extra_names)))
+        extra_logged = {name: v.detach() for name, v in zip(extra_names, extra)}
         return {'loss': loss.detach() * ws, 'rpn_cls': rpn_cls.detach(), 'rpn_loc': rpn_loc.detach(),
                 'rcnn_cls': rcnn_cls.detach(), 'rcnn_loc': rcnn_loc.detach(), 'rpn_acc': outputs['accuracy'][0],
                 'rcnn_acc': outputs['accuracy'][1], 'fake_loss_target': fake_loss_target, 'fake_loss_source': fake_loss_source,
