@@ -183,6 +183,17 @@ int scda_bbox_overlaps_hip(const float *boxes, int N, const float *query, int K,
 int scda_anchor_label_hip(const float *anchors, int KA, const float *gts, int G, int gt_stride, float neg_thresh, float pos_thresh,
                           float min_gt_best, float *best_iou, int *best_gt, unsigned *gt_best, signed char *labels, int *pos_list,
                           int *neg_list, int *counts, void *stream);
+/* scda_anchor_label_hip with ignore regions (:71-76): ign [I, ign_stride >= 4] fp32 rows (x1, y1, x2, y2, ...), padded zero rows
+ * included (the reference filters none here; their IoF is 0).  Per anchor the max over the rows of the IoF of
+ * utils/bbox_helper.py:29-45 -- intersection over the ANCHOR's area, no +1, numerator max(xmax - xmin, 0) * max(ymax - ymin, 0),
+ * divisor max(area, 1) -- in float64 on anchors64 (the float64 grid [KA,4]; the rows are promoted, as numpy promotes them); where it
+ * is > ign_thresh (strict, double) the label becomes -1, after the background assignment and before the two foreground
+ * assignments: a foreground anchor inside an ignore region stays foreground.  I has no cap.  I = 0 (ign, anchors64 may be null):
+ * the same launches and results as scda_anchor_label_hip, which forwards here. */
+int scda_anchor_label_ign_hip(const float *anchors, int KA, const float *gts, int G, int gt_stride, float neg_thresh, float pos_thresh,
+                              float min_gt_best, const double *anchors64, const float *ign, int I, int ign_stride, double ign_thresh,
+                              float *best_iou, int *best_gt, unsigned *gt_best, signed char *labels, int *pos_list, int *neg_list,
+                              int *counts, void *stream);
 /* :66-107 -- drop the surplus the host drew (drop_* index INTO pos_list / neg_list, as np.random.choice returns them) and emit
  * cls_targets int64 [A,fh,fw], loc_targets / loc_masks fp32 [4A,fh,fw]; anchors64 = the float64 anchor grid [KA,4] */
 int scda_anchor_finalize_hip(signed char *labels, const int *best_gt, const int *pos_list, const int *drop_pos, int n_drop_pos,
@@ -209,6 +220,18 @@ int scda_proposal_gather_hip(const float *props5, const long long *keep, const l
 int scda_proposal_match_hip(const float *props, int n_prop, int prop_stride, const float *gts, int G, int gt_stride, float img_h,
                             float img_w, float pos_thresh, float neg_hi, float neg_lo, float *rois, float *best_iou, int *best_gt,
                             signed char *labels, int *pos_list, int *neg_list, int *counts, void *stream);
+/* scda_proposal_match_hip with ignore regions (:79-86): ign [I, ign_stride >= 4] fp32 rows, already filtered by the host (:82, x2 -
+ * x1 > 1).  Per CLIPPED candidate the max IoF over the rows (the rule above, float32 throughout); ign_flags i8 [n_prop+G] = 1 where
+ * it is > ign_thresh (strict; the float32 the threshold rounds to, as numpy compares a float32 array), else -1; ign_list i32
+ * [n_prop+G] = the ascending indices of the flagged candidates -- np.where(max_iof > t)[0], over foreground, background and
+ * neither --, ign_count i32 [2] = {its length, 0}.  labels, pos_list, neg_list and counts are scda_proposal_match_hip's: the host
+ * takes the ignored candidates out of the negatives with the reference's own set arithmetic (:87), whose order depends on both
+ * sets' sizes.  I has no cap.  I = 0 (ign, ign_flags, ign_list, ign_count may be null and are not touched): the same launches and
+ * results as scda_proposal_match_hip, which forwards here. */
+int scda_proposal_match_ign_hip(const float *props, int n_prop, int prop_stride, const float *gts, int G, int gt_stride, float img_h,
+                                float img_w, float pos_thresh, float neg_hi, float neg_lo, const float *ign, int I, int ign_stride,
+                                float ign_thresh, float *rois, float *best_iou, int *best_gt, signed char *labels, int *pos_list,
+                                int *neg_list, int *counts, signed char *ign_flags, int *ign_list, int *ign_count, void *stream);
 /* Step 2 (:64-136): sel i32 [R] = sampled candidate indices, gt_of i32 [R] = matched gt (-1: background), enc f32 [R,4] = the
  * foreground rows' normalised targets -> rois5 [R,5] = (image_index, box), labels int64 [R], loc_targets / loc_weights [R, 4*C]. */
 int scda_proposal_finalize_hip(const float *cand_rois, const int *sel, const int *gt_of, const float *enc, const float *gts,

@@ -24,6 +24,34 @@ __device__ __forceinline__ float bbox_iou(const float *b, const float *q) {
     return __fdiv_rn(iw * ih, ua);
 }
 
+// max over the I ignore rows of the IoF of utils/bbox_helper.py:29-45: intersection over the FIRST box's area, no +1, the
+// numerator max(xmax - xmin, 0) * max(ymax - ymin, 0), the divisor max(area1, 1); one IEEE operation per source operator.  Every
+// IoF is >= +0 (a negative area1 divides by 1), so the maximum starts at 0.  Two call sites, two dtypes, as numpy promotes them:
+// clipped candidates against float32 rows stay float32 ...
+__device__ __forceinline__ float max_iof(const float *b, const float *__restrict__ ign, const int I, const int ign_stride) {
+    const float div = fmaxf((b[2] - b[0]) * (b[3] - b[1]), 1.f);
+    float m = 0.f;
+    for (int i = 0; i < I; ++i) {
+        const float *q = ign + (size_t)i * ign_stride;
+        const float dx = fmaxf(fminf(b[2], q[2]) - fmaxf(b[0], q[0]), 0.f), dy = fmaxf(fminf(b[3], q[3]) - fmaxf(b[1], q[1]), 0.f);
+        m = fmaxf(m, __fdiv_rn(dx * dy, div));
+    }
+    return m;
+}
+
+// ... and the float64 anchor grid promotes the float32 rows to float64
+__device__ __forceinline__ double max_iof(const double *b, const float *__restrict__ ign, const int I, const int ign_stride) {
+    const double div = fmax((b[2] - b[0]) * (b[3] - b[1]), 1.);
+    double m = 0.;
+    for (int i = 0; i < I; ++i) {
+        const float *q = ign + (size_t)i * ign_stride;
+        const double dx = fmax(fmin(b[2], (double)q[2]) - fmax(b[0], (double)q[0]), 0.);
+        const double dy = fmax(fmin(b[3], (double)q[3]) - fmax(b[1], (double)q[1]), 0.);
+        m = fmax(m, dx * dy / div);
+    }
+    return m;
+}
+
 // ---- anchor labelling: functions/anchor_target.py:38-64 -----------------------------------------------------------------
 // pass 1: per anchor the best gt (first maximum, as ndarray.argmax) and its IoU; per gt the best IoU over all anchors
 // (block-level max in LDS, then one atomicMax per block and gt on the IoU's bit pattern -- IoUs are >= 0, so unsigned order
@@ -56,17 +84,24 @@ __global__ __launch_bounds__(256) void anchor_match_kernel(const float *__restri
 // pass 2: labels.  -1 ignore / 0 background / 1 foreground, in the reference's order of assignments:
 //   labels[best_iou < neg] = 0 ; labels[(anchor, gt) pairs whose IoU equals that gt's best, if that best >= 0.1] = 1 (and
 //   best_gt <- that gt, the LAST such gt in np.where's row-major order) ; labels[best_iou > pos] = 1
+// IGN: between the first and the second assignment, labels[max IoF over the ignore rows > ign_thresh] = -1 (:71-76, float64 on the
+// float64 grid, a strict > against the double threshold): background inside an ignore region leaves the loss, foreground stays.
+// Padded zero rows are not filtered, as in the reference: their IoF is 0.
+template <bool IGN>
 __global__ __launch_bounds__(256) void anchor_label_kernel(const float *__restrict__ anchors, const int KA,
                                                            const float *__restrict__ gts, const int G, const int gt_stride,
                                                            const float *__restrict__ best_iou, int *__restrict__ best_gt,
                                                            const unsigned *__restrict__ gt_best_bits, const float neg_thresh,
                                                            const float pos_thresh, const float min_gt_best,
+                                                           const double *__restrict__ anchors64, const float *__restrict__ ign,
+                                                           const int I, const int ign_stride, const double ign_thresh,
                                                            signed char *__restrict__ labels) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= KA) return;
     const float *a = anchors + (size_t)k * 4;
     const float bi = best_iou[k];
     int lab = bi < neg_thresh ? 0 : -1;
+    if (IGN && max_iof(anchors64 + (size_t)k * 4, ign, I, ign_stride) > ign_thresh) lab = -1;
     int claim = -1;
     for (int g = 0; g < G; ++g) {
         const float gb = __uint_as_float(gt_best_bits[g]);
@@ -195,12 +230,17 @@ __global__ __launch_bounds__(256) void proposal_gather_kernel(const float *__res
 // (np.clip on float32 columns), IoU against every gt on the CLIPPED box, first maximum (ndarray.argmax) -> best_gt / best_iou, and
 // the class of the threshold tests of :55-59: 1 = foreground (best_iou > pos), 0 = background (lo <= best_iou < hi and not
 // foreground), -1 = neither.  The ordered index lists np.where would return come from anchor_compact_kernel.
+// IGN: ign_flags[r] = 1 where the clipped box's max IoF over the ignore rows exceeds ign_thresh (:84-86, float32 against the
+// threshold rounded to float32), else -1 -- for every candidate, whatever its class; labels do not change.
+template <bool IGN>
 __global__ __launch_bounds__(256) void proposal_match_kernel(const float *__restrict__ props, const int n_prop, const int prop_stride,
                                                              const float *__restrict__ gts, const int G, const int gt_stride,
                                                              const float hi_x, const float hi_y, const float pos_thresh,
                                                              const float neg_hi, const float neg_lo, float *__restrict__ rois,
                                                              float *__restrict__ best_iou, int *__restrict__ best_gt,
-                                                             signed char *__restrict__ labels) {
+                                                             signed char *__restrict__ labels, const float *__restrict__ ign,
+                                                             const int I, const int ign_stride, const float ign_thresh,
+                                                             signed char *__restrict__ ign_flags) {
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n_prop + G) return;
     const float *src = r < n_prop ? props + (size_t)r * prop_stride + 1 : gts + (size_t)(r - n_prop) * gt_stride;
@@ -218,6 +258,7 @@ __global__ __launch_bounds__(256) void proposal_match_kernel(const float *__rest
     best_iou[r] = bi;
     best_gt[r] = bg;
     labels[r] = (signed char)(bi > pos_thresh ? 1 : (bi < neg_hi && bi >= neg_lo) ? 0 : -1);
+    if (IGN) ign_flags[r] = (signed char)(max_iof(box, ign, I, ign_stride) > ign_thresh ? 1 : -1);
 }
 
 // The sampled RoIs of one image, after the host drew them: sel[i] = candidate index, gt_of[i] = its matched gt (>= 0: foreground,
@@ -253,20 +294,34 @@ using namespace scda;
 // positives / negatives and their counts.  anchors [KA,4] fp32 (the float64 grid cast as the reference casts it for the IoU),
 // gts [G, gt_stride >= 4] fp32.  Scratch and outputs are the caller's: best_iou [KA] f32, best_gt [KA] i32, gt_best [G] u32
 // (zeroed here), labels [KA] i8, pos_list / neg_list [KA] i32, counts [2] i32.
-SCDA_API int scda_anchor_label_hip(const float *anchors, int KA, const float *gts, int G, int gt_stride, float neg_thresh,
-                                   float pos_thresh, float min_gt_best, float *best_iou, int *best_gt, unsigned *gt_best,
-                                   signed char *labels, int *pos_list, int *neg_list, int *counts, void *stream) {
+// With ignore regions (:71-76): ign [I, ign_stride >= 4] fp32 rows (x1, y1, x2, y2, ...), anchors64 [KA,4] the float64 grid the IoF
+// is taken on, ign_thresh the double threshold.  I = 0 (ign and anchors64 may be null) is scda_anchor_label_hip.
+SCDA_API int scda_anchor_label_ign_hip(const float *anchors, int KA, const float *gts, int G, int gt_stride, float neg_thresh,
+                                       float pos_thresh, float min_gt_best, const double *anchors64, const float *ign, int I,
+                                       int ign_stride, double ign_thresh, float *best_iou, int *best_gt, unsigned *gt_best,
+                                       signed char *labels, int *pos_list, int *neg_list, int *counts, void *stream) {
     BOX_CHECK(anchors && gts && best_iou && best_gt && gt_best && labels && pos_list && neg_list && counts && KA > 0 && G > 0 &&
-              gt_stride >= 4, "scda_anchor_label_hip")
+              gt_stride >= 4 && I >= 0 && (I == 0 || (anchors64 && ign && ign_stride >= 4)), "scda_anchor_label_ign_hip")
     hipStream_t st = as_stream(stream);
     if (hipMemsetAsync(gt_best, 0, (size_t)G * sizeof(unsigned), st) != hipSuccess) return launch_status("hipMemsetAsync");
     const int blocks = cdiv(KA, 256);
     hipLaunchKernelGGL(anchor_match_kernel, dim3(blocks), dim3(256), (size_t)G * sizeof(unsigned), st, anchors, KA, gts, G, gt_stride,
                        best_iou, best_gt, gt_best);
-    hipLaunchKernelGGL(anchor_label_kernel, dim3(blocks), dim3(256), 0, st, anchors, KA, gts, G, gt_stride, best_iou, best_gt, gt_best,
-                       neg_thresh, pos_thresh, min_gt_best, labels);
+    if (I > 0)
+        hipLaunchKernelGGL(anchor_label_kernel<true>, dim3(blocks), dim3(256), 0, st, anchors, KA, gts, G, gt_stride, best_iou, best_gt,
+                           gt_best, neg_thresh, pos_thresh, min_gt_best, anchors64, ign, I, ign_stride, ign_thresh, labels);
+    else
+        hipLaunchKernelGGL(anchor_label_kernel<false>, dim3(blocks), dim3(256), 0, st, anchors, KA, gts, G, gt_stride, best_iou, best_gt,
+                           gt_best, neg_thresh, pos_thresh, min_gt_best, (const double *)nullptr, (const float *)nullptr, 0, 0, 0., labels);
     hipLaunchKernelGGL(anchor_compact_kernel, dim3(1), dim3(1024), 0, st, labels, KA, pos_list, neg_list, counts);
     return launch_status("anchor_label kernels");
+}
+
+SCDA_API int scda_anchor_label_hip(const float *anchors, int KA, const float *gts, int G, int gt_stride, float neg_thresh,
+                                   float pos_thresh, float min_gt_best, float *best_iou, int *best_gt, unsigned *gt_best,
+                                   signed char *labels, int *pos_list, int *neg_list, int *counts, void *stream) {
+    return scda_anchor_label_ign_hip(anchors, KA, gts, G, gt_stride, neg_thresh, pos_thresh, min_gt_best, nullptr, nullptr, 0, 0, 0.,
+                                     best_iou, best_gt, gt_best, labels, pos_list, neg_list, counts, stream);
 }
 
 // step 2 of 2 (:66-107): the host drew which surplus positives / negatives to drop (indices INTO pos_list / neg_list, as
@@ -311,18 +366,41 @@ SCDA_API int scda_proposal_gather_hip(const float *props5, const long long *keep
 // best gt / IoU; foreground / background classes; ordered index lists and counts.  props [n_prop, prop_stride >= 5] fp32 rows
 // (b, x1, y1, x2, y2, ...), gts [G, gt_stride >= 5] fp32 (x1, y1, x2, y2, class).  Outputs (caller-owned): rois [n_prop+G, 4],
 // best_iou / best_gt / labels [n_prop+G], pos_list / neg_list [n_prop+G] i32, counts [2] i32.
+// With ignore regions (:79-86): ign [I, ign_stride >= 4] fp32 rows the host already filtered (:82) -> ign_flags [n_prop+G] i8,
+// ign_list [n_prop+G] i32 = np.where(max IoF > ign_thresh)[0] over ALL candidates, ign_count i32 [2] = {its length, 0}; the host
+// then runs the reference's two set differences on the three lists.  I = 0 (ign and the three buffers may be null, none is
+// touched) is scda_proposal_match_hip.
+SCDA_API int scda_proposal_match_ign_hip(const float *props, int n_prop, int prop_stride, const float *gts, int G, int gt_stride,
+                                         float img_h, float img_w, float pos_thresh, float neg_hi, float neg_lo, const float *ign, int I,
+                                         int ign_stride, float ign_thresh, float *rois, float *best_iou, int *best_gt,
+                                         signed char *labels, int *pos_list, int *neg_list, int *counts, signed char *ign_flags,
+                                         int *ign_list, int *ign_count, void *stream) {
+    BOX_CHECK(gts && rois && best_iou && best_gt && labels && pos_list && neg_list && counts && n_prop >= 0 && (n_prop == 0 || props) &&
+              G > 0 && prop_stride >= 5 && gt_stride >= 5 && I >= 0 &&
+              (I == 0 || (ign && ign_stride >= 4 && ign_flags && ign_list && ign_count)), "scda_proposal_match_ign_hip")
+    hipStream_t st = as_stream(stream);
+    const int n = n_prop + G;
+    if (I > 0)
+        hipLaunchKernelGGL(proposal_match_kernel<true>, dim3(cdiv(n, 256)), dim3(256), 0, st, props, n_prop, prop_stride, gts, G, gt_stride,
+                           img_w - 1.f, img_h - 1.f, pos_thresh, neg_hi, neg_lo, rois, best_iou, best_gt, labels, ign, I, ign_stride,
+                           ign_thresh, ign_flags);
+    else
+        hipLaunchKernelGGL(proposal_match_kernel<false>, dim3(cdiv(n, 256)), dim3(256), 0, st, props, n_prop, prop_stride, gts, G, gt_stride,
+                           img_w - 1.f, img_h - 1.f, pos_thresh, neg_hi, neg_lo, rois, best_iou, best_gt, labels, (const float *)nullptr,
+                           0, 0, 0.f, (signed char *)nullptr);
+    hipLaunchKernelGGL(anchor_compact_kernel, dim3(1), dim3(1024), 0, st, labels, n, pos_list, neg_list, counts);
+    if (I > 0)     // the flags are 1 / -1, never 0: the second list of the compaction stays empty and is not written
+        hipLaunchKernelGGL(anchor_compact_kernel, dim3(1), dim3(1024), 0, st, ign_flags, n, ign_list, ign_list, ign_count);
+    return launch_status("proposal_match kernels");
+}
+
 SCDA_API int scda_proposal_match_hip(const float *props, int n_prop, int prop_stride, const float *gts, int G, int gt_stride,
                                      float img_h, float img_w, float pos_thresh, float neg_hi, float neg_lo, float *rois,
                                      float *best_iou, int *best_gt, signed char *labels, int *pos_list, int *neg_list, int *counts,
                                      void *stream) {
-    BOX_CHECK(gts && rois && best_iou && best_gt && labels && pos_list && neg_list && counts && n_prop >= 0 && (n_prop == 0 || props) &&
-              G > 0 && prop_stride >= 5 && gt_stride >= 5, "scda_proposal_match_hip")
-    hipStream_t st = as_stream(stream);
-    const int n = n_prop + G;
-    hipLaunchKernelGGL(proposal_match_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, props, n_prop, prop_stride, gts, G, gt_stride,
-                       img_w - 1.f, img_h - 1.f, pos_thresh, neg_hi, neg_lo, rois, best_iou, best_gt, labels);
-    hipLaunchKernelGGL(anchor_compact_kernel, dim3(1), dim3(1024), 0, st, labels, n, pos_list, neg_list, counts);
-    return launch_status("proposal_match kernels");
+    return scda_proposal_match_ign_hip(props, n_prop, prop_stride, gts, G, gt_stride, img_h, img_w, pos_thresh, neg_hi, neg_lo, nullptr, 0,
+                                       0, 0.f, rois, best_iou, best_gt, labels, pos_list, neg_list, counts, nullptr, nullptr, nullptr,
+                                       stream);
 }
 
 // step 2 of 2 (:64-136): gather what the host sampled (see proposal_finalize_kernel)

@@ -61,8 +61,22 @@ def _pinned_i32(a):
     return p
 
 
-def anchor_targets(feature_size, cfg, gts_dev):
-    """functions/anchor_target.py:16-116 for ONE image whose ground truth lives on the device.
+def ignore_regions_legal(ign):
+    """what the device paths take as ignore regions: None, or a float32 tensor [1, I, >= 4] on the host or on the device"""
+    return ign is None or (torch.is_tensor(ign) and ign.dtype == torch.float32 and ign.dim() == 3 and ign.shape[0] == 1 and ign.shape[2] >= 4)
+
+
+def _upload_rows(rows, dev):
+    """host rows [n, k] -> float32 on the device, through pinned memory on the current (side) stream"""
+    pin = torch.empty(rows.shape, dtype=torch.float32, pin_memory=True)
+    pin.copy_(torch.from_numpy(np.ascontiguousarray(rows, dtype=np.float32)))
+    return pin.to(dev, non_blocking=True)
+
+
+def anchor_targets(feature_size, cfg, gts_dev, ignore_regions=None):
+    """functions/anchor_target.py:16-116 for ONE image whose ground truth lives on the device.  ignore_regions: None, or [1,I,4] fp32
+    with I > 0 on the host or the device (:71-76: background anchors whose IoF with a region exceeds cfg['ignore_iou_thresh'] leave
+    the loss); their rows go up on the side stream as the host copy of the gts does.
     -> cls_targets int64 [1,A,fh,fw], loc_targets, loc_masks fp32 [1,4A,fh,fw], normaliser (int)"""
     B, A4, fh, fw = feature_size
     A = A4 // 4
@@ -83,7 +97,19 @@ def anchor_targets(feature_size, cfg, gts_dev):
             gts = gts_dev[0].contiguous()
         G = gts.shape[0]
         bufs = _bufs(KA, G, dev)
-        N.anchor_label(a32, gts, cfg['negative_iou_thresh'], cfg['positive_iou_thresh'], 0.1, bufs)
+        if ignore_regions is None:
+            N.anchor_label(a32, gts, cfg['negative_iou_thresh'], cfg['positive_iou_thresh'], 0.1, bufs)
+        else:
+            host_ign = getattr(ignore_regions, "_scda_host", None)
+            if host_ign is None and not ignore_regions.is_cuda:
+                host_ign = ignore_regions.detach().numpy()
+            if host_ign is not None:
+                ign = _upload_rows(host_ign[0], dev)
+            else:
+                aux.wait_stream(main)
+                ign = ignore_regions[0].contiguous()
+            N.anchor_label_ign(a32, gts, cfg['negative_iou_thresh'], cfg['positive_iou_thresh'], 0.1, a64, ign,
+                               float(cfg['ignore_iou_thresh']), bufs)
         bufs["counts_host"].copy_(bufs["counts"], non_blocking=True)
         aux.synchronize()
         n_pos, n_neg = (int(v) for v in bufs["counts_host"])
@@ -174,17 +200,31 @@ def _pt_bufs(n, dev):
     return b
 
 
+def _pt_ign_bufs(b, dev):
+    """the buffers only a call with ignore regions needs, beside those of _pt_bufs"""
+    if "ign_flags" not in b:
+        cap = b["cap"]
+        b.update({"ign_flags": torch.empty(cap, dtype=torch.int8, device=dev), "ign_list": torch.empty(cap, dtype=torch.int32, device=dev),
+                  "ign_count": torch.zeros(2, dtype=torch.int32, device=dev),
+                  "ign_host": torch.zeros(cap + 2, dtype=torch.int32, pin_memory=True)})
+    return b
+
+
 def proposal_targets_legal(cfg, gts, ignore_regions, use_ohem):
-    return (ignore_regions is None and not use_ohem and cfg['append_gts'] and cfg['positive_iou_thresh'] >= cfg['negative_iou_thresh_hi']
+    return (ignore_regions_legal(ignore_regions) and not use_ohem and cfg['append_gts'] and cfg['positive_iou_thresh'] >= cfg['negative_iou_thresh_hi']
             and torch.is_tensor(gts) and gts.is_cuda and gts.dtype == torch.float32 and gts.shape[0] == 1 and enabled())
 
 
-def proposal_targets(proposals, cfg, gts_dev, image_info):
+def proposal_targets(proposals, cfg, gts_dev, image_info, ignore_regions=None):
     """functions/proposal_target.py:17-177 for ONE image with the candidates resident on the device: clip, the (N + G) x G IoU, best gt,
     the threshold tests and the ordered foreground / background index lists are kernels (box_ops.hip: scda_proposal_match_hip), the
     gather of the sampled rows and the [512, 4C] target / weight maps too (scda_proposal_finalize_hip).  The host keeps what IS the
     reference's observable behaviour: the order in which Python-set arithmetic leaves the negatives (:87,90), the np.random.choice
     draws (:95-109, :149-151) and numpy's float32 log on the <= 128 foreground rows (utils/bbox_helper.py:70-86).
+    ignore_regions: None, or [1,I,4] fp32 on the host or the device (:79-87).  The host filters the padded rows (:82) and, if any is
+    left, the device also returns np.where(max IoF > cfg['ignore_iou_thresh'])[0] over ALL candidates; the host takes it out of the
+    negatives with the reference's own set difference (:87) before the one against the positives (:90) -- which of CPython's two
+    difference algorithms runs, and so the order of what is left, depends on both sets' sizes.
     -> rois fp32 [R,5], labels int64 [R], loc_targets, loc_weights fp32 [R,4C] on the device; None when the image has no usable
     ground truth (the caller's numpy path then behaves as the reference does)."""
     from scda_amd.dropin.functions import proposal_target as PT
@@ -199,6 +239,12 @@ def proposal_targets(proposals, cfg, gts_dev, image_info):
     if gts.shape[0] == 0 or props_host.shape[0] + gts.shape[0] == 0:
         return None
     gts = np.ascontiguousarray(gts, dtype=np.float32)
+    ign = None
+    if ignore_regions is not None:
+        ign = backend.host_array(ignore_regions)[0]
+        ign = ign[ign[:, 2] - ign[:, 0] > 1]                                       # remove padded ignore regions (:82)
+        if ign.shape[0] == 0:                                                      # (:83) none left: the step is skipped
+            ign = None
     n_prop, G = props_host.shape[0], gts.shape[0]
     n = n_prop + G
     C, per_image = cfg['num_classes'], cfg['batch_size']
@@ -216,8 +262,16 @@ def proposal_targets(proposals, cfg, gts_dev, image_info):
             pp.copy_(torch.from_numpy(np.ascontiguousarray(props_host, dtype=np.float32)))
             props_dev = pp.to(dev, non_blocking=True)
         bufs = _pt_bufs(n, dev)
-        N.proposal_match(props_dev.contiguous(), g_dev, float(info[0][0]), float(info[0][1]), cfg['positive_iou_thresh'],
-                         cfg['negative_iou_thresh_hi'], cfg['negative_iou_thresh_lo'], bufs)
+        if ign is None:
+            N.proposal_match(props_dev.contiguous(), g_dev, float(info[0][0]), float(info[0][1]), cfg['positive_iou_thresh'],
+                             cfg['negative_iou_thresh_hi'], cfg['negative_iou_thresh_lo'], bufs)
+        else:
+            bufs = _pt_ign_bufs(bufs, dev)
+            N.proposal_match_ign(props_dev.contiguous(), g_dev, float(info[0][0]), float(info[0][1]), cfg['positive_iou_thresh'],
+                                 cfg['negative_iou_thresh_hi'], cfg['negative_iou_thresh_lo'], _upload_rows(ign, dev),
+                                 float(cfg['ignore_iou_thresh']), bufs)
+            bufs["ign_host"][0:n].copy_(bufs["ign_list"][:n], non_blocking=True)
+            bufs["ign_host"][bufs["cap"]:].copy_(bufs["ign_count"], non_blocking=True)
         cap, host = bufs["cap"], bufs["host"]
         host[0:n].copy_(bufs["pos_list"][:n], non_blocking=True)
         host[cap:cap + n].copy_(bufs["neg_list"][:n], non_blocking=True)
@@ -230,6 +284,10 @@ def proposal_targets(proposals, cfg, gts_dev, image_info):
         pos_r = hv[0:n_pos].astype(np.int64)
         pos_g = hv[2 * cap:2 * cap + n].astype(np.int64)[pos_r]
         neg_r = hv[cap:cap + n_neg].astype(np.int64)
+        if ign is not None:
+            iv = bufs["ign_host"].numpy()
+            ign_r = iv[0:int(iv[cap])].astype(np.int64)
+            neg_r = np.array(list(set(neg_r) - set(ign_r)))                           # :87 -- likewise
         neg_r = np.array(list(set(neg_r) - set(pos_r)))                               # :90 -- CPython's set order, kept verbatim
         want_pos = int(cfg['positive_percent'] * per_image)
         if want_pos < n_pos:

@@ -27,7 +27,7 @@ def compute_proposal_targets(proposals, cfg, ground_truth_bboxes, image_info, ig
     if dev.type == 'cuda':
         from scda_amd import device_boxes
         if device_boxes.proposal_targets_legal(cfg, ground_truth_bboxes, ignore_regions, use_ohem):
-            out = device_boxes.proposal_targets(proposals, cfg, ground_truth_bboxes, image_info)   # IoU / matching / gather on the MI355X
+            out = device_boxes.proposal_targets(proposals, cfg, ground_truth_bboxes, image_info, ignore_regions)   # IoU / IoF / matching / gather on the MI355X
             if out is not None:
                 return out
     proposals, gts_all, image_info, ignore_regions = map(_np, (proposals, ground_truth_bboxes, image_info, ignore_regions))

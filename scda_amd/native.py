@@ -308,6 +308,25 @@ def anchor_label(anchors32, gts, neg_thresh, pos_thresh, min_gt_best, bufs):
                                        _p(bufs["pos_list"]), _p(bufs["neg_list"]), _p(bufs["counts"]), _stream()), "scda_anchor_label_hip")
 
 
+def anchor_label_ign(anchors32, gts, neg_thresh, pos_thresh, min_gt_best, anchors64, ign, ign_thresh, bufs):
+    """anchor_label with ignore regions (include/scda_ops.h: scda_anchor_label_ign_hip): ign [I, >=4] fp32 rows on the device,
+    anchors64 the float64 grid the IoF is taken on, ign_thresh the strict threshold (a double).  ign None: I = 0, which is
+    anchor_label"""
+    _req(anchors32, "anchors"); _req(gts, "gts")
+    I = 0
+    if ign is not None:
+        _req(ign, "ign"); _req(anchors64, "anchors64", torch.float64)
+        I = ign.shape[0]
+        if ign.dim() != 2 or ign.shape[1] < 4 or anchors64.shape != anchors32.shape:
+            raise ValueError("anchor_label_ign: ign must be [I, >=4] and anchors64 the grid of anchors32")
+    KA, G = anchors32.shape[0], gts.shape[0]
+    _check(lib().scda_anchor_label_ign_hip(_p(anchors32), KA, _p(gts), G, gts.shape[1], neg_thresh, pos_thresh, min_gt_best,
+                                           _p(anchors64) if I else None, _p(ign) if I else None, I, ign.shape[1] if I else 0, ign_thresh,
+                                           _p(bufs["best_iou"]), _p(bufs["best_gt"]), _p(bufs["gt_best"]), _p(bufs["labels"]),
+                                           _p(bufs["pos_list"]), _p(bufs["neg_list"]), _p(bufs["counts"]), _stream()),
+           "scda_anchor_label_ign_hip")
+
+
 def anchor_finalize(bufs, drop_pos, drop_neg, anchors64, gts, A, fh, fw):
     """-> cls_targets int64 [1,A,fh,fw], loc_targets, loc_masks fp32 [1,4A,fh,fw]"""
     dev = gts.device
@@ -329,6 +348,25 @@ def proposal_match(props, gts, img_h, img_w, pos_thresh, neg_hi, neg_lo, bufs):
                                          pos_thresh, neg_hi, neg_lo, _p(bufs["rois"]), _p(bufs["best_iou"]), _p(bufs["best_gt"]),
                                          _p(bufs["labels"]), _p(bufs["pos_list"]), _p(bufs["neg_list"]), _p(bufs["counts"]), _stream()),
            "scda_proposal_match_hip")
+
+
+def proposal_match_ign(props, gts, img_h, img_w, pos_thresh, neg_hi, neg_lo, ign, ign_thresh, bufs):
+    """proposal_match with ignore regions (include/scda_ops.h: scda_proposal_match_ign_hip): ign [I, >=4] fp32 rows on the device,
+    already filtered by the host; bufs additionally holds ign_flags i8 [n+G], ign_list i32 [n+G], ign_count i32 [2].  ign None:
+    I = 0, which is proposal_match (the three extra buffers are not needed then)"""
+    _req(props, "props"); _req(gts, "gts")
+    I = 0
+    if ign is not None:
+        _req(ign, "ign")
+        I = ign.shape[0]
+        if ign.dim() != 2 or ign.shape[1] < 4:
+            raise ValueError("proposal_match_ign: ign must be [I, >=4]")
+    _check(lib().scda_proposal_match_ign_hip(_p(props), props.shape[0], props.shape[1], _p(gts), gts.shape[0], gts.shape[1], img_h, img_w,
+                                             pos_thresh, neg_hi, neg_lo, _p(ign) if I else None, I, ign.shape[1] if I else 0, ign_thresh,
+                                             _p(bufs["rois"]), _p(bufs["best_iou"]), _p(bufs["best_gt"]), _p(bufs["labels"]),
+                                             _p(bufs["pos_list"]), _p(bufs["neg_list"]), _p(bufs["counts"]),
+                                             _p(bufs["ign_flags"]) if I else None, _p(bufs["ign_list"]) if I else None,
+                                             _p(bufs["ign_count"]) if I else None, _stream()), "scda_proposal_match_ign_hip")
 
 
 def proposal_finalize(cand_rois, sel, gt_of, enc, gts, num_classes, image_index):

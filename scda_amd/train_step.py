@@ -503,17 +503,19 @@ class ScdaTrainer:
             c = self._ones_row_cache = torch.ones(row, dtype=torch.float32, device=self.device)
         return c
 
-    def step(self, image, gts, image_info, target, gt_masks=None, gt_keypoints=None):
+    def step(self, image, gts, image_info, target, gt_masks=None, gt_keypoints=None, ignore_regions=None):
         """image/target [1,3,H,W] on the device; gts [1,G,5]; image_info [1,3]; gt_masks [1,G,H,W] binary (detectors with a mask
-        branch, BASELINE configs[4]); gt_keypoints [1,G,Kp,3] rows (x, y, v) on the host (detectors whose keypoint branch trains)
+        branch, BASELINE configs[4]); gt_keypoints [1,G,Kp,3] rows (x, y, v) on the host (detectors whose keypoint branch trains);
+        ignore_regions [1,I,4] float32 rows (x1, y1, x2, y2) on the host or the device, as the loaders of scda_amd/data.py yield
+        them: background anchors and background RoIs mostly inside one leave the RPN loss and the RCNN sample
         -> dict of 0-dim loss tensors"""
         with P.installed(self.probe):
-            return self._step(image, gts, image_info, target, gt_masks, gt_keypoints)
+            return self._step(image, gts, image_info, target, gt_masks, gt_keypoints, ignore_regions)
 
-    def _step(self, image, gts, image_info, target, gt_masks=None, gt_keypoints=None):
+    def _step(self, image, gts, image_info, target, gt_masks=None, gt_keypoints=None, ignore_regions=None):
         dev, ws, C = self.device, float(self.world_size), self.cluster_num
         x = {'cfg': self.cfg, 'image': image, 'image_info': image_info, 'ground_truth_bboxes': gts,
-             'ignore_regions': None, 'cluster_num': self.cluster_num, 'threshold': self.threshold}
+             'ignore_regions': ignore_regions, 'cluster_num': self.cluster_num, 'threshold': self.threshold}
         if gt_masks is not None:
             x['ground_truth_masks'] = gt_masks
         if gt_keypoints is not None:
