@@ -268,7 +268,10 @@ int scda_proposal_finalize_hip(const float *cand_rois, const int *sel, const int
  * waited for.  Capacity: N <= scda_kmeans_capacity() (1024) points, k <= 8, k <= N.
  * Outputs (the caller's): centres f32 [k,2], labels i32 [N], counts i32 [k], members i32 [k,N], seed_index i32 [k], n_iter i32 [1],
  * status i32 [1]: 0 ok; bit 0 = a cluster went empty; bit 1 = bad arguments or over capacity (only status and n_iter = 0 are
- * written).  Bit 0 has two cases, told apart by n_iter: a cluster went empty DURING Lloyd -> the run ends there, only counts = 0
+ * written); bit 2 = a mean or the tolerance of steps 2-3 is not finite, which is the case exactly when a float32 point is NaN or
+ * infinite: sklearn refuses such input with a ValueError, so the run ends before the seeding (counts = 0 for all k, n_iter = 0 and
+ * status are written, the other outputs keep what they held) and the caller takes the host path, which raises.  Any non-zero
+ * status sends the call to the host path.  Bit 0 has two cases, told apart by n_iter: a cluster went empty DURING Lloyd -> the run ends there, only counts = 0
  * (all k), n_iter = 0 and status are written and the other outputs keep what they held; a cluster is empty only AFTER the final
  * E-step -> every output is written and valid (labels, the real counts with a 0 among them, members, seed_index, centres,
  * n_iter >= 1), the flag says that the reference would raise on the empty cluster. */

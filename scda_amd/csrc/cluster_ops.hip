@@ -81,6 +81,11 @@ __global__ __launch_bounds__(kClusterCap) void kmeans_kernel(const float *rois, 
     }
     __syncthreads();
     const double tol_abs = 1e-4 * ((sred[2] / (double)N + sred[3] / (double)N) / 2.0);
+    if (!(__builtin_isfinite(mx) && __builtin_isfinite(my) && __builtin_isfinite(tol_abs))) {      // (uniform: all read the same sred)
+        if (tid < k) counts[tid] = 0;            // a NaN or infinite coordinate: sklearn raises on it, so the host path answers
+        if (tid == 0) { *status_out = 4; *n_iter_out = 0; }
+        return;
+    }
     const float mxf = (float)mx, myf = (float)my;
     const double x = (double)(xf - mxf), y = (double)(yf - myf);
     if (live) { sx[tid] = x; sy[tid] = y; }

@@ -11,7 +11,8 @@ generator for clusters smaller than `threshold` (:218-220), in the reference's o
 centres and a status word (under 100 bytes, one pinned buffer, one short synchronise of the box logic's side stream), the host
 draws and uploads the picks, and the gather is enqueued on the compute stream behind the features.  Nothing else waits.
 
-What is not covered: sklearn's relocation of a cluster that goes empty during Lloyd (the kernel raises a status flag), more than
+What is not covered: sklearn's relocation of a cluster that goes empty during Lloyd (the kernel raises a status flag), a NaN or infinite
+RoI coordinate (sklearn raises a ValueError on it; the kernel raises another flag so that the host path does), more than
 scda_kmeans_capacity() = 1024 points, more than 8 clusters, features that are not float32 rows on the device.  All of these take
 the unchanged sklearn path for that call, on the same state of the global generator.
 
@@ -112,8 +113,9 @@ def cluster_targets(rois, features, N_cluster=4, threshold=128):
         host[:head].copy_(work[:head], non_blocking=True)
         aux.synchronize()
     hv = host.numpy()
-    if int(hv[3 * k + 1]) != 0:       # a cluster went empty: sklearn's relocation is not restated (the global generator is untouched so far)
-        return _host_path(rois, features, k, threshold, "a cluster went empty")
+    if int(hv[3 * k + 1]) != 0:       # a cluster went empty (sklearn's relocation is not restated) or a point is not finite (sklearn raises);
+        # the global generator is untouched so far
+        return _host_path(rois, features, k, threshold, "kernel status %d" % int(hv[3 * k + 1]))
     counts = hv[2 * k:3 * k].copy()
     centres = hv[:2 * k].view(np.float32).reshape(k, 2).copy()
     picks = None

@@ -62,7 +62,8 @@ def _assign(x, y, centres):
 
 def kmeans(rois, k, first=None, uniforms=None):
     """-> dict(centres float32 [k,2], labels int32 [N], counts int32 [k], seed_index int32 [k], n_iter, status); status bit 0: a cluster
-    went empty (sklearn would relocate it: not restated, the other outputs are then unspecified), bit 1: bad arguments / over capacity"""
+    went empty (sklearn would relocate it: not restated, the other outputs are then unspecified), bit 1: bad arguments / over capacity,
+    bit 2: a mean or the tolerance is not finite (a NaN or infinite point, on which sklearn raises)"""
     X = roi_centres(rois)
     N = X.shape[0]
     if not (1 <= k <= MAX_K and k <= N <= CAPACITY):
@@ -70,9 +71,12 @@ def kmeans(rois, k, first=None, uniforms=None):
     if first is None:
         first, uniforms = seeding_constants(N, k)
     Xd = X.astype(np.float64)
-    mean64 = np.array([sum64(Xd[:, 0]) / N, sum64(Xd[:, 1]) / N])
-    d0, d1 = Xd[:, 0] - mean64[0], Xd[:, 1] - mean64[1]
-    tol_abs = TOL * ((sum64(d0 * d0) / N + sum64(d1 * d1) / N) / 2.0)
+    with np.errstate(invalid="ignore", over="ignore"):
+        mean64 = np.array([sum64(Xd[:, 0]) / N, sum64(Xd[:, 1]) / N])
+        d0, d1 = Xd[:, 0] - mean64[0], Xd[:, 1] - mean64[1]
+        tol_abs = TOL * ((sum64(d0 * d0) / N + sum64(d1 * d1) / N) / 2.0)
+    if not (np.isfinite(mean64).all() and np.isfinite(tol_abs)):
+        return {"status": 4}                               # a NaN or infinite point: sklearn raises, the host path answers
     mean32 = mean64.astype(np.float32)
     Xc = (X - mean32[None, :]).astype(np.float64)          # float32 subtraction, as sklearn centres float32 data
     x, y = Xc[:, 0], Xc[:, 1]
