@@ -331,8 +331,13 @@ int scda_box_predict_hip(const float *rois, const int *roi_counts, int B, int P,
  * counts; the score column of boxes is rewritten IN PLACE with each surviving row's final score (a discarded row's score is
  * unspecified), so boxes[first + keep[j]] is the reference's j-th returned row.  No workspace.  A list of length 0 gives count 0.
  * Capacity: max_n <= scda_soft_nms_capacity() = 2048 rows per list (its working copy fills 48 KB of LDS); a larger max_n, S <= 0 or
- * a method outside 0..2 returns SCDA_EINVAL before anything is launched.  Inputs are finite: the result for NaN scores is undefined
- * (it stays within bounds and terminates).  Gaussian caveat: the weight is the DEVICE's double exp rounded to float32, the
+ * a method outside 0..2 returns SCDA_EINVAL before anything is launched.  A list LONGER than max_n is cut to its first max_n rows:
+ * the sweep runs on those alone, the rows beyond them are neither read nor written and never appear in keep.  Non-finite input
+ * follows the reference's own comparisons.  Selection is `maxscore < boxes[pos, 4]` from maxscore = boxes[i, 4]: a NaN score at the
+ * head of the live range is selected, a NaN score anywhere else is never greater (it is selected once it stands at the head), +-inf
+ * order as numbers; a rescored NaN is not below the threshold, so it stays.  Overlap uses the reference's inline min / max (`a if
+ * a <= b else b`, the selected row's coordinate first), so a row with a NaN coordinate is not touched by any selected row.  Every
+ * index and loop bound is independent of the values: the sweep stays within bounds and terminates.  Gaussian caveat: the weight is the DEVICE's double exp rounded to float32, the
  * reference's is glibc's; the two may differ in the last place of the double, which changes the float32 weight only when the value
  * lies within about 2^-53 relative of a float32 rounding midpoint -- about one evaluation in 2^28. */
 int scda_soft_nms_capacity(void);

@@ -9,7 +9,9 @@
 // The working copy of a list -- x1, y1, x2, y2, score, original index -- lives in LDS (6 x 2048 x 4 bytes = 48 KB) with two short
 // scratch lists for the compaction (4 KB).  One iteration i on the live range [i, N):
 //   1. m = the first position of [i, N) with the largest score (the reference updates on strict <: the lowest position wins a tie);
-//      entries i and m are swapped; t = entry i.
+//      entries i and m are swapped; t = entry i.  Non-finite scores follow the reference's `maxscore < boxes[pos, 4]` from
+//      maxscore = boxes[i, 4]: a NaN AT i is selected (nothing is greater than it), a NaN anywhere else is never greater; +-inf order
+//      as numbers.  m is the same in every lane whatever the scores hold.
 //   2. every pos in (i, N) in parallel: the IoU(+1) with t in the reference's arithmetic -- Cython writes the source's "+ 1" beside
 //      a C float as "+ 1.0", so those sums and the products around them are evaluated in double and rounded once where they are
 //      assigned to a `cdef float`; iw * ih and the division are float32.  Only a row with iw > 0 and ih > 0 is touched at all: one
@@ -59,19 +61,22 @@ __global__ __launch_bounds__(kSoftWave) void soft_nms_segments_kernel(float *__r
     for (int i = 0; i < N; ++i) {
         // ---- 1. the first maximum of [i, N)
         constexpr int kNone = 0x7fffffff;
+        const float s0 = ssc[i];                                        // (one address: the same value in every lane)
         float bs = 0.f;
         int bp = kNone;
         for (int p = i + lane; p < N; p += kSoftWave) {
             const float v = ssc[p];
-            if (bp == kNone || v > bs) { bs = v; bp = p; }              // ascending p per lane: strict > keeps the lowest position
+            if (v == v && (bp == kNone || v > bs)) { bs = v; bp = p; }  // ascending p per lane: strict > keeps the lowest position
         }
+        // a NaN is never a candidate, so the (bs, bp) pairs are totally ordered and the butterfly leaves ONE pair in all lanes
 #pragma unroll
         for (int off = 1; off < kSoftWave; off <<= 1) {
             const float os = __shfl_xor(bs, off, kSoftWave);
             const int op = __shfl_xor(bp, off, kSoftWave);
             if (op != kNone && (bp == kNone || os > bs || (os == bs && op < bp))) { bs = os; bp = op; }
         }
-        const int m = min(max(bp, i), N - 1);                           // (clamp: a guard, bp is in [i, N) for finite scores)
+        // a NaN at i is its own maximum (`NaN < v` never holds); otherwise place i is a candidate and bp is in [i, N) (clamp: a guard)
+        const int m = s0 != s0 ? i : min(max(bp, i), N - 1);
         const float tx1 = sx1[m], ty1 = sy1[m], tx2 = sx2[m], ty2 = sy2[m], ts = ssc[m];
         const unsigned tid_ = sid[m];
         wave_sync();                                                    // every lane holds t before lane 0 overwrites place m
@@ -88,8 +93,10 @@ __global__ __launch_bounds__(kSoftWave) void soft_nms_segments_kernel(float *__r
             bool dead = false;
             if (p < N) {
                 const float x1 = sx1[p], y1 = sy1[p], x2 = sx2[p], y2 = sy2[p];
-                const float iw = (float)((double)(fminf(tx2, x2) - fmaxf(tx1, x1)) + 1.0);
-                const float ih = (float)((double)(fminf(ty2, y2) - fmaxf(ty1, y1)) + 1.0);
+                // the reference's own min / max (cython_nms.pyx:28-32: `a if a <= b else b`, t's coordinate first): a NaN in t's
+                // coordinate gives the row's, a NaN in the row's is returned (fminf / fmaxf would drop it) and the row is not touched
+                const float iw = (float)((double)((tx2 <= x2 ? tx2 : x2) - (tx1 >= x1 ? tx1 : x1)) + 1.0);
+                const float ih = (float)((double)((ty2 <= y2 ? ty2 : y2) - (ty1 >= y1 ? ty1 : y1)) + 1.0);
                 if (iw > 0.f && ih > 0.f) {
                     const float area = (float)(((double)(x2 - x1) + 1.0) * ((double)(y2 - y1) + 1.0));
                     const float inter = iw * ih;

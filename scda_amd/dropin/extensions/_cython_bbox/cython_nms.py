@@ -27,13 +27,25 @@ def nms(dets, thresh):
     return np.where(dead == 0)[0]
 
 
+def _max(a, b):
+    """the reference's own inline max / min (cython_nms.pyx:28-32); they differ from the builtins when a coordinate is NaN"""
+    return a if a >= b else b
+
+
+def _min(a, b):
+    return a if a <= b else b
+
+
 def soft_nms(boxes_in, sigma=0.5, Nt=0.3, threshold=0.001, method=0):
     boxes = np.array(boxes_in, dtype=np.float32, copy=True)
     n = boxes.shape[0]
     inds = np.arange(n)
     i = 0
     while i < n:
-        m = i + int(np.argmax(boxes[i:n, 4]))
+        # the reference starts from maxscore = boxes[i, 4] and moves on `maxscore < boxes[pos, 4]` (cython_nms.pyx:116-131): a NaN at i
+        # is selected (nothing is greater than it), a NaN anywhere else is never greater; np.argmax alone would take the first NaN
+        s = boxes[i:n, 4]
+        m = i if s[0] != s[0] else i + int(np.argmax(np.where(np.isnan(s), f32(-np.inf), s)))
         boxes[[i, m]] = boxes[[m, i]]
         inds[[i, m]] = inds[[m, i]]
         tx1, ty1, tx2, ty2 = boxes[i, :4]
@@ -42,8 +54,8 @@ def soft_nms(boxes_in, sigma=0.5, Nt=0.3, threshold=0.001, method=0):
             x1, y1, x2, y2 = boxes[pos, :4]
             # Cython writes the source's "+ 1" next to a C float as "+ 1.0": those sums and the products around them are evaluated
             # in double and rounded once on assignment to the `cdef float` (cython_nms.pyx:163-170)
-            iw = f32(f64(min(tx2, x2) - max(tx1, x1)) + 1.0)
-            ih = f32(f64(min(ty2, y2) - max(ty1, y1)) + 1.0)
+            iw = f32(f64(_min(tx2, x2) - _max(tx1, x1)) + 1.0)
+            ih = f32(f64(_min(ty2, y2) - _max(ty1, y1)) + 1.0)
             if iw > 0 and ih > 0:
                 area = f32((f64(x2 - x1) + 1.0) * (f64(y2 - y1) + 1.0))
                 ua = f32((f64(tx2 - tx1) + 1.0) * (f64(ty2 - ty1) + 1.0) + f64(area) - f64(iw * ih))

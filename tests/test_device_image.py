@@ -37,15 +37,23 @@ def apply_tables(a, new_w, new_h, filter):
 
 SIZES = [(64, 128, 32, 64), (37, 91, 50, 120), (100, 60, 100, 33), (48, 48, 96, 48), (128, 256, 75, 150), (20, 30, 7, 11),
          (33, 65, 33, 65), (256, 512, 128, 256)]
+# one- and two-pixel sides on either end and extreme down-scales (a 1201-tap window for 300 -> 1); tests/test_device_image_edges_gpu.py
+# holds the kernels to PIL at the same sizes
+EDGE_SIZES = [(1, 1, 1, 1), (1, 1, 5, 7), (1, 9, 1, 3), (9, 1, 4, 1), (2, 2, 64, 64), (300, 400, 1, 1), (257, 3, 2, 300), (3, 257, 300, 2),
+              (64, 64, 63, 65), (2, 700, 2, 1), (1, 4096, 1, 16)]
 
 
 @pytest.mark.parametrize("filter", sorted(PIL_FILTERS))
 def test_tables_reproduce_pil_resize(filter):
     rng = np.random.default_rng(3)
-    for H, W, nh, nw in SIZES:
+    for H, W, nh, nw in SIZES + EDGE_SIZES:
         a = rng.integers(0, 256, (H, W, 3), dtype=np.uint8)
         ref = np.asarray(Image.fromarray(a).resize((nw, nh), PIL_FILTERS[filter]))
         assert np.array_equal(apply_tables(a, nw, nh, filter), ref), (filter, H, W, nh, nw)
+    for H, W, nh, nw in EDGE_SIZES:                                     # and one channel
+        a = rng.integers(0, 256, (H, W, 1), dtype=np.uint8)
+        ref = np.asarray(Image.fromarray(a[:, :, 0]).resize((nw, nh), PIL_FILTERS[filter]))
+        assert np.array_equal(apply_tables(a, nw, nh, filter)[:, :, 0], ref), (filter, H, W, nh, nw)
 
 
 def test_default_filter_of_this_pillow_is_bicubic():
