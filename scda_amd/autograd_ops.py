@@ -93,7 +93,7 @@ class Conv2dFn(Function):
                 dw = None
         elif want_b:
             sink = _sink(ctx.bias_ref)
-            db = N.bias_grad_nchw(dy, out=sink)
+            db = N.conv2d_bias_grad(dy, x, w.shape, stride, pad, out=sink, row_period=rp)
             if sink is not None:
                 db = None
         return dx, dw, db, None, None, None, None, None, None
@@ -141,7 +141,7 @@ class ConvPoolFn(Function):
                 dw = None
         elif want_b:
             sink = _sink(ctx.bias_ref)
-            db = N.bias_grad_nchw(dyc, out=sink)
+            db = N.conv2d_bias_grad(dyc, x, w.shape, 1, 1, out=sink)
             if sink is not None:
                 db = None
         return dx, dw, db, None, None
@@ -377,7 +377,8 @@ class SoftmaxCEFn(Function):
 
     @staticmethod
     def forward(ctx, logits, targets, ignore_index):
-        out2, probs = N.softmax_ce_fwd(_c(logits), _c(targets), ignore_index)
+        targets = _c(targets)      # the backward reads the tensor the forward ran on: a strided view's rows are not `targets` rows
+        out2, probs = N.softmax_ce_fwd(_c(logits), targets, ignore_index)
         ctx.save_for_backward(probs, targets, out2)
         ctx.ignore = ignore_index
         return out2[0]
@@ -410,7 +411,8 @@ class SmoothL1Fn(Function):
 
     @staticmethod
     def forward(ctx, pred, mask, target, sigma, scale):
-        pred = _c(pred)
+        pred, target = _c(pred), _c(target)
+        mask = _c(mask) if mask is not None else None
         ctx.save_for_backward(pred, mask, target)
         ctx.cfg = (sigma, scale)
         return N.smooth_l1_fwd(pred, mask, target, sigma, scale)[0]

@@ -122,11 +122,20 @@ class Conv2d(FusedProducer, nn.Conv2d):
         return s + (f", fused_act={self.fused_act}" if self.fused_act else "")
 
 
+def _refuse_transposed_extras(m):
+    """the two transposed convolutions below read the weight as one dense [in, out, k, k] block with one tap per output pixel: what
+    nn.ConvTranspose2d would accept beyond that is refused, not ignored"""
+    if m.groups != 1 or m.dilation != (1, 1) or m.output_padding != (0, 0):
+        raise NotImplementedError("scda_amd.%s: groups/dilation/output_padding are not part of the SCDA path"
+                                  % type(m).__name__)
+
+
 class ConvTranspose1x1(nn.ConvTranspose2d):
     """nn.ConvTranspose2d(kernel_size=1, stride=1): a 1x1 conv with the [in,out,1,1] weight read transposed."""
 
     def __init__(self, cin, cout, **kw):
         super().__init__(cin, cout, kernel_size=1, stride=1, padding=0, **kw)
+        _refuse_transposed_extras(self)
 
     def forward(self, x):
         w = self.weight.transpose(0, 1).contiguous()  # [out,in,1,1]; 96 floats -- autograd handles the permutation
@@ -141,6 +150,7 @@ class ConvTranspose2x2s2(nn.ConvTranspose2d):
 
     def __init__(self, cin, cout, fused_act=A.ACT_NONE, slope=0.01, **kw):
         super().__init__(cin, cout, kernel_size=2, stride=2, padding=0, **kw)
+        _refuse_transposed_extras(self)
         self.fused_act, self.slope = fused_act, slope
 
     def forward(self, x):
@@ -307,7 +317,12 @@ class BatchNorm2d(nn.BatchNorm2d):
         self.fused_act = fused_act
         self.slope = slope
 
+    def _check_channels(self, x):
+        if x.dim() != 4 or x.shape[1] != self.num_features:    # as nn.BatchNorm2d: the kernels size every per-channel read by x
+            raise ValueError(f"scda_amd.BatchNorm2d({self.num_features}): expected a [B, {self.num_features}, H, W] input, got {tuple(x.shape)}")
+
     def forward(self, x):
+        self._check_channels(x)
         if not self.training:   # validation of vgg16_bn, dis_patch.eval(): running statistics, nothing is updated
             if self.running_mean is None:
                 raise NotImplementedError("scda_amd.BatchNorm2d: eval mode without running statistics")
@@ -331,6 +346,7 @@ class BatchNorm2d(nn.BatchNorm2d):
         """relu(self(x) + residual) -- the residual join of a ResNet block.  One kernel in training mode on the maps the plane form
         serves (batch 1); the batch norm followed by the join kernel otherwise (eval mode, other shapes, a fused activation of its
         own, the parity tests' replay hook: they replay the join's mask)."""
+        self._check_channels(x)
         if (self.training and self.fused_act == A.ACT_NONE and P.replay() is None and self.momentum is not None and x.dim() == 4
                 and x.shape == residual.shape and N.batchnorm_add_relu_ok(x) and x.is_contiguous() and residual.is_contiguous()
                 and N.aligned16(x, residual) and not os.environ.get("SCDA_BN_NO_JOIN")):

@@ -1387,9 +1387,17 @@ def conv2d_wino_pack(w, for_dgrad=False, cache=True):
     return out
 
 
+def _req_wino(x, u, bias, M, mask_src=None):
+    """the Winograd launches read the bias dword by dword from its first element (x and the mask are checked by the callers, the packed
+    filters come from conv2d_wino_pack): a strided or short one is refused here"""
+    if bias is not None and (not bias.is_contiguous() or bias.numel() != M or bias.dtype != torch.float32):
+        raise ValueError(f"conv2d_wino: bias must be {M} contiguous float32 values, got {tuple(bias.shape)} {bias.dtype}")
+
+
 def conv2d_wino(x, u, bias, M, act=ACT_NONE, slope=0.01, mask_src=None, mask_slope=0.0, for_dgrad=False, row_period=0):
     """one Winograd launch: y [B, M, H, W] from x [B, C, H, W] and packed filters u (forward, or the data gradient with x = dy);
     row_period = 7 on a [1, C, R * 7, 7] tensor: a stack of R independent 7 x 7 maps"""
+    _req_wino(x, u, bias, M, mask_src)
     B, C, H, W = x.shape
     y = torch.empty(B, M, H, W, dtype=torch.float32, device=x.device)
     ws, n = _conv_ws(B, C, H, W, M, 3, 3, 1, 1, x.device)
@@ -1413,6 +1421,7 @@ def conv_pool_fusable(B, Cin, IH, IW, Cout, KH, KW, stride, pad, row_period=0):
 
 def conv2d_wino_pool(x, u, bias, M, act=ACT_NONE, slope=0.01):
     """-> (pooled [B, M, H/2, W/2], winner uint8 [B, M, H/2, W/2]) of maxpool2x2(act(conv3x3(x) + bias)), one launch"""
+    _req_wino(x, u, bias, M)
     B, C, H, W = x.shape
     y = torch.empty(B, M, H // 2, W // 2, dtype=torch.float32, device=x.device)
     idx = torch.empty(B, M, H // 2, W // 2, dtype=torch.uint8, device=x.device)
@@ -1564,6 +1573,19 @@ def conv2d_wgrad_bias(dy, x, w_shape, stride, pad, out=None, db_out=None, row_pe
     return out, db_out
 
 
+def conv2d_bias_grad(dy, x, w_shape, stride, pad, out=None, row_period=0):
+    """db of a conv layer on its own, with the bits conv2d_wgrad_bias gives for the layer: where that call runs a kernel with the
+    bias gradient fused in (Winograd, or the fusable direct shapes) the same kernel runs here and its weight gradient is dropped, so
+    a gradient does not depend on which others were asked for.  (No SCDA net trains a bias under a frozen weight.)"""
+    _req(dy, "dy"); _req(x, "x")
+    B, Cin, IH, IW = x.shape
+    Cout, _, KH, KW = w_shape
+    if not (wino_wgrad_ok(B, Cin, IH, IW, Cout, KH, KW, stride, pad, row_period)
+            or lib().scda_conv2d_wgrad_bias_fusable(B, Cout, dy.shape[2], dy.shape[3], _p(dy))):
+        return bias_grad_nchw(dy, out=out)
+    return conv2d_wgrad_bias(dy, x, w_shape, stride, pad, db_out=out, row_period=row_period)[1]
+
+
 def gemm(a, b, M, N, K, lda, ldb, trans_a=False, trans_b=False, bias=None, bias_on_n=True, act=ACT_NONE, slope=0.01,
          out=None, accumulate=False):
     """C[M,N] (+)= op(A) op(B) (+bias) -> act.  See include/scda_ops.h for the operand layouts."""
@@ -1584,13 +1606,21 @@ def gemm(a, b, M, N, K, lda, ldb, trans_a=False, trans_b=False, bias=None, bias_
 
 def linear_fwd(x, w, bias, act=ACT_NONE):
     """y[M,out] = x[M,in] @ w[out,in]^T + b"""
+    if x.dim() != 2 or w.dim() != 2 or w.shape[1] != x.shape[1]:          # (gemm checks device, dtype and contiguity)
+        raise ValueError(f"linear: x {tuple(x.shape)} and w {tuple(w.shape)} must be [M,in] and [out,in]")
     M, K = x.shape
     N = w.shape[0]
+    if bias is not None:
+        _req(bias, "bias")
+        if bias.numel() != N:
+            raise ValueError(f"linear: bias must have {N} values, got {bias.numel()}")
     return gemm(x, w, M, N, K, K, K, False, False, bias, True, act)
 
 
 def linear_dgrad(dy, w):
     """dx[M,in] = dy[M,out] @ w[out,in]"""
+    if dy.dim() != 2 or w.dim() != 2 or w.shape[0] != dy.shape[1]:
+        raise ValueError(f"linear: dy {tuple(dy.shape)} and w {tuple(w.shape)} must be [M,out] and [out,in]")
     M, K = dy.shape
     N = w.shape[1]
     return gemm(dy, w, M, N, K, K, N, False, True)
@@ -1598,12 +1628,36 @@ def linear_dgrad(dy, w):
 
 def linear_wgrad(dy, x, out=None, accumulate=True):
     """dw[out,in] (+)= dy[M,out]^T @ x[M,in]; with `out`: accumulates into it unless accumulate=False (overwrite)"""
+    if dy.dim() != 2 or x.dim() != 2 or x.shape[0] != dy.shape[0]:
+        raise ValueError(f"linear: dy {tuple(dy.shape)} and x {tuple(x.shape)} must be [M,out] and [M,in]")
     Kb, M = dy.shape
     N = x.shape[1]
+    if out is not None and out.numel() != M * N:
+        raise ValueError(f"linear: the weight gradient has {M * N} values, out {out.numel()}")
     return gemm(dy, x, M, N, Kb, M, N, True, True, out=out, accumulate=out is not None and accumulate)
 
 
 # ------------------------------------------------------ layer kernels -------
+def _req_like(t, name, ref, ref_name, dtype=torch.float32):
+    """t: a contiguous device tensor of `dtype` with as many elements as `ref`"""
+    if _req(t, name, dtype).numel() != ref.numel():
+        raise ValueError(f"{name} must have the {ref.numel()} elements of {ref_name}, got {t.numel()}")
+    return t
+
+
+def _req_channels(C, **vectors):
+    """per-channel vectors of a batch norm (None: not given): contiguous float32 of C elements each"""
+    for name, v in vectors.items():
+        if v is not None and _req(v, name).numel() != C:
+            raise ValueError(f"{name} must have one value per channel ({C}), got {v.numel()}")
+
+
+def _req_map(x, name="x"):
+    if _req(x, name).dim() != 4:
+        raise ValueError(f"{name} must be [B, C, H, W], got {tuple(x.shape)}")
+    return x.shape
+
+
 def maxpool2x2_fwd(x):
     _req(x, "x")
     B, C, H, W = x.shape
@@ -1617,11 +1671,13 @@ def maxpool2x2_bwd(dy, idx, x_shape, relu_y=None):
     """relu_y = the pool's output: additionally applies the gradient of a ReLU that produced the pool's input"""
     _req(dy, "dy"); _req(idx, "idx", torch.uint8)
     B, C, H, W = x_shape
+    if tuple(dy.shape) != (B, C, H // 2, W // 2) or idx.shape != dy.shape:
+        raise ValueError(f"maxpool2x2_bwd: dy and idx must be {(B, C, H // 2, W // 2)}, got {tuple(dy.shape)} and {tuple(idx.shape)}")
     dx = torch.empty(B, C, H, W, dtype=torch.float32, device=dy.device)
     if relu_y is None:
         _check(lib().scda_maxpool2x2_bwd_hip(_p(dy), _p(idx), _p(dx), B * C, H, W, _stream()), "scda_maxpool2x2_bwd_hip")
     else:
-        _req(relu_y, "relu_y")
+        _req_like(relu_y, "relu_y", dy, "dy")
         _check(lib().scda_maxpool2x2_bwd_relu_hip(_p(dy), _p(idx), _p(relu_y), _p(dx), B * C, H, W, _stream()),
                "scda_maxpool2x2_bwd_relu_hip")
     return dx
@@ -1655,7 +1711,7 @@ def act_fwd(x, mode, slope=0.01):
 
 
 def act_bwd(dy, y, mode, slope=0.01):
-    _req(dy, "dy"); _req(y, "y")
+    _req(dy, "dy"); _req_like(y, "y", dy, "dy")
     dx = torch.empty_like(dy)
     _check(lib().scda_act_bwd_hip(_p(dy), _p(y), _p(dx), dy.numel(), mode, slope, _stream()), "scda_act_bwd_hip")
     return dx
@@ -1664,7 +1720,7 @@ def act_bwd(dy, y, mode, slope=0.01):
 def axpby(a, b, alpha=1.0, beta=1.0):
     _req(a, "a")
     if b is not None:
-        _req(b, "b")
+        _req_like(b, "b", a, "a")
     y = torch.empty_like(a)
     _check(lib().scda_axpby_hip(_p(a), _p(b), _p(y), a.numel(), alpha, beta, _stream()), "scda_axpby_hip")
     return y
@@ -1677,7 +1733,7 @@ def dropout_mask(shape, p, seed, device):
 
 
 def dropout_apply(x, mask, scale):
-    _req(x, "x"); _req(mask, "mask", torch.uint8)
+    _req(x, "x"); _req_like(mask, "mask", x, "x", torch.uint8)
     y = torch.empty_like(x)
     _check(lib().scda_dropout_apply_hip(_p(x), _p(mask), _p(y), x.numel(), scale, _stream()), "scda_dropout_apply_hip")
     return y
@@ -1687,7 +1743,7 @@ def dropout_seeded(x, p, seed, scale, relu_src=None):
     """y = keep(seed, i) ? x * scale : 0 (no mask tensor; the backward calls this again with dy); relu_src: see scda_ops.h"""
     _req(x, "x")
     if relu_src is not None:
-        _req(relu_src, "relu_src")
+        _req_like(relu_src, "relu_src", x, "x")
     y = torch.empty_like(x)
     _check(lib().scda_dropout_seeded_hip(_p(x), _p(y), x.numel(), p, seed & 0xFFFFFFFFFFFFFFFF, scale, _p(relu_src), _stream()),
            "scda_dropout_seeded_hip")
@@ -1697,12 +1753,20 @@ def dropout_seeded(x, p, seed, scale, relu_src=None):
 def sigmoid_bce_rows_fwd(x, t, w, scale, out=None, want_prob=True):
     """out[0] (+)= scale * sum_c w[c] * mean_i BCE(sigmoid(x[c,i]), t[c or 0, i]); -> (out [1], prob [C,n] | None)"""
     _req(x, "x"); _req(t, "t")
+    if x.dim() != 2:
+        raise ValueError("logits must be [C,n]")
     C, n = x.shape
-    t_rows = t.numel() // n
+    t_rows = t.numel() // n if n else 0
     if t.numel() != t_rows * n or t_rows not in (1, C):
         raise ValueError("labels must be [1,n] or [C,n]")
     if w is not None:
         _req(w, "w")
+        if w.numel() != C:
+            raise ValueError(f"weights must have one value per row ({C}), got {w.numel()}")
+    if out is not None:
+        _req(out, "out")
+        if out.numel() != 1:
+            raise ValueError("out must hold one value")
     acc = out is not None
     if out is None:
         out = torch.empty(1, dtype=torch.float32, device=x.device)
@@ -1713,9 +1777,21 @@ def sigmoid_bce_rows_fwd(x, t, w, scale, out=None, want_prob=True):
 
 
 def sigmoid_bce_rows_bwd(prob, t, w, scale, g):
+    _req(prob, "prob"); _req(t, "t"); _req(g, "g")
+    if prob.dim() != 2:
+        raise ValueError("prob must be [C,n]")
     C, n = prob.shape
+    t_rows = t.numel() // n if n else 0
+    if t.numel() != t_rows * n or t_rows not in (1, C):
+        raise ValueError("labels must be [1,n] or [C,n]")
+    if w is not None:
+        _req(w, "w")
+        if w.numel() != C:
+            raise ValueError(f"weights must have one value per row ({C}), got {w.numel()}")
+    if g.numel() != 1:
+        raise ValueError("g must hold one value")
     dx = torch.empty_like(prob)
-    _check(lib().scda_sigmoid_bce_rows_bwd_hip(_p(prob), _p(t), t.numel() // n, _p(w), C, n, scale, _p(g), _p(dx), _stream()),
+    _check(lib().scda_sigmoid_bce_rows_bwd_hip(_p(prob), _p(t), t_rows, _p(w), C, n, scale, _p(g), _p(dx), _stream()),
            "scda_sigmoid_bce_rows_bwd_hip")
     return dx
 
@@ -1742,7 +1818,11 @@ def colsum(dy, out=None):
 
 def softmax_ce_fwd(logits, targets, ignore_index=-100):
     _req(logits, "logits"); _req(targets, "targets", torch.int64)
+    if logits.dim() != 2:
+        raise ValueError("logits must be [R,C]")
     R, C = logits.shape
+    if targets.numel() != R:
+        raise ValueError(f"targets must hold one class per row ({R}), got {targets.numel()}")
     probs = torch.empty_like(logits)
     out2 = torch.empty(2, dtype=torch.float32, device=logits.device)
     _check(lib().scda_softmax_ce_fwd_hip(_p(logits), _p(targets), R, C, ignore_index, _p(probs), _p(out2), _stream()),
@@ -1751,8 +1831,14 @@ def softmax_ce_fwd(logits, targets, ignore_index=-100):
 
 
 def softmax_ce_bwd(probs, targets, out2, g, ignore_index=-100):
-    _req(probs, "probs"); _req(g, "g")
+    _req(probs, "probs"); _req(targets, "targets", torch.int64); _req(out2, "out2"); _req(g, "g")
+    if probs.dim() != 2:
+        raise ValueError("probs must be [R,C]")
     R, C = probs.shape
+    if targets.numel() != R:
+        raise ValueError(f"targets must hold one class per row ({R}), got {targets.numel()}")
+    if out2.numel() != 2 or g.numel() != 1:
+        raise ValueError("out2 must hold two values and g one")
     dx = torch.empty_like(probs)
     _check(lib().scda_softmax_ce_bwd_hip(_p(probs), _p(targets), R, C, ignore_index, _p(out2), _p(g), _p(dx), _stream()),
            "scda_softmax_ce_bwd_hip")
@@ -1775,10 +1861,18 @@ def accuracy(logits, targets, ignore_index=-1):
     return out
 
 
-def smooth_l1_fwd(pred, mask, target, sigma, scale):
+def _req_smooth_l1(pred, mask, target):
     _req(pred, "pred"); _req(target, "target")
+    if target.shape != pred.shape:
+        raise ValueError(f"target must have the shape of pred {tuple(pred.shape)}, got {tuple(target.shape)}")
     if mask is not None:
         _req(mask, "mask")
+        if mask.shape != pred.shape:
+            raise ValueError(f"mask must have the shape of pred {tuple(pred.shape)}, got {tuple(mask.shape)}")
+
+
+def smooth_l1_fwd(pred, mask, target, sigma, scale):
+    _req_smooth_l1(pred, mask, target)
     L = lib()
     ws = torch.empty(L.scda_smooth_l1_workspace_bytes() // 4, dtype=torch.float32, device=pred.device)
     out = torch.empty(1, dtype=torch.float32, device=pred.device)
@@ -1788,6 +1882,9 @@ def smooth_l1_fwd(pred, mask, target, sigma, scale):
 
 
 def smooth_l1_bwd(pred, mask, target, sigma, scale, g):
+    _req_smooth_l1(pred, mask, target); _req(g, "g")
+    if g.numel() != 1:
+        raise ValueError("g must hold one value")
     dp = torch.empty_like(pred)
     _check(lib().scda_smooth_l1_bwd_hip(_p(pred), _p(mask), _p(target), pred.numel(), sigma, scale, _p(g), _p(dp), _stream()),
            "scda_smooth_l1_bwd_hip")
@@ -1805,8 +1902,9 @@ def instnorm_fwd(x, eps, act, slope):
 
 
 def instnorm_bwd(dy, x, mean, rstd, act, slope):
-    _req(dy, "dy"); _req(x, "x")
-    B, C, H, W = x.shape
+    B, C, H, W = _req_map(x)
+    _req_like(dy, "dy", x, "x")
+    _req_channels(B * C, mean=mean, rstd=rstd)
     dx = torch.empty_like(x)
     _check(lib().scda_instnorm_bwd_hip(_p(dy), _p(x), _p(mean), _p(rstd), _p(dx), B * C, H * W, act, slope, _stream()),
            "scda_instnorm_bwd_hip")
@@ -1852,8 +1950,10 @@ def _bn_ws(B, C, HW, device):
 
 
 def batchnorm_fwd(x, gamma, beta, run_mean, run_var, eps, momentum, act, slope):
-    _req(x, "x"); _req(gamma, "gamma"); _req(beta, "beta")
-    B, C, H, W = x.shape
+    B, C, H, W = _req_map(x)
+    if gamma is None or beta is None:
+        raise TypeError("batchnorm_fwd: gamma and beta must be tensors")
+    _req_channels(C, gamma=gamma, beta=beta, running_mean=run_mean, running_var=run_var)
     y = torch.empty_like(x)
     mean = torch.empty(C, dtype=torch.float32, device=x.device)
     rstd = torch.empty(C, dtype=torch.float32, device=x.device)
@@ -1865,8 +1965,13 @@ def batchnorm_fwd(x, gamma, beta, run_mean, run_var, eps, momentum, act, slope):
 
 def batchnorm_bwd(dy, x, gamma, beta, mean, rstd, act, slope, need_dx=True, out=None):
     """out = (dgamma, dbeta) buffers to accumulate into, or None to allocate"""
-    _req(dy, "dy"); _req(x, "x")
-    B, C, H, W = x.shape
+    B, C, H, W = _req_map(x)
+    _req_like(dy, "dy", x, "x")
+    if any(v is None for v in (gamma, beta, mean, rstd)):
+        raise TypeError("batchnorm_bwd: gamma, beta, mean and rstd must be tensors")
+    _req_channels(C, gamma=gamma, beta=beta, mean=mean, rstd=rstd)
+    if out is not None:
+        _req_channels(C, dgamma=out[0], dbeta=out[1])
     dx = torch.empty_like(x) if need_dx else None
     dg, db = out if out is not None else (torch.empty(C, dtype=torch.float32, device=x.device),
                                           torch.empty(C, dtype=torch.float32, device=x.device))
@@ -1889,10 +1994,13 @@ def aligned16(*tensors):
 
 
 def batchnorm_add_relu_fwd(x, residual, gamma, beta, run_mean, run_var, eps, momentum):
-    _req(x, "x"); _req(residual, "residual"); _req(gamma, "gamma"); _req(beta, "beta")
+    B, C, H, W = _req_map(x)
+    _req(residual, "residual")
     if residual.shape != x.shape:
         raise ValueError("batchnorm_add_relu_fwd: shape mismatch")
-    B, C, H, W = x.shape
+    if gamma is None or beta is None:
+        raise TypeError("batchnorm_add_relu_fwd: gamma and beta must be tensors")
+    _req_channels(C, gamma=gamma, beta=beta, running_mean=run_mean, running_var=run_var)
     y = torch.empty_like(x)
     mean = torch.empty(C, dtype=torch.float32, device=x.device)
     rstd = torch.empty(C, dtype=torch.float32, device=x.device)
@@ -1903,8 +2011,13 @@ def batchnorm_add_relu_fwd(x, residual, gamma, beta, run_mean, run_var, eps, mom
 
 def batchnorm_add_relu_bwd(dy, x, y, gamma, beta, mean, rstd, need_dx=True, out=None):
     """-> (dx, d_residual, dgamma, dbeta); out = (dgamma, dbeta) buffers to accumulate into, or None to allocate"""
-    _req(dy, "dy"); _req(x, "x"); _req(y, "y")
-    B, C, H, W = x.shape
+    B, C, H, W = _req_map(x)
+    _req_like(dy, "dy", x, "x"); _req_like(y, "y", x, "x")
+    if any(v is None for v in (gamma, beta, mean, rstd)):
+        raise TypeError("batchnorm_add_relu_bwd: gamma, beta, mean and rstd must be tensors")
+    _req_channels(C, gamma=gamma, beta=beta, mean=mean, rstd=rstd)
+    if out is not None:
+        _req_channels(C, dgamma=out[0], dbeta=out[1])
     dx = torch.empty_like(x) if need_dx else None
     dres = torch.empty_like(x)
     dg, db = out if out is not None else (torch.empty(C, dtype=torch.float32, device=x.device),
@@ -1917,10 +2030,12 @@ def batchnorm_add_relu_bwd(dy, x, y, gamma, beta, mean, rstd, need_dx=True, out=
 
 def batchnorm_eval(x, gamma, beta, run_mean, run_var, eps, act, slope, dy=None):
     """eval-mode batch norm (+act); with dy: the gradient w.r.t. x"""
-    _req(x, "x"); _req(gamma, "gamma"); _req(beta, "beta"); _req(run_mean, "running_mean"); _req(run_var, "running_var")
+    B, C, H, W = _req_map(x)
+    if any(v is None for v in (gamma, beta, run_mean, run_var)):
+        raise TypeError("batchnorm_eval: gamma, beta and the running statistics must be tensors")
+    _req_channels(C, gamma=gamma, beta=beta, running_mean=run_mean, running_var=run_var)
     if dy is not None:
-        _req(dy, "dy")
-    B, C, H, W = x.shape
+        _req_like(dy, "dy", x, "x")
     out = torch.empty_like(x)
     _check(lib().scda_batchnorm_eval_hip(_p(x), _p(dy), _p(out), _p(gamma), _p(beta), _p(run_mean), _p(run_var), B, C, H * W, eps, act,
                                          slope, _stream()), "scda_batchnorm_eval_hip")
@@ -2016,6 +2131,9 @@ def bce_fwd(p, t):
 
 
 def bce_bwd(p, t, g):
+    _req(p, "p"); _req(t, "t"); _req(g, "g")
+    if p.numel() != t.numel() or g.numel() != 1:
+        raise ValueError("bce: shape mismatch")
     dp = torch.empty_like(p)
     _check(lib().scda_bce_bwd_hip(_p(p), _p(t), p.numel(), _p(g), _p(dp), _stream()), "scda_bce_bwd_hip")
     return dp
