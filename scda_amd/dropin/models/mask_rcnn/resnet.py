@@ -35,16 +35,28 @@ def folded_conv_bn(x, conv, bn, act):
     """conv -> eval-mode BN (-> ReLU) of a FROZEN pair (stem and layer1: models/mask_rcnn/resnet.py:213-238 keep them in eval mode
     with requires_grad = False) as ONE convolution: w' = w * gamma / sqrt(var + eps) per output channel, b' = beta - mean * gamma /
     sqrt(var + eps), bias and ReLU in the MFMA kernel's epilogue -- the affine map of a frozen batch norm is a constant, so the
-    separate pass over the layer's output (69 MB per layer1 map at 800 x 1344) disappears.  The folded tensors are cached and
-    rebuilt when any of the five source tensors changes (load_state_dict copies in place and bumps their versions)."""
-    key = tuple(t._version for t in (conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var)) + (conv.weight.data_ptr(),)
+    separate pass over the layer's output (69 MB per layer1 map at 800 x 1344) disappears."""
+    w, b = folded_params(conv, bn)
+    return A.conv2d(x, w, b, conv.stride[0], conv.padding[0], act, 0.0, (None, False), conv.row_period)
+
+
+def folded_params(conv, bn):
+    """-> (w', b') of folded_conv_bn, cached on the conv and rebuilt when any of the five source tensors changes.  A source is the
+    same when it is the same tensor OBJECT (Module.to() / .cpu() / .float() replace every buffer by a new tensor whose version starts
+    at 0 again, and the allocator may hand it the address of the old one), at the same address (the same calls re-home a Parameter
+    under its old object and version) with the same version (load_state_dict and every other in-place torch op bump it), in the same
+    native.WEIGHT_EPOCH (a collective or a kernel writes through raw pointers and moves none of the above: its author bumps the
+    epoch, as broadcast_params and checkpoint.restore do)."""
+    src = (conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var)
+    key = tuple(t._version for t in src) + tuple(t.data_ptr() for t in src) + (N.WEIGHT_EPOCH[0],)
     cache = getattr(conv, "_scda_folded", None)
-    if cache is None or cache[0] != key:
+    if cache is None or cache[0] != key or any(a is not t for a, t in zip(cache[3], src)):
         with torch.no_grad():
             k = bn.weight / torch.sqrt(bn.running_var + bn.eps)
-            cache = (key, (conv.weight * k.view(-1, 1, 1, 1)).contiguous(), (bn.bias - bn.running_mean * k).contiguous())
+            # (the cache holds the five sources themselves: an object that is alive cannot lend its identity to a successor)
+            cache = (key, (conv.weight * k.view(-1, 1, 1, 1)).contiguous(), (bn.bias - bn.running_mean * k).contiguous(), src)
         conv._scda_folded = cache
-    return A.conv2d(x, cache[1], cache[2], conv.stride[0], conv.padding[0], act, 0.0, (None, False), conv.row_period)
+    return cache[1], cache[2]
 
 
 class Bottleneck(nn.Module):

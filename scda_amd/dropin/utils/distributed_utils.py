@@ -5,8 +5,9 @@
   571 MB).  Here each model's gradients live in ONE flat fp32 bucket (scda_amd.flat.FlatParams); the call is a single
   all-reduce on that bucket.  Sum semantics are unchanged (losses are pre-divided by world_size by the caller).
   With async_op=True the collective runs on RCCL's stream and overlaps the next phase; call .wait() before the step.
-* broadcast_params(model): one broadcast of the flat parameter bucket + one per buffer (BN running stats, int64
-  counters), instead of one per state_dict entry.
+* broadcast_params(model): one broadcast of the flat parameter bucket + one per state_dict entry outside it (buffers: BN
+  running stats, int64 counters; frozen parameters), instead of one per state_dict entry; the packed-weight caches of
+  the receiving rank are invalidated (a collective moves no tensor version).
 * dist_init(port, backend): SLURM variables as in the reference, with a RANK/WORLD_SIZE/LOCAL_RANK (torchrun)
   fallback; always rendezvous on 127.0.0.1 unless MASTER_ADDR is set.
 """
@@ -85,14 +86,22 @@ def broadcast_params(model):
     """rank 0's parameters and buffers to everyone"""
     from scda_amd.layers import flush_counters
     flush_counters(model)              # BatchNorm batch counters are kept on the host between reads of the buffer
+    from scda_amd import native
     flat = _flat_of(model)
     if flat is not None:
         dist.broadcast(flat.data, 0)
-        for b in model.buffers():
-            dist.broadcast(b, 0)
-        return
-    for p in model.state_dict().values():
-        dist.broadcast(p, 0)
+        # what state_dict() holds and the bucket does not: buffers, and the parameters with requires_grad = False (a frozen stem,
+        # frozen BN affines), which FlatParams leaves where they are
+        for t in model.state_dict().values():
+            if not flat.holds(t):
+                dist.broadcast(t, 0)
+        flat.epoch += 1
+    else:
+        for p in model.state_dict().values():
+            dist.broadcast(p, 0)
+    # a collective writes through raw pointers: no tensor version moves, and a rank that ran a forward pass before this call would keep
+    # convolving with the packed copies of its OWN old weights (native._pack_tag)
+    native.WEIGHT_EPOCH[0] += 1
 
 
 def _first_slurm_host(nodelist):

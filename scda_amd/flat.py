@@ -58,6 +58,10 @@ class FlatParams:
         return t is not None and t.device == bucket.device and \
             bucket.data_ptr() <= t.data_ptr() < bucket.data_ptr() + self.numel * 4
 
+    def holds(self, t):
+        """`t` (a parameter, or an alias of one such as a state_dict() entry) lives inside the parameter bucket"""
+        return self._inside(t, self.data)
+
     def check_aliases(self, span=None):
         """Every parameter must still be a view of `data` and its gradient a view of `grad`.  A gradient that was set to None
         or replaced by a fresh tensor (Module.zero_grad(set_to_none=True), an optimiser other than FlatAdam) is copied into the

@@ -1286,6 +1286,19 @@ WEIGHT_EPOCH = [0]   # fallback epoch for weights that are not part of a FlatPar
 _PACK_CACHE = {}
 
 
+def _pack_tag(w):
+    """what a packed copy of `w` was made from: the pack cache serves an entry only under an equal tag.  A weight inside a FlatParams
+    bucket is written three ways, and each moves one field: a torch op on the Parameter bumps w._version; a torch op on the bucket
+    (flat.data, FlatAdam's bucket Parameter, any detached alias or slice of them: they share ONE counter, which `p.data = view` does
+    NOT hand to the Parameter) bumps flat.data._version; a kernel or collective that writes through raw pointers bumps neither, so
+    whoever launches it bumps flat.epoch (FlatAdam.step, checkpoint.restore, broadcast_params) -- or WEIGHT_EPOCH for a weight
+    outside every bucket."""
+    flat = getattr(w, "_scda_flat", None)
+    if flat is None:
+        return (w._version, WEIGHT_EPOCH[0], 0, tuple(w.shape))
+    return (w._version, flat.epoch, flat.data._version, tuple(w.shape))
+
+
 def conv2d_pack_weight(w, for_dgrad=False, cache=True):
     """[Cout,Cin,KH,KW] -> the library's GEMM-ready layout for the forward / data-gradient kernel (see scda_ops.h).
     Cached per (storage, direction) until the weight changes (tensor version or optimiser epoch)."""
@@ -1295,8 +1308,7 @@ def conv2d_pack_weight(w, for_dgrad=False, cache=True):
     # on every call and would leave a dead entry behind each time
     cache = cache and isinstance(w, torch.nn.Parameter)
     key = (w.data_ptr(), for_dgrad)
-    flat = getattr(w, "_scda_flat", None)
-    tag = (w._version, flat.epoch if flat is not None else WEIGHT_EPOCH[0], tuple(w.shape))
+    tag = _pack_tag(w)
     if cache:
         hit = _PACK_CACHE.get(key)
         # valid only for the very same tensor object (a freed temporary's address may be reused by another weight)
@@ -1372,8 +1384,7 @@ def conv2d_wino_pack(w, for_dgrad=False, cache=True):
     Cout, Cin, KH, KW = w.shape
     cache = cache and isinstance(w, torch.nn.Parameter)
     key = (w.data_ptr(), 2 + int(for_dgrad))
-    flat = getattr(w, "_scda_flat", None)
-    tag = (w._version, flat.epoch if flat is not None else WEIGHT_EPOCH[0], tuple(w.shape))
+    tag = _pack_tag(w)
     if cache:
         hit = _PACK_CACHE.get(key)
         if hit is not None and hit[0] == tag and hit[2]() is w:
@@ -1477,7 +1488,7 @@ def conv2d_pack_all(flat):
     for w, d, off, n in entries:
         if w.data_ptr() < flat.data.data_ptr():   # parameter was re-homed: fall back to the lazy path for it
             continue
-        _PACK_CACHE[(w.data_ptr(), d)] = ((w._version, flat.epoch, tuple(w.shape)), out[off:off + n], weakref.ref(w))
+        _PACK_CACHE[(w.data_ptr(), d)] = (_pack_tag(w), out[off:off + n], weakref.ref(w))
 
 
 def conv2d_fwd(x, w, bias, stride, pad, act=ACT_NONE, slope=0.01, row_period=0):
